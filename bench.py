@@ -8,18 +8,31 @@ ljspeech hyper-parameters, about 620 frames = 7.2 s of audio).  Inputs (ids) and
 outputs (waveforms) are device resident; the only host traffic inside a step is
 the frame-count read-back the data-dependent length needs.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs:
+set-up, W warm-up steps plus one warm-up call on every in-flight slot, ONE timed
+region of exactly K steps, and the result line (`value` = utterances/s over
+that region, `ms_per_step` = its milliseconds per step).  `--dump-outputs DIR`
+writes what the last timed step returned (waveform, int16 waveform, frame
+counts) as DIR/*.npy; the inputs are seeded, so two builds can be compared
+output for output.
+
+`--full` adds everything else the line has carried: the profiled pass and the
+roofline, repeated regions (median), single-stream latency, the call-coalescing,
+denoiser, steady-state and vocoder-only regions, the fp16 and split-bf16 modes,
+BASELINE configs 3, 4 and 5, the micro-batched leg and the CPU baseline.
+
 `--gpus N` (N > 1): one process per GPU.  Started by the driver under
 `python -m torch.distributed.run` the ranks are already there; started by hand
 without that environment, this script re-executes itself under
 torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1).  Rank 0
 builds the folded weight blobs and broadcasts them over RCCL/xGMI once;
 utterances are independent, so the timed region has no collective ("weak"
-scaling: every rank synthesises its own K utterances; max over ranks).  After
-the headline region every run also times BASELINE config 3 — 256 utterances,
-P ~ clip(N(120,15),60,200), LPT-sharded over the ranks, audio gathered to rank 0
-in sentence order — and reports it as `config3` (strong scaling), and BASELINE
-config 5 — 210 sentences cycling three resident voices, in-order delivery — as
-`config5` (time to first audio, sustained x real time).
+scaling: every rank synthesises its own K utterances; max over ranks).  With
+`--full`, after the headline region the run also times BASELINE config 3 — 256
+utterances, P ~ clip(N(120,15),60,200), LPT-sharded over the ranks, audio
+gathered to rank 0 in sentence order — and reports it as `config3` (strong
+scaling), and BASELINE config 5 — 210 sentences cycling three resident voices,
+in-order delivery — as `config5` (time to first audio, sustained x real time).
 
 `--device cpu --library <emulator .so> --tiny` runs the same code path on the
 CPU emulator build with gloo (tests/test_bench_path.py, world size 2).
@@ -432,7 +445,14 @@ def main():
                     help="utterances per call (rows of one padded batch). Default 1 = BASELINE.json's quoted configuration")
     ap.add_argument("--repeats", type=int, default=0,
                     help="how many times the K-step region is timed (each bracketed by barrier + synchronize); the line "
-                         "reports the median.  0 = as many as fit ~2 s, at least 5")
+                         "reports the median.  0 = once in a plain run; with --full as many as fit ~2 s, at least 5")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: profiled pass and roofline, repeated regions, single-stream latency, "
+                         "call-coalescing / denoiser / steady-state / vocoder-only regions, fp16 and split-bf16 modes, BASELINE "
+                         "configs 3, 4 and 5, the micro-batched leg and the CPU baseline (the --no-* switches below apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy: waveform [B, n] "
+                         "float32, waveform_int16 [B, n] as float32, frames [B] float64 (rows zero-padded past their length)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-steady-state", action="store_true", help="skip the 10 x K-step regions reported as `steady_state`")
     ap.add_argument("--voc-only-sleep-ms", type=float, default=0.0,
@@ -614,12 +634,38 @@ def main():
         # concurrent batch-1 calls may ride fused padded calls (csrc/host_join.h): any worker may lead a pass of up to `conc` rows
         eng.reserve(conc + 1, g, v, max_batch=conc, max_ids=max(args.ids, 200), max_frames=max_frames)
 
+    last = {}  # the slot whose buffers hold the last headline step (n_utts - 1) and its frame counts (--dump-outputs)
+
     def step(i, slot=0, denoiser=0.0):
         """One utterance (one batch of B) through the fused call; returns its frame count."""
         fr = eng.synthesize_raw(g, v, ids_dev[i * B].data_ptr(), lens, args.ids, 0.667, args.length_scale,
                                 wav_f32[slot].data_ptr(), wav_i16[slot].data_ptr(), max_samples, seed=1234 + i,
                                 audio_settings=s, denoiser_strength=denoiser, flags=io_flags)
+        if i == n_utts - 1:
+            last.update(slot=slot, frames=fr.copy())
         return int(fr.sum())
+
+    def dump_outputs(out_dir):
+        """What the last timed step returned to its caller, as float32 / float64 .npy files (at most 64 MB: rows beyond that
+        are a fixed sample, listed in rows.npy)."""
+        sync()
+        fr = last["frames"].astype(np.int64)
+        n = int(fr.max()) * hop
+        rows = np.arange(B)
+        if 2 * 4 * B * n > 64 * 2 ** 20:
+            rows = np.sort(np.random.default_rng(0).choice(B, max(1, (64 * 2 ** 20) // (8 * max(1, n))), replace=False))
+        f32 = wav_f32[last["slot"]].view(B, max_samples)[:, :n].cpu().numpy()[rows]
+        i16 = wav_i16[last["slot"]].view(B, max_samples)[:, :n].cpu().numpy()[rows].astype(np.float32)
+        for r, b in enumerate(rows):  # a row ends at its own frame count; the buffer past it is not output
+            f32[r, fr[b] * hop:] = 0.0
+            i16[r, fr[b] * hop:] = 0.0
+        d = Path(out_dir)
+        d.mkdir(parents=True, exist_ok=True)
+        np.save(d / "waveform.npy", np.ascontiguousarray(f32, np.float32))
+        np.save(d / "waveform_int16.npy", np.ascontiguousarray(i16, np.float32))
+        np.save(d / "frames.npy", fr[rows].astype(np.float64))
+        if len(rows) < B:
+            np.save(d / "rows.npy", rows.astype(np.float64))
 
     from concurrent.futures import ThreadPoolExecutor
 
@@ -659,40 +705,50 @@ def main():
         return out
 
     # ---- warm-up: W steps single-stream, then every in-flight slot on the longest shape
+    eng.set_option("serial_branches", 1 if args.serial_branches else 0)
     for i in range(W):
         step(i)
     if conc > 1:
         run_steps(0, max(W, conc))
-        if dn_ok:
+        if dn_ok and args.full:
             run_steps(0, max(W, conc), denoiser=0.005)
-    if dn_ok:
+    if dn_ok and args.full:
         step(0, 0, 0.005)
     barrier()
 
-    # ---- profiled pass: HIP events around every launch.  The product schedule keeps a call on ONE
-    # stream (the three MRF chains' same-geometry convs go out as one grouped launch), so every
-    # launch is timed alone on the GPU and its duration is what the roofline uses.
-    # --serial-branches times the un-grouped, one-conv-per-launch form instead.
-    eng.set_profiling(True)
-    eng.set_option("serial_branches", 1 if args.serial_branches else 0)
-    step(W)  # that schedule's workspace shape, outside the measured pass
-    eng.profile_reset()
-    barrier()
-    t0 = time.perf_counter()
-    frames = sum(step(i) for i in range(W, n_utts))
-    barrier()
-    dt_prof = time.perf_counter() - t0
-    prof = eng.profile()
-    prof_kernels = eng.profile_kernels()
-    eng.set_profiling(False)
-    eng.set_option("serial_branches", 1 if args.serial_branches else 0)
-    step(W)
+    if args.full:
+        # ---- profiled pass: HIP events around every launch.  The product schedule keeps a call on ONE
+        # stream (the three MRF chains' same-geometry convs go out as one grouped launch), so every
+        # launch is timed alone on the GPU and its duration is what the roofline uses.
+        # --serial-branches times the un-grouped, one-conv-per-launch form instead.
+        eng.set_profiling(True)
+        eng.set_option("serial_branches", 1 if args.serial_branches else 0)
+        step(W)  # that schedule's workspace shape, outside the measured pass
+        eng.profile_reset()
+        barrier()
+        t0 = time.perf_counter()
+        frames = sum(step(i) for i in range(W, n_utts))
+        barrier()
+        dt_prof = time.perf_counter() - t0
+        prof = eng.profile()
+        prof_kernels = eng.profile_kernels()
+        eng.set_profiling(False)
+        eng.set_option("serial_branches", 1 if args.serial_branches else 0)
+        step(W)
 
-    # ---- the timed regions (event-free): exactly K steps each, repeated; medians reported
-    est = max(1e-4, min(timed(lambda: run_steps(W, n_utts, threads=1), 1)))
-    repeats = args.repeats if args.repeats > 0 else int(min(40, max(5, np.ceil(2.0 / est))))
-    t_single = timed(lambda: run_steps(W, n_utts, threads=1), repeats)
-    t_flight = timed(lambda: run_steps(W, n_utts), repeats) if conc > 1 else t_single
+        # ---- the timed regions (event-free): exactly K steps each, repeated; medians reported
+        est = max(1e-4, min(timed(lambda: run_steps(W, n_utts, threads=1), 1)))
+        repeats = args.repeats if args.repeats > 0 else int(min(40, max(5, np.ceil(2.0 / est))))
+        t_single = timed(lambda: run_steps(W, n_utts, threads=1), repeats)
+        t_flight = timed(lambda: run_steps(W, n_utts), repeats) if conc > 1 else t_single
+    else:
+        # ---- the timed region (event-free): exactly K steps, once unless --repeats says otherwise
+        repeats = max(1, args.repeats)
+        region_frames = []
+        t_flight = timed(lambda: region_frames.append(run_steps(W, n_utts)), repeats)
+        frames, dt_prof, t_single = region_frames[-1], 0.0, [0.0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs)
     # the same region with the other setting of option "call_coalesce" (csrc/host_join.h: concurrent batch-1 callers become the
     # rows of fused padded calls), reported next to the headline — which runs the library's DEFAULT
     t_flight_nc = t_flight
@@ -700,7 +756,7 @@ def main():
     cs0 = cs1 = (0, 0)
     cc_default = eng.get_call_coalesce_default()
     cc_other = 0 if cc_default else args.call_coalesce_lanes
-    if conc > 1 and B == 1:
+    if args.full and conc > 1 and B == 1:
         eng.set_option("call_coalesce", cc_other)
         run_steps(0, max(W, conc))
         cs0 = eng.coalesce_stats()
@@ -727,13 +783,13 @@ def main():
             t_steady_nc = timed(run_long_cc, 2)
         eng.set_option("call_coalesce", cc_default)
         run_steps(0, max(W, conc))
-    t_dn = timed(lambda: run_steps(W, n_utts, denoiser=0.005), max(3, repeats // 3)) if dn_ok else [float("nan")]
+    t_dn = timed(lambda: run_steps(W, n_utts, denoiser=0.005), max(3, repeats // 3)) if dn_ok and args.full else [float("nan")]
     # ---- steady state: the SAME calls in regions ten times as long.  A K-step region starts on an idle GPU (every caller begins
     # with its acoustic pass: ~2 ms before the first vocoder launch) and drains at its end (the last calls run with fewer and
     # fewer others to fill their launches' tails); at K = 20 that is ~4 % of a 74 ms region.  Reported next to the headline,
     # which keeps the K-step definition.
     t_steady, K_steady = None, 0
-    if conc > 1 and not args.tiny and not args.no_steady_state:
+    if args.full and conc > 1 and not args.tiny and not args.no_steady_state:
         K_steady = 10 * K
 
         def run_long():
@@ -759,16 +815,18 @@ def main():
         t_steady = timed(run_long, 3)
     # host CPU seconds (all threads of this process) over one more pass of the headline region: what a rank costs the host
     # per utterance — the one term of the 1 -> 8 GPU curve that the ranks share (8 ranks x `conc` threads on one host)
-    barrier()
-    c0, w0 = time.process_time(), time.perf_counter()
-    run_steps(W, n_utts)
-    barrier()
-    host_cpu_s, host_wall_s = time.process_time() - c0, time.perf_counter() - w0
+    host_cpu_s = host_wall_s = 0.0
+    if args.full:
+        barrier()
+        c0, w0 = time.process_time(), time.perf_counter()
+        run_steps(W, n_utts)
+        barrier()
+        host_cpu_s, host_wall_s = time.process_time() - c0, time.perf_counter() - w0
     # what GlowTTS costs UNDER LOAD: the same K steps with the acoustic model taken out — every call is the vocoder alone on
     # the device-resident mel GlowTTS produced for that utterance (same in-flight count, same buffers); the difference to the
     # headline region is GlowTTS's price per utterance when its launches compete with other calls' vocoder launches
     t_voc = t_voc_steady = None
-    if B == 1 and not args.tiny:
+    if args.full and B == 1 and not args.tiny:
         mels = {i: eng.glow_infer_raw(g, ids_dev[i].data_ptr(), lens, args.ids, 0.667, args.length_scale, seed=1234 + i, audio_settings=s,
                                       flags=ffi.IN_DEVICE) for i in range(W, n_utts)}
         if mels:
@@ -830,7 +888,7 @@ def main():
     half = None
     x3_flight = 0.0
     glow_f16 = False
-    if args.precision == "f32" and (not args.tiny or args.tiny_half) and not args.no_half_mode and not args.acoustic_f16:
+    if args.full and args.precision == "f32" and (not args.tiny or args.tiny_half) and not args.no_half_mode and not args.acoustic_f16:
         eng.set_precision(v, ffi.PRECISION_F16)
         # `half` on the acoustic model: the decoder's WaveNets in fp16 (0), or a reported no-op on a geometry wn_f16.h does not cover
         glow_f16 = args.half_acoustic == "f16" and eng.set_precision(g, ffi.PRECISION_F16) == 0
@@ -877,7 +935,7 @@ def main():
 
     # ---- BASELINE config 3: 256 utterances, LPT-sharded over the ranks, ordered gather (strong scaling)
     c3 = None
-    if not args.no_config3:
+    if args.full and not args.no_config3:
         rows = config3_ids(ghp.num_symbols, n=args.config3_utterances) if not args.tiny else \
             config3_ids(ghp.num_symbols, n=args.config3_utterances, mean=12, std=3, lo=5, hi=20)
         lengths = [len(r) for r in rows]
@@ -945,7 +1003,7 @@ def main():
     # de V=54 / fr V=42), dealt round-robin to the ranks, each rank keeps `--config5-threads` batch-1 calls in flight
     # and delivers its sentences in order (larynx/__main__.py:229-268 raw-stream semantics)
     c5 = None
-    if not args.no_config5 and not args.tiny and on_gpu:
+    if args.full and not args.no_config5 and not args.tiny and on_gpu:
         voices = [(ghp, g)]
         for vhp2, seed2 in ((HP.THORSTEN, 2001), (HP.SIWIS, 2002)):
             voices.append((vhp2, eng.load_glow(vhp2, synthetic.make_glow_state_dict(vhp2, seed=seed2))))  # seeded: identical on every rank
@@ -1002,37 +1060,18 @@ def main():
     # (P = 19 ... 120: the golden batch of tests/golden/batch8, whose every row the parity suite checks against the
     # reference) per call, fused entry, device-resident ids and waveforms; every rank runs the same batch (weak scaling)
     c4 = None
-    if not args.no_config4 and not args.tiny and on_gpu:
+    if args.full and not args.no_config4 and not args.tiny and on_gpu:
         c4 = config4_leg(eng, args, dev, barrier, timed, pool, conc, world, red_dev, use_dist, s)
 
     # ---- the same utterances as micro-batches of 8 (2 calls in flight): what batching buys on top of the batch-1 headline
     mb = None
-    if B == 1 and on_gpu and not args.tiny and not args.no_micro_batch and args.precision == "f32":
+    if args.full and B == 1 and on_gpu and not args.tiny and not args.no_micro_batch and args.precision == "f32":
         mb = micro_batch_leg(eng, g, v, ghp, vhp, args, dev, barrier, timed, world, red_dev, use_dist, s, rank)
 
     if rank == 0:
         audio_s = total_frames * hop / SAMPLE_RATE  # audio produced by all ranks in one K-step region
         utt_s = world * K * B / dt_flight
         fpu = total_frames / (world * K * B)
-        traffic = None
-        tpath = REPO / "profiles" / f"{ROUND}_roofline_traffic.json"
-        if not tpath.is_file():
-            tpath = REPO / "profiles" / "r01_roofline_traffic.json"
-        if tpath.is_file():  # PMC counters cannot be read from inside this process: committed rocprofv3 passes
-            tj = json.loads(tpath.read_text())
-            traffic = tj.get("hbm_bytes_per_launch", tj.get("hbm_bytes_per_launch_raw"))
-        dom = prof["conv_mfma.hifigan_resblock"]
-        # The roofline uses the RAW event time of every launch (HIP events on the launch stream): on the boxes where both exist it
-        # agrees with rocprofv3's kernel durations of the same command (profiles/r05_events_vs_rocprof.txt), which is what the
-        # committed profiles/ summary holds.  The same figures minus the cost of an EMPTY event pair (measured here on an idle
-        # stream: ~4.5 us) are kept under `*_minus_event_overhead`: that subtraction over-corrects (part of the records' cost
-        # overlaps the kernel) and is NOT the headline.
-        ev_us = eng.profile_event_overhead_us() if on_gpu else 0.0
-        dom_ms_raw = dom["ms"]
-        dom_ms = max(dom_ms_raw - 1e-3 * ev_us * dom["launches"], 0.5 * dom_ms_raw)
-        dom_tf = dom["flop"] / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
-        dom_tf_raw = dom["flop"] / (dom_ms_raw * 1e-3) / 1e12 if dom_ms_raw > 0 else 0.0
-        all_conv_ms = sum(v_["ms"] for k_, v_ in prof.items() if k_.startswith("conv_mfma"))
         flop_utt = algorithmic_flop(args.ids, fpu, quality)
         out = {
             "metric": "utterances_per_sec",
@@ -1061,170 +1100,194 @@ def main():
                 "calls_in_flight_per_gpu": conc,
             },
             "timing": {
-                "method": f"K={K} steps bracketed by barrier + synchronize, repeated {repeats}x after {W} warm-up steps and a full "
-                          f"warm-up of every in-flight slot; value / ms_per_step = the median repeat (max over ranks)",
+                "method": f"K={K} steps bracketed by barrier + synchronize, "
+                          + (f"repeated {repeats}x" if repeats > 1 else "timed once")
+                          + f" after {W} warm-up steps and a full warm-up of every in-flight slot; value / ms_per_step = "
+                          + ("the median repeat" if repeats > 1 else "that region") + " (max over ranks)",
                 "repeats": repeats,
                 "ms_per_step_min": 1e3 * dt_flight_min / K,
                 "ms_per_step_max": 1e3 * dt_flight_max / K,
             },
             "rtf": dt_flight * world / audio_s,
             "x_realtime_per_gpu": audio_s / (dt_flight * world),
-            "latency_ms_single_stream": 1e3 * dt_single / K,  # per call (= per utterance at batch 1), same method
-            "latency_ms_single_stream_min": 1e3 * dt_single_min / K,
-            "utterances_per_sec_single_stream": world * K * B / dt_single,
-            "rtf_single_stream": dt_single * world / audio_s,
-            "x_realtime_single_stream": audio_s / (dt_single * world),
             "end_to_end_tflops_per_gpu": flop_utt * K * B / dt_flight / 1e12,
-            # (max over ranks) host CPU time of one pass of the headline region / its utterances: all threads of the rank's
-            # process — the Python callers, ctypes, the HIP runtime's launch path (~170 launches per utterance)
-            "host_cpu_ms_per_utterance": 1e3 * host_cpu_max / (K * B),
-            "host_cpu_cores_busy_per_rank": host_cpu_max / host_wall_max if host_wall_max > 0 else None,
-            "steady_state": None if dt_steady <= 0 else {
-                "what": f"the same calls, the same {conc} in flight, in timed regions of {K_steady} steps instead of {K} (3 repeats, median; same "
-                        "bracketing).  NOT the headline: `value` keeps the K-step region, which starts on an idle GPU (every caller begins "
-                        "with its acoustic pass) and drains at its end — about 4 % of a 74 ms region at K = 20",
-                "steps": K_steady,
-                "utterances_per_sec": world * K_steady * B / dt_steady,
-                "ms_per_step": 1e3 * dt_steady / K_steady,
-                "vocoder_only_utterances_per_sec": None if dt_voc_steady <= 0 else world * K_steady * B / dt_voc_steady,
-                "glow_under_load_ms": None if dt_voc_steady <= 0 else 1e3 * (dt_steady - dt_voc_steady) / K_steady,
-            },
-            "glow_under_load_ms": None if dt_voc <= 0 else 1e3 * (dt_flight - dt_voc) / K,
-            "vocoder_only_under_load": None if dt_voc <= 0 else {
-                "what": "the headline region with GlowTTS taken out: the same K utterances, the same calls in flight, each call the vocoder "
-                        "alone (mi355tts_hifigan_infer_padded) on the device-resident mel GlowTTS produced for it; "
-                        "glow_under_load_ms = ms_per_step - this = what the acoustic model costs per utterance when its ~140 small launches "
-                        "compete with other calls' vocoder launches (alone it takes latency_ms_single_stream minus the vocoder's share)",
-                "ms_per_step": 1e3 * dt_voc / K,
-                "utterances_per_sec": world * K * B / dt_voc,
-            },
-            "call_coalescing": None if not (conc > 1 and B == 1) else {
-                "what": f"option call_coalesce = {cc_other} (the library default, which the headline runs, is {cc_default}): concurrent batch-1 "
-                        "mi355tts_synthesize callers become the rows of fused padded calls — acoustic pass and vocoder — at most that many "
-                        "in flight (csrc/host_join.h); rows equal their solitary calls to f32 round-off (tests/test_emu_coalesce.py, "
-                        "tests/test_gpu_parity.py::test_coalesced_calls_equal_their_solitary_results).  NOT the headline: the same timed "
-                        "region with the option at its other setting",
-                "call_coalesce": cc_other,
-                "rows_per_pass": (cs1[1] - cs0[1]) / max(1, cs1[0] - cs0[0]),
-                "utterances_per_sec": world * K * B / dt_flight_nc,
-                "ms_per_step": 1e3 * dt_flight_nc / K,
-                "steady_state_utterances_per_sec_rank0": None if not t_steady_nc else 10 * K * B / float(np.median(t_steady_nc)),
-            },
-            "denoiser_on": None if not dn_ok else {
-                "denoiser_strength": 0.005,
-                "note": "the reference CLI/server default (larynx/__main__.py:512-516); STFT denoiser on the device",
-                "ms_per_step": 1e3 * dt_dn / K,
-                "utterances_per_sec": world * K * B / dt_dn,
-            },
-            "half_mode": None if not half else {
-                "dtype": "f16: the native fp16 vocoder — fp16 weights, fp16 activation planes in HBM between ALL layers (conv_pre, upsamplers, every "
-                         "ResBlock conv, conv_post), one v_mfma_f32_32x32x16_f16 per product, f32 accumulate (csrc/conv_f16.h, hifigan_f16.h); "
-                         + ("GlowTTS: the decoder's WaveNets in fp16, one launch per coupling block (csrc/wn_f16.h); encoder, durations, "
-                            "start / end convs, coupling and InvConvNear in f32" if glow_f16 else "GlowTTS in f32"),
-                "acoustic_model": "f16 decoder WaveNets (wn_f16_kernel)" if glow_f16 else "f32",
-                "what": "the reference's `half` switch (`.half()` on both models, larynx/glow_tts.py:90-91, larynx/hifi_gan.py:96-97) on this backend; "
-                        "NOT the headline — reported next to it",
-                "parity": "vocoder: waveform error vs the reference's f32 output no larger than the reference's OWN generator under .half() on the same "
-                          "input (tests/golden/*.npz: ref_half_rms, made by oracle/make_golden.py); acoustic model: mel error no larger than the "
-                          "reference's OWN decoder under .half() (tests/golden/glow_half_reference.json, oracle/make_golden_glow_half.py); both: the fused "
-                          "call within the reference's two models under .half().  Asserted per golden case in tests/test_gpu_parity.py::"
-                          "test_f16_mode_against_the_reference, ::test_f16_acoustic_mode_against_the_reference, ::test_f16_fused_call_against_the_reference",
-                "utterances_per_sec": world * K * B / dt_half_flight,
-                "ms_per_step": 1e3 * dt_half_flight / K,
-                "latency_ms_single_stream": 1e3 * dt_half_single / K,
-                "x_realtime_per_gpu": audio_s / (dt_half_flight * world),
-                "resblock_class_ms_per_step": half[2]["ms"] / K,
-                "profile_ms_per_step": {k: c["ms"] / K for k, c in half[3].items() if c["launches"]},
-                # ONE fp16 MFMA per product: executed matrix work = the algorithmic FLOPs
-                "roofline": None if half[2]["ms"] <= 0 else {
-                    "kernel": "HiFi-GAN ResBlock launches in the fp16 mode: conv_f16_group_kernel (the three MRF chains' same-geometry convs per launch), "
-                              "HIP events per launch, single stream",
-                    "bound": "mfma",
-                    "achieved": half[2]["flop"] / (half[2]["ms"] * 1e-3) / 1e12,
-                    "peak": BF16_PEAK_TFLOPS,
-                    "unit": "TFLOP/s",
-                    "frac": half[2]["flop"] / (half[2]["ms"] * 1e-3) / 1e12 / BF16_PEAK_TFLOPS,
-                    "note": "algorithmic FLOPs (one MFMA per product) / dense fp16 peak (= the bf16 figure); launches measured one call at a time",
-                    "launches": half[2]["launches"],
-                    "avg_launch_us": 1e3 * half[2]["ms"] / max(1, half[2]["launches"]),
-                    "frac_minus_event_overhead": half[2]["flop"] / (max(half[2]["ms"] - 1e-3 * ev_us * half[2]["launches"], 0.5 * half[2]["ms"]) * 1e-3) / 1e12 / BF16_PEAK_TFLOPS,
-                    "by_kernel": by_kernel_table(half[4]),
-                },
-            },
-            "bf16x3_mode": None if not half else {
-                "dtype": "bf16x3: ResBlock convs and upsamplers on the bf16 matrix cores with split operands (three MFMAs per product, f32 planes; "
-                         "conv_bf16.h) — the ACCURATE reduced mode: waveform RMS <= 2.9e-6 vs the reference's f32 output on the golden set",
-                "utterances_per_sec": world * K * B / dt_x3_flight if dt_x3_flight > 0 else None,
-                "ms_per_step": 1e3 * dt_x3_flight / K,
-            },
             "weight_broadcast_seconds": broadcast_s if use_dist else None,
-            "per_rank": {
-                "utterances_per_sec": [K * B / t[0] for t in per_rank],
-                "min": min(K * B / t[0] for t in per_rank), "max": max(K * B / t[0] for t in per_rank),
-                "latency_ms_single_stream": [1e3 * t[1] / K for t in per_rank],
-                "note": "each rank's own median over the repeats; `value` = all ranks' utterances / the slowest rank's time",
-            },
             "host_affinity_rank0": affinity,
             # hardware-queue group of every worker stream as mi355tts_reserve measured it (creation order; a call takes the free
             # worker whose queue carries the fewest calls: include/mi355tts.h, mi355tts_worker_queue_groups)
             "worker_queue_groups_rank0": qgroups_headline,
             "process_group": (("nccl (RCCL)" if rccl else ("gloo" if not on_gpu else f"gloo (RCCL init failed: {pg_note}); every rank folded its own seeded weights")) if use_dist else None),
-            "roofline": {
-                "kernel": "HiFi-GAN ResBlock launches: rb_group_kernel (256- and 128-channel stages: the continuous-stream tile of rb_conv.h; conv_group_kernel = the k-split tile at the utterance lengths the promotion rule leaves alone), rb_pair_group_kernel (fused conv pairs of the 64/32-channel stages on four waves, rb_pair.h)",
-                "bound": "mfma",
-                "achieved": dom_tf_raw,
-                "peak": FP32_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": dom_tf_raw / FP32_PEAK_TFLOPS,
-                "traffic": traffic,
-                "traffic_source": f"profiles/{tpath.name if tpath.is_file() else '-'} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same "
-                                  f"command, bytes per launch, FETCH_SIZE doubled per the guide's gfx950 correction for 16-B/lane reads)",
-                "algorithmic_bytes_per_launch": "in + out planes of the launch's three members: e.g. stage 1 of 'high' 3 x (20.4 + 20.4) MB = 123 MB; "
-                                                "class average 92 MB per launch (1656 MB per utterance over 18 launches)",
-                "algorithmic_flop_per_launch": dom["flop"] / max(1, dom["launches"]),
-                "launches": dom["launches"],
-                "avg_launch_us": 1e3 * dom_ms_raw / max(1, dom["launches"]),
-                "event_pair_overhead_us": ev_us,
-                "avg_launch_us_minus_event_overhead": 1e3 * dom_ms / max(1, dom["launches"]),
-                "achieved_minus_event_overhead": dom_tf,
-                "frac_minus_event_overhead": dom_tf / FP32_PEAK_TFLOPS,
-                # context, not the kernel figure: all algorithmic FLOPs of the utterances / the timed regions' wall time (GlowTTS, the
-                # upsamplers and the output tail included) — what the chip sustains with the headline's calls in flight
-                "end_to_end_under_load": {"achieved": flop_utt * K * B / dt_flight / 1e12, "frac": flop_utt * K * B / dt_flight / 1e12 / FP32_PEAK_TFLOPS,
-                                          "steady_state_achieved": None if dt_steady <= 0 else flop_utt * K_steady * B / dt_steady / 1e12,
-                                          "steady_state_frac": None if dt_steady <= 0 else flop_utt * K_steady * B / dt_steady / 1e12 / FP32_PEAK_TFLOPS,
-                                          "unit": "TFLOP/s per GPU"},
-                "share_of_step_time": dom["ms"] / (1e3 * dt_prof),
-                "all_conv_mfma_ms_per_step": all_conv_ms / K,
-                "schedule": ("serial_branches=1: one conv (or fused conv pair) per launch, the three MRF chains one after another "
-                             "on one stream" if args.serial_branches else
-                             "product schedule: one stream per call; the same-geometry convs (or fused conv pairs) of the three MRF "
-                             "chains of a step are ONE grouped launch (conv_group_kernel / rb_group_kernel / rb_pair_group_kernel), each launch timed alone"),
-                "timing": "HIP events on the launch stream around every launch, profiled pass of the same K steps; `avg_launch_us` / `achieved` / "
-                          "`frac` = the RAW event times (they agree with rocprofv3's kernel durations of the same command: "
-                          "profiles/r05_events_vs_rocprof.txt); `*_minus_event_overhead` = the same minus the cost of an EMPTY event pair "
-                          "measured in this run (`event_pair_overhead_us`) — an over-correction, kept for comparison with round 4's line",
-            },
-            "profile_ms_per_step": {k_: v_["ms"] / K for k_, v_ in prof.items()},
         }
-        out["roofline"]["by_kernel"] = by_kernel_table(prof_kernels)
-        if args.precision != "f32":
-            # the reduced modes as the line's own subject: price the class against the 16-bit matrix peak — per USEFUL product (fp16: one
-            # MFMA per product; bf16x3 executes three), and no committed PMC traffic for these kernels
-            rf = out["roofline"]
-            rf["kernel"] = ("HiFi-GAN ResBlock launches in the fp16 mode: pair_f16_group_kernel (fused conv1 + conv2 of a step, 128 / 64 / 32 channels), "
-                            "conv_f16_group_kernel (256 channels)" if args.precision == "f16" else
-                            "HiFi-GAN ResBlock launches in the split-bf16 mode: conv_bf16_group_kernel / pair_bf16_group_kernel (three bf16 MFMAs per product)")
-            rf["peak"] = BF16_PEAK_TFLOPS
-            rf["frac"] = dom_tf_raw / BF16_PEAK_TFLOPS
-            rf["frac_minus_event_overhead"] = dom_tf / BF16_PEAK_TFLOPS
-            rf["frac_note"] = "achieved = algorithmic f32-path FLOPs / time, priced against the dense 16-bit MFMA peak (2.5 PFLOP/s): per useful product"
-            e2e = rf["end_to_end_under_load"]
-            e2e["frac"] = e2e["achieved"] / BF16_PEAK_TFLOPS
-            e2e["steady_state_frac"] = None if e2e["steady_state_achieved"] is None else e2e["steady_state_achieved"] / BF16_PEAK_TFLOPS
-            rf["traffic"] = None
-            rf["traffic_source"] = "no committed PMC passes for this mode's kernels"
-            rf["algorithmic_bytes_per_launch"] = "half the f32 figure in the fp16 mode (fp16 planes), conv1's plane never leaves LDS in the fused launches"
+        if args.full:
+            traffic = None
+            tpath = REPO / "profiles" / f"{ROUND}_roofline_traffic.json"
+            if not tpath.is_file():
+                tpath = REPO / "profiles" / "r01_roofline_traffic.json"
+            if tpath.is_file():  # PMC counters cannot be read from inside this process: committed rocprofv3 passes
+                tj = json.loads(tpath.read_text())
+                traffic = tj.get("hbm_bytes_per_launch", tj.get("hbm_bytes_per_launch_raw"))
+            dom = prof["conv_mfma.hifigan_resblock"]
+            # The roofline uses the RAW event time of every launch (HIP events on the launch stream): on the boxes where both exist it
+            # agrees with rocprofv3's kernel durations of the same command (profiles/r05_events_vs_rocprof.txt), which is what the
+            # committed profiles/ summary holds.  The same figures minus the cost of an EMPTY event pair (measured here on an idle
+            # stream: ~4.5 us) are kept under `*_minus_event_overhead`: that subtraction over-corrects (part of the records' cost
+            # overlaps the kernel) and is NOT the headline.
+            ev_us = eng.profile_event_overhead_us() if on_gpu else 0.0
+            dom_ms_raw = dom["ms"]
+            dom_ms = max(dom_ms_raw - 1e-3 * ev_us * dom["launches"], 0.5 * dom_ms_raw)
+            dom_tf = dom["flop"] / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
+            dom_tf_raw = dom["flop"] / (dom_ms_raw * 1e-3) / 1e12 if dom_ms_raw > 0 else 0.0
+            all_conv_ms = sum(v_["ms"] for k_, v_ in prof.items() if k_.startswith("conv_mfma"))
+            out.update({
+                "latency_ms_single_stream": 1e3 * dt_single / K,  # per call (= per utterance at batch 1), same method
+                "latency_ms_single_stream_min": 1e3 * dt_single_min / K,
+                "utterances_per_sec_single_stream": world * K * B / dt_single,
+                "rtf_single_stream": dt_single * world / audio_s,
+                "x_realtime_single_stream": audio_s / (dt_single * world),
+                # (max over ranks) host CPU time of one pass of the headline region / its utterances: all threads of the rank's
+                # process — the Python callers, ctypes, the HIP runtime's launch path (~170 launches per utterance)
+                "host_cpu_ms_per_utterance": 1e3 * host_cpu_max / (K * B),
+                "host_cpu_cores_busy_per_rank": host_cpu_max / host_wall_max if host_wall_max > 0 else None,
+                "steady_state": None if dt_steady <= 0 else {
+                    "what": f"the same calls, the same {conc} in flight, in timed regions of {K_steady} steps instead of {K} (3 repeats, median; same "
+                            "bracketing).  NOT the headline: `value` keeps the K-step region, which starts on an idle GPU (every caller begins "
+                            "with its acoustic pass) and drains at its end — about 4 % of a 74 ms region at K = 20",
+                    "steps": K_steady,
+                    "utterances_per_sec": world * K_steady * B / dt_steady,
+                    "ms_per_step": 1e3 * dt_steady / K_steady,
+                    "vocoder_only_utterances_per_sec": None if dt_voc_steady <= 0 else world * K_steady * B / dt_voc_steady,
+                    "glow_under_load_ms": None if dt_voc_steady <= 0 else 1e3 * (dt_steady - dt_voc_steady) / K_steady,
+                },
+                "glow_under_load_ms": None if dt_voc <= 0 else 1e3 * (dt_flight - dt_voc) / K,
+                "vocoder_only_under_load": None if dt_voc <= 0 else {
+                    "what": "the headline region with GlowTTS taken out: the same K utterances, the same calls in flight, each call the vocoder "
+                            "alone (mi355tts_hifigan_infer_padded) on the device-resident mel GlowTTS produced for it; "
+                            "glow_under_load_ms = ms_per_step - this = what the acoustic model costs per utterance when its ~140 small launches "
+                            "compete with other calls' vocoder launches (alone it takes latency_ms_single_stream minus the vocoder's share)",
+                    "ms_per_step": 1e3 * dt_voc / K,
+                    "utterances_per_sec": world * K * B / dt_voc,
+                },
+                "call_coalescing": None if not (conc > 1 and B == 1) else {
+                    "what": f"option call_coalesce = {cc_other} (the library default, which the headline runs, is {cc_default}): concurrent batch-1 "
+                            "mi355tts_synthesize callers become the rows of fused padded calls — acoustic pass and vocoder — at most that many "
+                            "in flight (csrc/host_join.h); rows equal their solitary calls to f32 round-off (tests/test_emu_coalesce.py, "
+                            "tests/test_gpu_parity.py::test_coalesced_calls_equal_their_solitary_results).  NOT the headline: the same timed "
+                            "region with the option at its other setting",
+                    "call_coalesce": cc_other,
+                    "rows_per_pass": (cs1[1] - cs0[1]) / max(1, cs1[0] - cs0[0]),
+                    "utterances_per_sec": world * K * B / dt_flight_nc,
+                    "ms_per_step": 1e3 * dt_flight_nc / K,
+                    "steady_state_utterances_per_sec_rank0": None if not t_steady_nc else 10 * K * B / float(np.median(t_steady_nc)),
+                },
+                "denoiser_on": None if not dn_ok else {
+                    "denoiser_strength": 0.005,
+                    "note": "the reference CLI/server default (larynx/__main__.py:512-516); STFT denoiser on the device",
+                    "ms_per_step": 1e3 * dt_dn / K,
+                    "utterances_per_sec": world * K * B / dt_dn,
+                },
+                "half_mode": None if not half else {
+                    "dtype": "f16: the native fp16 vocoder — fp16 weights, fp16 activation planes in HBM between ALL layers (conv_pre, upsamplers, every "
+                             "ResBlock conv, conv_post), one v_mfma_f32_32x32x16_f16 per product, f32 accumulate (csrc/conv_f16.h, hifigan_f16.h); "
+                             + ("GlowTTS: the decoder's WaveNets in fp16, one launch per coupling block (csrc/wn_f16.h); encoder, durations, "
+                                "start / end convs, coupling and InvConvNear in f32" if glow_f16 else "GlowTTS in f32"),
+                    "acoustic_model": "f16 decoder WaveNets (wn_f16_kernel)" if glow_f16 else "f32",
+                    "what": "the reference's `half` switch (`.half()` on both models, larynx/glow_tts.py:90-91, larynx/hifi_gan.py:96-97) on this backend; "
+                            "NOT the headline — reported next to it",
+                    "parity": "vocoder: waveform error vs the reference's f32 output no larger than the reference's OWN generator under .half() on the same "
+                              "input (tests/golden/*.npz: ref_half_rms, made by oracle/make_golden.py); acoustic model: mel error no larger than the "
+                              "reference's OWN decoder under .half() (tests/golden/glow_half_reference.json, oracle/make_golden_glow_half.py); both: the fused "
+                              "call within the reference's two models under .half().  Asserted per golden case in tests/test_gpu_parity.py::"
+                              "test_f16_mode_against_the_reference, ::test_f16_acoustic_mode_against_the_reference, ::test_f16_fused_call_against_the_reference",
+                    "utterances_per_sec": world * K * B / dt_half_flight,
+                    "ms_per_step": 1e3 * dt_half_flight / K,
+                    "latency_ms_single_stream": 1e3 * dt_half_single / K,
+                    "x_realtime_per_gpu": audio_s / (dt_half_flight * world),
+                    "resblock_class_ms_per_step": half[2]["ms"] / K,
+                    "profile_ms_per_step": {k: c["ms"] / K for k, c in half[3].items() if c["launches"]},
+                    # ONE fp16 MFMA per product: executed matrix work = the algorithmic FLOPs
+                    "roofline": None if half[2]["ms"] <= 0 else {
+                        "kernel": "HiFi-GAN ResBlock launches in the fp16 mode: conv_f16_group_kernel (the three MRF chains' same-geometry convs per launch), "
+                                  "HIP events per launch, single stream",
+                        "bound": "mfma",
+                        "achieved": half[2]["flop"] / (half[2]["ms"] * 1e-3) / 1e12,
+                        "peak": BF16_PEAK_TFLOPS,
+                        "unit": "TFLOP/s",
+                        "frac": half[2]["flop"] / (half[2]["ms"] * 1e-3) / 1e12 / BF16_PEAK_TFLOPS,
+                        "note": "algorithmic FLOPs (one MFMA per product) / dense fp16 peak (= the bf16 figure); launches measured one call at a time",
+                        "launches": half[2]["launches"],
+                        "avg_launch_us": 1e3 * half[2]["ms"] / max(1, half[2]["launches"]),
+                        "frac_minus_event_overhead": half[2]["flop"] / (max(half[2]["ms"] - 1e-3 * ev_us * half[2]["launches"], 0.5 * half[2]["ms"]) * 1e-3) / 1e12 / BF16_PEAK_TFLOPS,
+                        "by_kernel": by_kernel_table(half[4]),
+                    },
+                },
+                "bf16x3_mode": None if not half else {
+                    "dtype": "bf16x3: ResBlock convs and upsamplers on the bf16 matrix cores with split operands (three MFMAs per product, f32 planes; "
+                             "conv_bf16.h) — the ACCURATE reduced mode: waveform RMS <= 2.9e-6 vs the reference's f32 output on the golden set",
+                    "utterances_per_sec": world * K * B / dt_x3_flight if dt_x3_flight > 0 else None,
+                    "ms_per_step": 1e3 * dt_x3_flight / K,
+                },
+                "per_rank": {
+                    "utterances_per_sec": [K * B / t[0] for t in per_rank],
+                    "min": min(K * B / t[0] for t in per_rank), "max": max(K * B / t[0] for t in per_rank),
+                    "latency_ms_single_stream": [1e3 * t[1] / K for t in per_rank],
+                    "note": "each rank's own median over the repeats; `value` = all ranks' utterances / the slowest rank's time",
+                },
+                "roofline": {
+                    "kernel": "HiFi-GAN ResBlock launches: rb_group_kernel (256- and 128-channel stages: the continuous-stream tile of rb_conv.h; conv_group_kernel = the k-split tile at the utterance lengths the promotion rule leaves alone), rb_pair_group_kernel (fused conv pairs of the 64/32-channel stages on four waves, rb_pair.h)",
+                    "bound": "mfma",
+                    "achieved": dom_tf_raw,
+                    "peak": FP32_PEAK_TFLOPS,
+                    "unit": "TFLOP/s",
+                    "frac": dom_tf_raw / FP32_PEAK_TFLOPS,
+                    "traffic": traffic,
+                    "traffic_source": f"profiles/{tpath.name if tpath.is_file() else '-'} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same "
+                                      f"command, bytes per launch, FETCH_SIZE doubled per the guide's gfx950 correction for 16-B/lane reads)",
+                    "algorithmic_bytes_per_launch": "in + out planes of the launch's three members: e.g. stage 1 of 'high' 3 x (20.4 + 20.4) MB = 123 MB; "
+                                                    "class average 92 MB per launch (1656 MB per utterance over 18 launches)",
+                    "algorithmic_flop_per_launch": dom["flop"] / max(1, dom["launches"]),
+                    "launches": dom["launches"],
+                    "avg_launch_us": 1e3 * dom_ms_raw / max(1, dom["launches"]),
+                    "event_pair_overhead_us": ev_us,
+                    "avg_launch_us_minus_event_overhead": 1e3 * dom_ms / max(1, dom["launches"]),
+                    "achieved_minus_event_overhead": dom_tf,
+                    "frac_minus_event_overhead": dom_tf / FP32_PEAK_TFLOPS,
+                    # context, not the kernel figure: all algorithmic FLOPs of the utterances / the timed regions' wall time (GlowTTS, the
+                    # upsamplers and the output tail included) — what the chip sustains with the headline's calls in flight
+                    "end_to_end_under_load": {"achieved": flop_utt * K * B / dt_flight / 1e12, "frac": flop_utt * K * B / dt_flight / 1e12 / FP32_PEAK_TFLOPS,
+                                              "steady_state_achieved": None if dt_steady <= 0 else flop_utt * K_steady * B / dt_steady / 1e12,
+                                              "steady_state_frac": None if dt_steady <= 0 else flop_utt * K_steady * B / dt_steady / 1e12 / FP32_PEAK_TFLOPS,
+                                              "unit": "TFLOP/s per GPU"},
+                    "share_of_step_time": dom["ms"] / (1e3 * dt_prof),
+                    "all_conv_mfma_ms_per_step": all_conv_ms / K,
+                    "schedule": ("serial_branches=1: one conv (or fused conv pair) per launch, the three MRF chains one after another "
+                                 "on one stream" if args.serial_branches else
+                                 "product schedule: one stream per call; the same-geometry convs (or fused conv pairs) of the three MRF "
+                                 "chains of a step are ONE grouped launch (conv_group_kernel / rb_group_kernel / rb_pair_group_kernel), each launch timed alone"),
+                    "timing": "HIP events on the launch stream around every launch, profiled pass of the same K steps; `avg_launch_us` / `achieved` / "
+                              "`frac` = the RAW event times (they agree with rocprofv3's kernel durations of the same command: "
+                              "profiles/r05_events_vs_rocprof.txt); `*_minus_event_overhead` = the same minus the cost of an EMPTY event pair "
+                              "measured in this run (`event_pair_overhead_us`) — an over-correction, kept for comparison with round 4's line",
+                },
+                "profile_ms_per_step": {k_: v_["ms"] / K for k_, v_ in prof.items()},
+            })
+            out["roofline"]["by_kernel"] = by_kernel_table(prof_kernels)
+            if args.precision != "f32":
+                # the reduced modes as the line's own subject: price the class against the 16-bit matrix peak — per USEFUL product (fp16: one
+                # MFMA per product; bf16x3 executes three), and no committed PMC traffic for these kernels
+                rf = out["roofline"]
+                rf["kernel"] = ("HiFi-GAN ResBlock launches in the fp16 mode: pair_f16_group_kernel (fused conv1 + conv2 of a step, 128 / 64 / 32 channels), "
+                                "conv_f16_group_kernel (256 channels)" if args.precision == "f16" else
+                                "HiFi-GAN ResBlock launches in the split-bf16 mode: conv_bf16_group_kernel / pair_bf16_group_kernel (three bf16 MFMAs per product)")
+                rf["peak"] = BF16_PEAK_TFLOPS
+                rf["frac"] = dom_tf_raw / BF16_PEAK_TFLOPS
+                rf["frac_minus_event_overhead"] = dom_tf / BF16_PEAK_TFLOPS
+                rf["frac_note"] = "achieved = algorithmic f32-path FLOPs / time, priced against the dense 16-bit MFMA peak (2.5 PFLOP/s): per useful product"
+                e2e = rf["end_to_end_under_load"]
+                e2e["frac"] = e2e["achieved"] / BF16_PEAK_TFLOPS
+                e2e["steady_state_frac"] = None if e2e["steady_state_achieved"] is None else e2e["steady_state_achieved"] / BF16_PEAK_TFLOPS
+                rf["traffic"] = None
+                rf["traffic_source"] = "no committed PMC passes for this mode's kernels"
+                rf["algorithmic_bytes_per_launch"] = "half the f32 figure in the fp16 mode (fp16 planes), conv1's plane never leaves LDS in the fused launches"
         if c3 is not None:
             out["config3"] = c3
         if c4 is not None:
@@ -1233,7 +1296,7 @@ def main():
             out["micro_batched"] = mb
         if c5 is not None:
             out["config5"] = c5
-        if not args.no_cpu_baseline and world == 1 and on_gpu and not args.tiny:
+        if args.full and not args.no_cpu_baseline and world == 1 and on_gpu and not args.tiny:
             out["cpu_baseline"] = cpu_baseline(ids_host[0], args.length_scale)  # = golden case ljspeech_high_S120
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -1,4 +1,5 @@
 import json
+import os
 from pathlib import Path
 
 import numpy as np
@@ -7,6 +8,15 @@ from larynx_amd import hparams as HP
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 CASES = sorted(p.stem for p in GOLDEN.glob("*.npz"))
+
+
+def reference_has(path) -> bool:
+    """True when `path` (a file of the reference checkout) exists and this user can read it: a tree that exists but is not
+    readable counts as absent (Path.is_file raises PermissionError there instead of returning False)."""
+    try:
+        return Path(path).is_file() and os.access(path, os.R_OK)
+    except OSError:
+        return False
 
 
 def load_case(name):

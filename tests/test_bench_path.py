@@ -7,15 +7,20 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
+
+from larynx_amd import hparams as HP
 
 REPO = Path(__file__).resolve().parent.parent
 
 
-def _run(emu_library, gpus, utterances=7, extra=()):
+def _run(emu_library, gpus, utterances=7, extra=(), full=True):
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--ids", "12",
-           "--concurrency", "2", "--repeats", "2", "--config3-utterances", str(utterances), "--device", "cpu", "--library", str(emu_library),
-           "--tiny", "--no-cpu-baseline", *extra]
+           "--concurrency", "2", "--device", "cpu", "--library", str(emu_library), "--tiny"]
+    if full:  # the secondary legs (roofline, config 3, ...) only run with --full
+        cmd += ["--full", "--repeats", "2", "--config3-utterances", str(utterances), "--no-cpu-baseline"]
+    cmd += list(extra)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=str(REPO))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -58,3 +63,24 @@ def test_bench_line_at_world_size(emu_library_path, gpus, utterances):
     assert len(out["per_rank"]["utterances_per_sec"]) == gpus
     assert c3["utterances_per_sec"] > 0 and c3["audio_seconds"] > 0
     assert out["denoiser_on"] is None  # the emulator's tiny vocoder (hop 8) is below the denoiser's STFT size
+
+
+def test_plain_bench_line_times_the_headline_only_and_dumps_its_outputs(emu_library_path, tmp_path):
+    """A plain run: one timed region of exactly --steps steps, the headline fields, none of the --full legs; --dump-outputs
+    writes what the last timed step returned, identical from run to run (seeded inputs)."""
+    outs = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = _run(emu_library_path, 1, full=False, extra=("--dump-outputs", str(d)))
+        assert out["metric"] == "utterances_per_sec" and out["unit"] == "utterances/s" and out["higher_is_better"] is True
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["timing"]["repeats"] == 1 and out["dtype"] == "f32"
+        assert out["value"] > 0 and abs(out["value"] - 3 / (out["ms_per_step"] * 3 / 1e3)) < 1e-6 * out["value"]
+        assert not {"roofline", "config3", "half_mode", "steady_state", "denoiser_on", "cpu_baseline"} & set(out)
+        arrays = {n: np.load(d / f"{n}.npy") for n in ("waveform", "waveform_int16", "frames")}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        fr = int(arrays["frames"][0])
+        assert fr > 0 and arrays["waveform"].shape == arrays["waveform_int16"].shape == (1, fr * HP.TINY_HIFIGAN.hop)
+        assert np.abs(arrays["waveform"]).max() > 0
+        outs.append(arrays)
+    for n in outs[0]:
+        assert np.array_equal(outs[0][n], outs[1][n]), n

@@ -47,7 +47,7 @@ def test_bench_runs_on_two_gpus():
     n = _gpus()
     if n < 2:
         pytest.skip(f"{n} GPU visible: `bench.py --gpus 2` needs two (the driver's scaling run launches it on its 8-GPU node)")
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-half-mode",
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-half-mode",
            "--no-config4", "--no-config5", "--config3-utterances", "16"]
     p = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]

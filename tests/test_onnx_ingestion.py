@@ -109,7 +109,10 @@ def test_exporter_variants_from_the_reference_modules(emu_library_path, tmp_path
     `tests/onnx_variants_check.py` in a process of its own (it imports the reference tree; skipped where /root/reference
     does not exist, e.g. on the GPU box).  All 20 combinations of opset {11, 12, 13, 14, 17} x folding x
     keep_initializers_as_inputs were checked once with this code; three of them run in the suite."""
-    if not Path("/root/reference/glow_tts/models.py").is_file():
+    from oracle.make_golden import REF  # where onnx_variants_check.py imports the reference from
+    from tests.golden_util import reference_has
+
+    if not reference_has(REF / "glow_tts" / "models.py"):
         pytest.skip("needs the reference checkout")
     import subprocess
     import sys

@@ -27,9 +27,10 @@ from larynx_amd import hparams as HP
 from larynx_amd import synthetic
 from larynx_amd.audio import ljspeech_audio_settings
 from oracle import audio_np, glow_tts_np, hifi_gan_np
+from tests.golden_util import reference_has
 
 REF = Path(os.environ.get("LARYNX_REFERENCE", "/root/reference"))
-pytestmark = pytest.mark.skipif(not (REF / "larynx" / "__init__.py").is_file(), reason="needs the reference checkout")
+pytestmark = pytest.mark.skipif(not reference_has(REF / "larynx" / "__init__.py"), reason="needs the reference checkout")
 
 # shrunk hyper-parameters with the 80 mel channels the reference's Generator hard-codes (hifi_gan/models.py:153)
 GLOW = HP.GlowHParams(num_symbols=46, hidden_channels=32, filter_channels=64, filter_channels_dp=40, n_blocks_dec=2,

@@ -4,7 +4,7 @@ out=gpurun_out/$1; var=$2; va=$3; vb=$4; shift 4
 mkdir -p $out
 for i in 1 2; do
   for v in $va $vb; do
-    env $var=$v timeout 600 python bench.py --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode "$@" \
+    env $var=$v timeout 600 python bench.py --full --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode "$@" \
       > $out/${var}_${v}_$i.json 2> $out/${var}_${v}_$i.err
     python - $out/${var}_${v}_$i.json "$var=$v" <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ mkdir -p $O
 for rep in 1 2; do
 for lib in "$@"; do
   n=$(basename $lib .so)
-  python bench.py --precision f16 --library $lib --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch ${F16_AB_EXTRA:-} > $O/${n}_$rep.json 2> $O/${n}_$rep.err
+  python bench.py --full --precision f16 --library $lib --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch ${F16_AB_EXTRA:-} > $O/${n}_$rep.json 2> $O/${n}_$rep.err
   python - $O/${n}_$rep.json $n <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

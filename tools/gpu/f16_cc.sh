@@ -4,7 +4,7 @@ O=gpurun_out/${1:-r06_f16_cc}
 mkdir -p $O
 for rep in 1 2; do
 for cc in 0 2 3 4; do
-  python bench.py --precision f16 --set-option call_coalesce=$cc --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch > $O/cc${cc}_$rep.json 2> $O/cc${cc}_$rep.err
+  python bench.py --full --precision f16 --set-option call_coalesce=$cc --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch > $O/cc${cc}_$rep.json 2> $O/cc${cc}_$rep.err
   python - $O/cc${cc}_$rep.json $cc <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ O=gpurun_out/$T
 mkdir -p $O
 for rep in 1 2; do
 for val in 1 0; do
-  python bench.py --precision f16 --set-option $OPT=$val --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch "$@" > $O/${OPT}${val}_$rep.json 2> $O/${OPT}${val}_$rep.err
+  python bench.py --full --precision f16 --set-option $OPT=$val --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch "$@" > $O/${OPT}${val}_$rep.json 2> $O/${OPT}${val}_$rep.err
   python - $O/${OPT}${val}_$rep.json $OPT=$val <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ mkdir -p $out
 for i in 1 2; do
   for v in "" "--acoustic-f16"; do
     n=$([ -z "$v" ] && echo f32 || echo mixed)
-    timeout 600 python bench.py --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode $v > $out/${n}_$i.json 2> $out/${n}_$i.err
+    timeout 600 python bench.py --full --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode $v > $out/${n}_$i.json 2> $out/${n}_$i.err
     python - $out/${n}_$i.json $n <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ mkdir -p $out
 for v in 0 1; do MI355TTS_RB_NB4_MIN_TILES=$v python tools/wave_hash.py high 617 2>&1 | tail -1 | cut -c1-400; done | tee $out/bits.txt
 for i in 1 2; do
   for v in 0 1; do
-    MI355TTS_RB_NB4_MIN_TILES=$v timeout 600 python bench.py --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode \
+    MI355TTS_RB_NB4_MIN_TILES=$v timeout 600 python bench.py --full --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode \
       > $out/nb4_${v}_$i.json 2> $out/nb4_${v}_$i.err
     python - $out/nb4_${v}_$i.json $v <<'PY'
 import json, sys

@@ -4,7 +4,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for v in ${@:-0 3}; do
   O=gpurun_out/r06_qmap/d$v; rm -rf $O; mkdir -p $O
-  BENCH_DUMMY_STREAMS=$v timeout 300 rocprofv3 --kernel-trace -d $O -o t --output-format csv -- python bench.py --gpus 1 --steps 20 --warmup 5 --repeats 3 --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode --no-steady-state > $O/bench.log 2>&1
+  BENCH_DUMMY_STREAMS=$v timeout 300 rocprofv3 --kernel-trace -d $O -o t --output-format csv -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --repeats 3 --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode --no-steady-state > $O/bench.log 2>&1
   python - $O/t_kernel_trace.csv $v <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -16,7 +16,7 @@ bash tools/gpu/rb_diag.sh r04_diag1 \
 # the real pipeline under load: per-kernel begin / end of 8 calls in flight (do ResBlock launches of different streams overlap?)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_diag1
-timeout 300 rocprofv3 --kernel-trace -d $O/trace8 -o t --output-format csv -- python bench.py --steps 16 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --repeats 1 > $O/trace8.log 2>&1
+timeout 300 rocprofv3 --kernel-trace -d $O/trace8 -o t --output-format csv -- python bench.py --full --steps 16 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --repeats 1 > $O/trace8.log 2>&1
 python - <<'PY'
 import csv, glob, re
 f = glob.glob("gpurun_out/r04_diag1/trace8/**/*kernel_trace.csv", recursive=True)[0]
@@ -101,7 +101,7 @@ ab_rb_pipeline() {
 # r04 session 6: the continuous-stream tile in the pipeline (A B A B inside one session) + the parity suite
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab1; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 for i in 1 2; do
   timeout 300 $B --set-option rb_conv=0 > $O/old_$i.json 2> $O/old_$i.err
   timeout 300 $B > $O/new_$i.json 2> $O/new_$i.err
@@ -124,7 +124,7 @@ ab_rb_kernel_stats() {
 # r04 session 7: per-kernel durations of the two tiles in the pipeline (single stream, rocprofv3), then the parity suite
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab2; mkdir -p $O
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1"
 for v in old new old new; do
   opt=""; [ $v = old ] && opt="--set-option rb_conv=0"
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/t_$v -o t --output-format csv -- $B $opt > $O/t_$v.log 2>&1
@@ -139,7 +139,7 @@ per_position() {
 # r04 session 8: per-position durations of the 18 grouped ResBlock launches of an utterance (single stream)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_pos; mkdir -p $O
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1"
 timeout 300 rocprofv3 --kernel-trace -d $O/t -o t --output-format csv -- $B > $O/t.log 2>&1
 python - <<'PY'
 import csv, glob, re, collections
@@ -184,7 +184,7 @@ ab_stage0_m128() {
 # r04 session 10: bench line of the current build (new fields), 128-row tile for stage 0 too, calls in flight x GlowTTS coalescing
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab3; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 show() { python - "$@" <<'PY'
 import json, sys
 for f in sys.argv[1:]:
@@ -210,7 +210,7 @@ ab_glow_priority_stream() {
 # r04 session 11: GlowTTS on a high-priority stream (option glow_priority), hardware queue counts
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab4; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 show() { python - "$@" <<'PY'
 import json, sys
 for f in sys.argv[1:]:
@@ -261,7 +261,7 @@ ab_glow_lds_footprint() {
 # attention at 66 KB vs 144 KB
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab5; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 show() { python - "$@" <<'PY'
 import json, sys
 for f in sys.argv[1:]:
@@ -289,7 +289,7 @@ ab_glow_wave_priority() {
 # r04 session 16: s_setprio 3 at the entry of the GlowTTS kernels vs none
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab6; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 show() { python - "$@" <<'PY'
 import json, sys
 for f in sys.argv[1:]:
@@ -316,7 +316,7 @@ ab_host_wait() {
 # r04 session 17: how the caller threads wait for their streams (spin / blocking event / query + sleep)
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab7; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 show() { python - "$@" <<'PY'
 import json, sys
 for f in sys.argv[1:]:
@@ -343,7 +343,7 @@ ab_calls_in_flight() {
 # r04 session 18: more calls in flight with coalesced GlowTTS passes
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab8; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 run() { n=$1; shift; timeout 400 "$@" > $O/$n.json 2> $O/$n.err; }
 for c in 8 16 24 32; do run c$c $B --concurrency $c; done
 MI355TTS_SYNC_MODE=2 run c32_poll $B --concurrency 32
@@ -363,7 +363,7 @@ ab_rb_upsamplers() {
 # r04 session 19: the upsamplers on the continuous-stream tile: per-kernel durations (single stream) and the bench line, A B A B
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab9; mkdir -p $O
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1"
 for v in old new; do
   opt=""; [ $v = old ] && opt="--set-option rb_conv=0"
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/t_$v -o t --output-format csv -- $B $opt > $O/t_$v.log 2>&1
@@ -371,7 +371,7 @@ for v in old new; do
   echo "== $v"; grep -E "conv_mfma_kernel<2,|rb_conv_kernel|conv_mfma_kernel<7, 32" $f | cut -c1-150
   rm -rf $O/t_$v
 done
-B2="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B2="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 for i in 1 2; do
   timeout 300 $B2 --set-option rb_conv=0 > $O/old_$i.json 2> $O/old_$i.err
   timeout 300 $B2 > $O/new_$i.json 2> $O/new_$i.err
@@ -390,7 +390,7 @@ ab_voc_only_sleep() {
 # latency but no GPU): how much of glow_under_load_ms is latency (callers not feeding the GPU), how much is GPU work?
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab10; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 for c in 8 16; do for ms in 0 4 8 12; do timeout 300 $B --concurrency $c --voc-only-sleep-ms $ms > $O/c${c}_s$ms.json 2> $O/c${c}_s$ms.err; done; done
 python - <<'PY'
 import json, glob
@@ -404,7 +404,7 @@ ab_steps() {
 # value against the number of steps K of a timed region (each region starts on an idle GPU and drains at its end)
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab11; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 for k in 20 50 100 200 400; do timeout 600 $B --steps $k > $O/k$k.json 2> $O/k$k.err; done
 timeout 600 $B --steps 200 --concurrency 12 > $O/k200_c12.json 2> $O/k200_c12.err
 timeout 600 $B --steps 200 --concurrency 16 > $O/k200_c16.json 2> $O/k200_c16.err
@@ -421,7 +421,7 @@ ab_stage0_m128_steady() {
 # the 128-row continuous-stream tile for the 256-channel stage too (MI355TTS_M128_MIN_TILES=64), read in the steady-state leg
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab12; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 for i in 1 2; do
   timeout 600 $B > $O/base_$i.json 2> $O/base_$i.err
   MI355TTS_M128_MIN_TILES=64 timeout 600 $B > $O/m128_$i.json 2> $O/m128_$i.err
@@ -438,7 +438,7 @@ ab_rb_pair() {
 # the 4-wave fused pair kernel without a k-split (rb_pair.h, option rb_pair) vs the 8-wave one: kernel stats, bench, parity
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab13; mkdir -p $O
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
 for v in old new; do
   opt=""; [ $v = old ] && opt="--set-option rb_pair=0"
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/t_$v -o t --output-format csv -- $B $opt > $O/t_$v.log 2>&1
@@ -446,7 +446,7 @@ for v in old new; do
   echo "== $v"; grep -E "pair" $f | cut -c1-150
   rm -rf $O/t_$v
 done
-B2="python bench.py --no-cpu-baseline --no-config3 --no-config5 --no-half-mode"
+B2="python bench.py --full --no-cpu-baseline --no-config3 --no-config5 --no-half-mode"
 for i in 1 2; do
   timeout 300 $B2 --set-option rb_pair=0 > $O/old_$i.json 2> $O/old_$i.err
   timeout 300 $B2 > $O/new_$i.json 2> $O/new_$i.err
@@ -466,14 +466,14 @@ ab_rb_pair_variants() {
 # three waves per SIMD (-DRBP_LB32=3); libraries built with those switches next to the default one
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab14; mkdir -p $O
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
 for v in "" _p64 _lb3 _p64_p32lb3; do
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/t$v -o t --output-format csv -- $B --library larynx_amd/libmi355tts$v.so > $O/t$v.log 2>&1
   f=$(find $O/t$v -name "*kernel_stats.csv" | head -1)
   echo "== lib$v"; grep -E "pair" $f | cut -c1-140
   rm -rf $O/t$v
 done
-B2="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B2="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 for i in 1 2; do for v in "" _p64 _lb3 _p64_p32lb3; do timeout 300 $B2 --library larynx_amd/libmi355tts$v.so > $O/lib${v}_$i.json 2> $O/lib${v}_$i.err; done; done
 python - <<'PY'
 import json, glob
@@ -499,14 +499,14 @@ ab_wide_stores() {
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab15; mkdir -p $O
 for q in high medium; do PYTHONPATH=. python tools/ab_bits.py larynx_amd/libmi355tts_nowide.so larynx_amd/libmi355tts.so $q; done
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
 for v in _nowide _rbwide ""; do
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/t$v -o t --output-format csv -- $B --library larynx_amd/libmi355tts$v.so > $O/t$v.log 2>&1
   f=$(find $O/t$v -name "*kernel_stats.csv" | head -1)
   echo "== lib$v"; grep -E "rb_|conv_group|conv_kernel" $f | cut -c1-150
   rm -rf $O/t$v
 done
-B2="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
+B2="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode"
 for i in 1 2; do for v in _nowide _rbwide ""; do timeout 300 $B2 --library larynx_amd/libmi355tts$v.so > $O/lib${v}_$i.json 2> $O/lib${v}_$i.err; done; done
 python - <<'PY'
 import json, glob
@@ -541,7 +541,7 @@ ab_snake() {
 # against the 64 x 32 k-split tile (MI355TTS_NO_GROUP_PROMOTE=1): kernel stats, bench, parity
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab16; mkdir -p $O
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
 for v in old new; do
   e=0; [ $v = old ] && e=1
   MI355TTS_NO_GROUP_PROMOTE=$e timeout 300 rocprofv3 --kernel-trace --stats -d $O/t_$v -o t --output-format csv -- $B > $O/t_$v.log 2>&1
@@ -549,7 +549,7 @@ for v in old new; do
   echo "== $v"; grep -E "rb_|conv_group|pair" $f | cut -c1-150
   rm -rf $O/t_$v
 done
-B2="python bench.py --no-cpu-baseline --no-config3 --no-config5 --no-half-mode"
+B2="python bench.py --full --no-cpu-baseline --no-config3 --no-config5 --no-half-mode"
 for i in 1 2; do
   MI355TTS_NO_GROUP_PROMOTE=1 timeout 300 $B2 > $O/old_$i.json 2> $O/old_$i.err
   timeout 300 $B2 > $O/new_$i.json 2> $O/new_$i.err
@@ -580,7 +580,7 @@ ab_bf16_snake() {
 # (profiles/r04_ab17.txt): the BF_E tile and its promotion were taken out again — this function records how it was measured
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_ab17; mkdir -p $O
-B="python bench.py --precision bf16x3 --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
+B="python bench.py --full --precision bf16x3 --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
 for v in old new; do
   e=0; [ $v = old ] && e=1
   MI355TTS_NO_GROUP_PROMOTE=$e timeout 300 rocprofv3 --kernel-trace --stats -d $O/t_$v -o t --output-format csv -- $B > $O/t_$v.log 2>&1
@@ -588,7 +588,7 @@ for v in old new; do
   echo "== $v"; grep -E "bf16" $f | cut -c1-150
   rm -rf $O/t_$v
 done
-B2="python bench.py --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-steady-state"
+B2="python bench.py --full --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-steady-state"
 for i in 1 2; do
   MI355TTS_NO_GROUP_PROMOTE=1 timeout 300 $B2 > $O/old_$i.json 2> $O/old_$i.err
   timeout 300 $B2 > $O/new_$i.json 2> $O/new_$i.err
@@ -613,7 +613,7 @@ for f in 360 440 520 560 600 680 700 760 840 1040 1100; do
   done
 done
 O=gpurun_out/r04_ab18; mkdir -p $O
-B2="python bench.py --no-cpu-baseline --no-config4 --no-config5 --no-half-mode --no-steady-state"
+B2="python bench.py --full --no-cpu-baseline --no-config4 --no-config5 --no-half-mode --no-steady-state"
 for i in 1 2; do
   MI355TTS_NO_GROUP_PROMOTE=1 timeout 400 $B2 > $O/old_$i.json 2> $O/old_$i.err
   timeout 400 $B2 > $O/new_$i.json 2> $O/new_$i.err
@@ -631,7 +631,7 @@ pmc_by_stage() {
 # workgroups) and the 128-channel stage (> 1024), promotion on and off (off: conv_group_kernel runs the 256-channel stage)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04_pmc_stage; mkdir -p $O
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --concurrency 1 --repeats 1 --no-steady-state"
 for v in new old; do
   e=0; [ $v = old ] && e=1
   MI355TTS_NO_GROUP_PROMOTE=$e timeout 240 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_LDS -d $O/sq_$v -o sq --output-format csv -- $B > $O/sq_$v.log 2>&1

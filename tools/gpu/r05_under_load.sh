@@ -6,7 +6,7 @@ export PYTHONPATH=$GRAFT_REPO_ROOT
 O=gpurun_out/r05_under_load
 mkdir -p $O
 for wn in 0 1; do
-  timeout 300 rocprofv3 --kernel-trace -d $O/trace$wn -o t --output-format csv -- python bench.py --steps 16 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --no-steady-state --repeats 1 --set-option wn_layer=$wn > $O/trace$wn.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace -d $O/trace$wn -o t --output-format csv -- python bench.py --full --steps 16 --warmup 3 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --no-steady-state --repeats 1 --set-option wn_layer=$wn > $O/trace$wn.log 2>&1
   python - $wn <<'PY'
 import csv, glob, re, sys
 wn = sys.argv[1]

@@ -8,15 +8,15 @@ O=gpurun_out/r06_final
 mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q > $O/gputest.log 2>&1; echo "rc $?" >> $O/gputest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "rc $?" >> $O/smoke.log
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver.err
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 \
   > $O/bench_torchrun_n1.json 2> $O/bench_torchrun.err
-timeout 600 python bench.py --precision f16 --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch > $O/bench_f16.json 2> $O/bench_f16.err
+timeout 600 python bench.py --full --precision f16 --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch > $O/bench_f16.json 2> $O/bench_f16.err
 tools/profile_round.sh r06 > $O/profile_round.log 2>&1
 F=gpurun_out/r06_f16
 rm -rf $F; mkdir -p $F
-F16="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --no-micro-batch --no-steady-state --concurrency 1 --repeats 1 --precision f16"
+F16="python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-config3 --no-config4 --no-config5 --no-half-mode --no-micro-batch --no-steady-state --concurrency 1 --repeats 1 --precision f16"
 timeout 240 rocprofv3 --kernel-trace --stats -d $F/trace -o trace --output-format csv -- $F16 > $F/bench_trace.log 2>&1
 timeout 240 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_LDS -d $F/pmc_sq -o sq --output-format csv -- $F16 > $F/bench_sq.log 2>&1
 timeout 240 rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM_RD SQ_INST_LEVEL_LDS SQ_LDS_IDX_ACTIVE SQ_INSTS_MFMA -d $F/pmc_sq2 -o sq2 --output-format csv -- $F16 > $F/bench_sq2.log 2>&1

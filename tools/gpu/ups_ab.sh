@@ -6,7 +6,7 @@ mkdir -p $out
 for kv in "MI355TTS_NO_UPS_PLANES=1" "MI355TTS_NO_UPS_PLANES=0" "MI355TTS_UPS_NB=1" "MI355TTS_UPS_NB=4"; do echo -n "$kv "; env $kv python tools/wave_hash.py high 617 2>&1 | tail -1 | cut -c1-60; done | tee $out/bits.txt
 for i in 1 2; do
   for kv in "MI355TTS_NO_UPS_PLANES=1" "MI355TTS_NO_UPS_PLANES=0" "MI355TTS_UPS_NB=1" "MI355TTS_UPS_NB=4"; do
-    env $kv timeout 600 python bench.py --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode \
+    env $kv timeout 600 python bench.py --full --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-half-mode \
       > $out/${kv}_$i.json 2> $out/${kv}_$i.err
     python - $out/${kv}_$i.json "$kv" <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_dropin.py -m g
 echo "tests rc $?" >> $out/tests.log
 for i in 1 2; do
   for a in f32 f16; do
-    timeout 600 python bench.py --precision f16 --half-acoustic $a --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch \
+    timeout 600 python bench.py --full --precision f16 --half-acoustic $a --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch \
       > $out/acoustic_${a}_$i.json 2> $out/acoustic_${a}_$i.err
   done
 done

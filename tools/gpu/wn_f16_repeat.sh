@@ -5,7 +5,7 @@
 out=gpurun_out/${1:-r06_wn_repeat}
 mkdir -p $out
 for r in 1 2 3 1 2; do
-  MI355TTS_WN_REPEAT=$r timeout 600 python bench.py --precision f16 --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-steady-state \
+  MI355TTS_WN_REPEAT=$r timeout 600 python bench.py --full --precision f16 --no-config3 --no-config4 --no-config5 --no-cpu-baseline --no-micro-batch --no-steady-state \
     > $out/repeat_$r.json 2> $out/repeat_$r.err
   python - $out/repeat_$r.json $r <<'PY'
 import json, sys
