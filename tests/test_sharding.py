@@ -225,3 +225,92 @@ def test_eight_rank_gloo_matches_single_process(emu_library, emu_engine, tmp_pat
     assert all(2 <= len(s) <= 3 for s in shards)
     for i in range(len(rows)):
         assert np.array_equal(merged[i], solo[i]), i
+
+
+def test_edge_frames_hand_computed_cases():
+    """`workload_check.edge_frames` / `cover_edges` on cases worked out by hand, and the tile table of 'high' / 'medium'."""
+    from larynx_amd import hparams as HP
+    from tests import workload_check as W
+
+    hp = HP.HifiGanHParams(upsample_rates=(3,), upsample_kernel_sizes=(6,))
+    # one stage of 3 F columns on 32-column tiles with a 5-column halo: 3 F mod 32 = 0 (F = 32), 1 (F = 11), 2 ... 4 (F = 22, 1
+    # and 33, 12)
+    e = W.edge_frames(hp, [("t", 0, 32, 5)], 1, 40)
+    assert {F: [k for (_, _, _, k) in hits] for F, hits in e.items()} == {1: ["halo"], 11: ["one"], 12: ["halo"], 22: ["halo"], 32: ["full"],
+                                                                         33: ["halo"]}
+    assert W.cover_edges(e) == [1, 11, 32]  # one F per kind, the shortest
+    # 'high', the 64-channel stage (F * 128 columns) on the k = 11 pair tile (118 columns, halo 25): 10 F mod 118 is 0 at F = 59,
+    # never 1 (even), below 25 at F = 1, 2 (10, 20), 12 ... 14 (2, 12, 22), 24 ... 26 (4, 14, 24), 36, 37 (6, 16), 48, 49 (8, 18), 60
+    hi = HP.HIFIGAN_HIGH
+    e = W.edge_frames(hi, [("pair", 2, 118, 25)], 1, 60)
+    assert sorted(e) == [1, 2, 12, 13, 14, 24, 25, 26, 36, 37, 48, 49, 59, 60] and e[59][0][3] == "full" and e[12][0][3] == "halo"
+    tiles = W.vocoder_tiles(hi, "f32")
+    assert ("pair T2 K=11", 2, 118, 25) in tiles and ("pair T2 K=3", 3, 254, 5) in tiles and ("POST_TW", 3, 256, 3) in tiles
+    assert {w for (_, s, w, _) in tiles if s in (0, 1)} == {32, 64, 128, 256}
+    tiles16 = W.vocoder_tiles(hi, "f16")
+    assert ("f16 h_tile_dims", 0, 128, 25) in tiles16 and ("pair_f16 TO K=7", 1, 122, 15) in tiles16 and ("pair_f16 TO K=3", 3, 254, 5) in tiles16
+    med = W.vocoder_tiles(HP.HIFIGAN_MEDIUM, "f32")
+    assert {(s, w) for (l, s, w, _) in med if l.startswith("mrf")} == {(2, 256), (3, 256)}
+    sigs = {F: ("a" if F <= 4 or F >= 8 else "b") for F in range(1, 11)}
+    assert W.choose_lengths(sigs, (2,)) == [1, 2, 4, 5, 7, 8] and W.choose_lengths(sigs, (2,), cap=3) == [1, 2, 4, 5]  # (the edges come on top of the cap)
+
+
+def test_config3_work_list_twin(emu_engine):
+    """tests/test_gpu_config3.py's config 3 checks on the tiny models: the bench's --tiny list (24 utterances), frames against the
+    oracle, the bench form under load and alone bit for bit, batch 8 against batch 1, mels and waveforms against the oracle."""
+    from bench import config3_ids
+    from larynx_amd import hparams as HP
+    from larynx_amd import sharding, synthetic
+    from larynx_amd.audio import ljspeech_audio_settings
+    from tests import workload_check as W
+
+    ghp, vhp = HP.TINY_GLOW, HP.TINY_HIFIGAN
+    gsd, vsd = synthetic.make_glow_state_dict(ghp, seed=11), synthetic.make_hifigan_state_dict(vhp, seed=11)
+    g, v = emu_engine.load_glow(ghp, gsd), emu_engine.load_hifigan(vhp, vsd)
+    s = ljspeech_audio_settings()
+    rows = config3_ids(ghp.num_symbols, n=24, mean=12, std=3, lo=5, hi=20)
+    ls, seed = 0.65, 1234
+    try:
+        ref = [W.oracle_frames(gsd, ghp, r, ls) for r in rows]
+        lone = W.check_load_independence(emu_engine, g, v, rows, ls, seed, s, threads=4, label="tiny")
+        frames = [lone[i][0] for i in range(len(rows))]
+        exempt = W.check_frames(frames, ref, ghp.n_sqz, "tiny")
+        W.check_micro_batches(emu_engine, g, v, rows, ls, seed, s, batch=8)
+        ok = [i for i in range(len(rows)) if i not in exempt]
+        longest = max(ok, key=lambda i: frames[i])
+        ref_mels = W.check_mels(emu_engine, g, gsd, ghp, rows, ls, seed, sorted(set(ok[::4]) | {min(ok, key=lambda i: frames[i]), longest}),
+                                exempt, label="tiny")
+        first = sharding.micro_batches(list(range(len(rows))), [len(r) for r in rows], 8)[0]
+        pick = sorted(i for i in set(first) | {longest} if i not in exempt)
+        W.check_waves_end_to_end(emu_engine, g, v, gsd, vsd, ghp, vhp, rows, ls, seed, s, pick, lone, ref_mels, label="tiny")
+    finally:
+        emu_engine.unload(g)
+        emu_engine.unload(v)
+
+
+def test_vocoder_tile_edge_sweep_twin(emu_engine, monkeypatch):
+    """tests/test_gpu_config3.py's vocoder sweep on a 256-channel test vocoder (stages of 128 and 64 channels, one dilation step
+    per chain) over F = 1 ... 100, the launch thresholds lowered to emulator sizes: the 128-row tile of the 128-channel stage from 2
+    tiles of 128 columns (F >= 65), the four-wave pair from 4 tiles (F >= 89), the promotion and snake order on "8 CUs"."""
+    from larynx_amd import hparams as HP
+    from larynx_amd import synthetic
+    from tests import workload_check as W
+
+    monkeypatch.setenv("MI355TTS_M128_MIN_TILES", "2")
+    monkeypatch.setenv("MI355TTS_RB_PAIR_MIN_TILES", "4")
+    monkeypatch.setenv("MI355TTS_GROUP_NCU", "8")
+    hp = HP.HifiGanHParams(upsample_rates=(2, 2), upsample_kernel_sizes=(4, 4), upsample_initial_channel=256,
+                           resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((5,), (3,), (5,)), num_mels=16)
+    vsd = synthetic.make_hifigan_state_dict(hp, seed=97)
+    v = emu_engine.load_hifigan(hp, vsd)
+    oracle = W.OracleWaves()
+    try:
+        sigs = W.scan_signatures(emu_engine, v, hp.num_mels, 1, 100, label="twin")
+        edges = W.cover_edges(W.edge_frames(hp, W.vocoder_tiles(hp, "f32"), 1, 100))
+        Fs = W.choose_lengths(sigs, edges, cap=12)
+        print("twin lengths", Fs, "edge cover", edges)
+        ran = W.check_lengths(emu_engine, v, vsd, hp, Fs, oracle, "twin", label="twin")
+        for k in ("rb_group_kernel.snake", "rb_group_kernel", "conv_group_kernel", "rb_pair_group_kernel", "pair_group_kernel"):
+            assert k in ran, (k, sorted(ran))
+    finally:
+        emu_engine.unload(v)

@@ -1,0 +1,402 @@
+"""Whole-workload checks against the CPU oracle, shared by the device tests (tests/test_gpu_config3.py) and their emulator
+twin (tests/test_sharding.py): frame counts of a work list, the bench form of BASELINE config 3 under load and alone, the
+micro-batched shard, mels and waveforms at the lengths where the vocoder's tile choices and tile seams move.
+
+Which kernels a vocoder call gets depends on the frame count, the batch and the load (csrc/host_launch.h: plan_conv,
+promote_group_plans, plan_pair, run_group), so the lengths compared here are chosen from the launch-rule transitions the
+library itself shows (`kernel_signature`) and from where a stage's last tile is full, one column or narrower than the halo
+(`edge_frames`)."""
+import threading
+import time
+
+import numpy as np
+
+from oracle import audio_np, glow_tts_np, hifi_gan_np
+
+F32 = np.float32
+
+# ---- frame counts ------------------------------------------------------------------------------------------------
+# The device computes w = exp(logw) * length_scale in f32 from its own logw: an utterance with a duration this close (relative)
+# to an integer may legitimately ceil the other way.  2e-5 is ~20x the logw round-off expected of an f32 encoder.
+CEIL_MARGIN = 2e-5
+MAX_EXEMPT = 16
+
+
+def oracle_frames(gsd, hp, ids, length_scale):
+    """(F, margin): the oracle's frame count and the relative distance of the closest duration to a ceil boundary,
+    min |w - round(w)| / max(w, 1) over the phonemes (w = exp(logw) * length_scale in f32)."""
+    _, logw = glow_tts_np.text_encoder(gsd, np.asarray(ids, np.int64), hp)
+    _, F, _ = glow_tts_np.durations_to_frames(logw, length_scale, hp.n_sqz)
+    w = np.exp(logw.astype(F32)) * F32(length_scale)
+    margin = float(np.min(np.abs(w - np.round(w)) / np.maximum(w, F32(1.0))))
+    return int(F), margin
+
+
+def check_frames(frames, ref, n_sqz=2, label=""):
+    """`frames[i]` (device) against `ref[i]` = oracle_frames(...): equal wherever the margin is >= CEIL_MARGIN; below it
+    |dF| <= n_sqz and the utterance is exempt from value checks (at most MAX_EXEMPT of a list).  Returns the exempt indices."""
+    exempt = set()
+    matched = []
+    for i, (f, (F, margin)) in enumerate(zip(frames, ref)):
+        f = int(f)
+        if margin < CEIL_MARGIN:
+            exempt.add(i)
+            print(f"{label} frames: utterance {i} exempt (ceil margin {margin:.2e}): device {f}, oracle {F}")
+            assert abs(f - F) <= n_sqz, (i, f, F, margin)
+        else:
+            assert f == F, (i, f, F, margin)
+        if f == F:
+            matched.append(margin)
+    assert len(exempt) <= MAX_EXEMPT, sorted(exempt)
+    print(f"{label} frames: {len(frames)} utterances, {len(exempt)} exempt, smallest margin still matched {min(matched):.2e}")
+    return exempt
+
+
+# ---- waveforms -----------------------------------------------------------------------------------------------------------
+# f32: the RMS bar of test_vocoder_alone_on_reference_mel; int16 within 1 LSB of the reference's conversion of the oracle's
+# waveform; per sample: RMS hides a one-column seam error, so the largest |error| of any sample is bounded too, at 4x the largest
+# measured on the device (MI355X, tests/test_gpu_config3.py).  The error scales with the waveform, so there are two figures:
+# config 3 end to end (oracle mel -> oracle vocoder; 24 rows, F = 390 ... 936): 3.7e-6; the vocoder sweep's synthetic mels
+# (quiet waveforms; 'high' / 'medium' / 'low', F = 1 ... 1100, batch 1 and ragged batches): 2.1e-7.
+MAX_ABS_END_TO_END = 3.7e-6
+MAX_ABS_SWEEP = 2.1e-7
+F32_WAVE = dict(rms=2e-5, max=4 * MAX_ABS_END_TO_END, lsb=1)
+F32_SWEEP = dict(rms=2e-5, max=4 * MAX_ABS_SWEEP, lsb=1)
+
+
+def f16_wave_bounds(vhp):
+    """The bar of test_f16_mode_against_the_reference for every committed golden of this vocoder geometry: the largest error
+    the reference's own generator under .half() made against its f32 waveform (RMS; max and int16 x 1.5, as there)."""
+    from tests.golden_util import CASES, load_case
+
+    got = [c for c in (load_case(n) for n in CASES) if "ref_half_rms" in c and c["voc_hp"] == vhp]
+    assert got, vhp
+    return dict(rms=max(float(c["ref_half_rms"]) for c in got), max=1.5 * max(float(c["ref_half_max"]) for c in got),
+                lsb=1.5 * max(int(c["ref_half_i16"]) for c in got))
+
+
+def compare_wave(wav, i16, ref, n, bounds=F32_WAVE, label=""):
+    """One row: samples [0, n) against the oracle's float waveform `ref` (RMS, max |error|, int16 against the reference's
+    conversion of `ref`), the rest of the row exactly 0.  Prints and returns the measured values."""
+    wav, i16 = np.asarray(wav), np.asarray(i16)
+    assert ref.shape[0] == n and wav.shape[0] >= n and i16.shape[0] == wav.shape[0], (ref.shape, n, wav.shape, i16.shape)
+    d = wav[:n].astype(np.float64) - ref.astype(np.float64)
+    rms = float(np.sqrt(np.mean(d ** 2)))
+    mx = float(np.abs(d).max())
+    where = int(np.abs(d).argmax())
+    lsb = int(np.abs(i16[:n].astype(np.int32) - audio_np.audio_float_to_int16(ref).astype(np.int32)).max())
+    print(f"{label}: n {n} rms {rms:.2e} max {mx:.2e} (sample {where}) int16 {lsb} LSB")
+    assert np.all(wav[n:] == 0) and np.all(i16[n:] == 0), label
+    assert rms <= bounds["rms"] and mx <= bounds["max"] and lsb <= bounds["lsb"], (label, rms, mx, where, lsb, bounds)
+    return rms, mx, lsb
+
+
+# ---- which kernels ran ---------------------------------------------------------------------------------------------------
+def kernel_signature(eng):
+    """The `kernel_counts()` names that launched since the last `profile_reset()`."""
+    return frozenset(k for k, c in eng.kernel_counts().items() if c > 0)
+
+
+# The column widths of the vocoder's tiles, one entry per kernel family: (label, precision, stage rule, width of the last tile
+# as a function of (C, K)).  Stage rules (ResBlock1 unless named): "conv" = the grouped / single ResBlock convs (C >= 128 in f32,
+# every stage of ResBlock2), "pair" = the fused conv1 + conv2 steps (32 / 64 channels), "mrf" = the one-launch narrow stages
+# (<= 16 channels), "post" = conv_post on the waveform, "f16conv" / "f16pair" = the fp16 generator's grouped convs and pairs.
+TILE_WIDTHS = (
+    # conv_mfma.h T_T = WN * NB * 32 of plan_conv's shapes: TILE_TINY 32, TILE_SMALL and TILE_M128 64, TILE_W128 (and
+    # rb_group_kernel<11, 7, 3, 4>) 128, TILE_NB2 256
+    ("conv_mfma T_T=32", "f32", "conv", lambda C, K: 32),
+    ("conv_mfma T_T=64", "f32", "conv", lambda C, K: 64),
+    ("conv_mfma T_T=128", "f32", "conv", lambda C, K: 128),
+    ("conv_mfma T_T=256", "f32", "conv", lambda C, K: 256),
+    # rb_pair.h / resblock_pair.h T2 = T1 - (K - 1), T1 = 128 * NB (host_launch.h plan_pair: NB = 1 at 64 channels, 2 at 32)
+    ("pair T2", "f32", "pair", lambda C, K: 128 * (2 if C == 32 else 1) - (K - 1)),
+    # mrf_small.h / mrf8: run_mrf_small's T = 256
+    ("mrf_small T", "f32", "mrf", lambda C, K: 256),
+    # voc_out.h POST_TW
+    ("POST_TW", "f32", "post", lambda C, K: 256),
+    # hifigan_f16.h h_tile_dims: HT_WIDE 128 columns (128+ rows or Cin > 64), HT_MID / HT_SLIM 256
+    ("f16 h_tile_dims", "f16", "f16conv", lambda C, K: 128 if C > 64 else 256),
+    # pair_f16.h TO = 32 * NB * WN - (K - 1) of h_pair_tile's shape: 128 columns at C = 128, 256 at C <= 64
+    ("pair_f16 TO", "f16", "f16pair", lambda C, K: (128 if C > 64 else 256) - (K - 1)),
+    # conv_f16.h HPOST_TW
+    ("HPOST_TW", "f16", "post", lambda C, K: 256),
+)
+
+
+def vocoder_tiles(hp, precision="f32"):
+    """The (label, stage, width, halo) tiles a vocoder's kernels use in `precision`; halo = the widest per-side input halo of
+    the conv the tile runs first ((K - 1) * dilation / 2)."""
+    out = []
+    rb1 = hp.resblock == "1"
+    last = len(hp.upsample_rates) - 1
+    for i in range(len(hp.upsample_rates)):
+        C = hp.stage_channels(i)
+        chains = list(zip(hp.resblock_kernel_sizes, hp.resblock_dilation_sizes))
+        halo_all = max((k - 1) * max(d) // 2 for k, d in chains)
+        for label, prec, rule, width in TILE_WIDTHS:
+            if prec != precision:
+                continue
+            if rule == "post":
+                if i == last:
+                    out.append((label, i, width(C, 7), 3))
+                continue
+            if rule in ("pair", "f16pair"):
+                ok = rb1 and (C in (32, 64) if rule == "pair" else C <= 128)
+                if ok:
+                    for k, d in chains:
+                        out.append((f"{label} K={k}", i, width(C, k), (k - 1) * max(d) // 2))
+                continue
+            ok = {"conv": (C >= 128) if rb1 else True, "mrf": rb1 and C <= 16, "f16conv": (C > 128) if rb1 else True}[rule]
+            if ok:
+                out.append((label, i, width(C, 3), halo_all))
+    return sorted(set(out), key=lambda t: (t[1], t[2], t[0]))
+
+
+def edge_frames(hp, tiles, lo, hi):
+    """{F: [(label, stage, width, kind)]} for every F in [lo, hi] at which some stage's (length F * prod(u[:stage + 1])) last
+    tile of some width in `tiles` (vocoder_tiles) is exactly full ("full"), one column wide ("one") or narrower than that
+    kernel's halo ("halo")."""
+    out = {}
+    for F in range(max(1, lo), hi + 1):
+        hits = []
+        for label, stage, width, halo in tiles:
+            L = F * int(np.prod(hp.upsample_rates[: stage + 1]))
+            r = L % width
+            kind = "full" if r == 0 else "one" if r == 1 else "halo" if r < halo else None
+            if kind:
+                hits.append((label, stage, width, kind))
+        if hits:
+            out[F] = hits
+    return out
+
+
+def cover_edges(edges, cap=None):
+    """A small set of frame counts that together hit every (stage, width, kind) edge in `edges` (edge_frames): greedy, the F
+    that hits the most edges not yet hit, the shorter F on a tie (the oracle's cost grows with F)."""
+    left = {(s, w, k) for hits in edges.values() for (_, s, w, k) in hits}
+    chosen = []
+    while left and (cap is None or len(chosen) < cap):
+        F = max(edges, key=lambda f: (len(left & {(s, w, k) for (_, s, w, k) in edges[f]}), -f))
+        gain = left & {(s, w, k) for (_, s, w, k) in edges[F]}
+        if not gain:
+            break
+        chosen.append(F)
+        left -= gain
+    return sorted(chosen)
+
+
+# ---- the vocoder sweep ---------------------------------------------------------------------------------------------------
+def sweep_mel(num_mels, F):
+    """The synthetic vocoder input of frame count F (the launch-count tests' 0.57 + 0.06 randn), seeded by F."""
+    return (0.57 + 0.06 * np.random.default_rng(1000 + F).standard_normal((num_mels, F))).astype(F32)
+
+
+def scan_signatures(eng, v, num_mels, lo, hi, label=""):
+    """{F: kernel_signature} of a lone batch-1 call at every F in [lo, hi]; prints each signature's range."""
+    sigs = {}
+    for F in range(lo, hi + 1):
+        mb = eng.mel_from_numpy(sweep_mel(num_mels, F))
+        eng.profile_reset()
+        eng.hifigan_infer(v, mb, want_float=False)
+        sigs[F] = kernel_signature(eng)
+        mb.free()
+    start = lo
+    for F in range(lo, hi + 1):
+        if F == hi or sigs[F + 1] != sigs[F]:
+            print(f"{label} scan: F {start}..{F}: {sorted(sigs[F])}")
+            start = F + 1
+    return sigs
+
+
+def choose_lengths(sigs, edges=(), cap=12):
+    """One length per signature (its shortest F), then the transitions (F and F + 1 where the signature changes) by increasing
+    F until `cap`; then every F of `edges` (cover_edges: a handful)."""
+    Fs = sorted(sigs)
+    first = {}
+    for F in Fs:
+        first.setdefault(sigs[F], F)
+    chosen = sorted(first.values())
+    trans = [f for F in Fs[:-1] if sigs[F] != sigs[F + 1] for f in (F, F + 1)]
+    for f in trans:
+        if len(chosen) >= cap:
+            break
+        if f not in chosen:
+            chosen.append(f)
+    assert len(first) <= cap, "more kernel signatures than the cap: raise the cap"
+    return sorted(set(chosen) | set(edges))
+
+
+class OracleWaves:
+    """The oracle's waveform per (vocoder, frame count) of the sweep's mels — computed once, shared by the f32 and the fp16
+    comparison of the same mel."""
+
+    def __init__(self):
+        self._c = {}
+        self.seconds = 0.0
+
+    def __call__(self, vsd, vhp, key, F):
+        if (key, F) not in self._c:
+            t = time.perf_counter()
+            self._c[(key, F)] = hifi_gan_np.hifigan_infer(vsd, vhp, sweep_mel(vhp.num_mels, F))
+            self.seconds += time.perf_counter() - t
+        return self._c[(key, F)]
+
+
+def check_lengths(eng, v, vsd, vhp, Fs, oracle, key, bounds=F32_SWEEP, label="", batch=8, solo_rms=1e-5):
+    """Each F in `Fs` as a lone batch-1 call against the oracle, then one ragged padded batch of up to `batch` of them: every
+    row against the oracle and within RMS `solo_rms` of its batch-1 result (1e-5 in f32, as config 4).  Returns the kernel
+    names that ran."""
+    hop = vhp.hop
+    ran = set()
+    solo = {}
+    for F in Fs:
+        mb = eng.mel_from_numpy(sweep_mel(vhp.num_mels, F))
+        eng.profile_reset()
+        wav, i16 = eng.hifigan_infer(v, mb)
+        sig = kernel_signature(eng)
+        ran |= sig
+        mb.free()
+        solo[F] = wav[0]
+        compare_wave(wav[0], i16[0], oracle(vsd, vhp, key, F), F * hop, bounds, f"{label} F={F} B=1")
+    rows = sorted(Fs, key=lambda f: (-f, f))[:batch]  # the batch keeps the longest: the most tiles per row
+    rows = rows[::2] + rows[1::2][::-1]  # ragged, not sorted
+    Fmax = max(rows)
+    mel = np.zeros((len(rows), vhp.num_mels, Fmax), F32)
+    for b, F in enumerate(rows):
+        mel[b, :, :F] = sweep_mel(vhp.num_mels, F)
+    mb = eng.mel_from_numpy(mel, np.array(rows, np.int32))
+    eng.profile_reset()
+    wav, i16 = eng.hifigan_infer(v, mb)
+    ran |= kernel_signature(eng)
+    mb.free()
+    for b, F in enumerate(rows):
+        n = F * hop
+        compare_wave(wav[b], i16[b], oracle(vsd, vhp, key, F), n, bounds, f"{label} F={F} row {b} of B={len(rows)}")
+        d = float(np.sqrt(np.mean((wav[b, :n].astype(np.float64) - solo[F][:n]) ** 2)))
+        assert d <= solo_rms, (label, F, d)
+    return ran
+
+
+# ---- BASELINE config 3 ---------------------------------------------------------------------------------------------------
+def bench_form(eng, g, v, rows, length_scale, seed, audio_settings, threads=1):
+    """Every utterance through the call bench.py's config3 leg makes (`synthesize(..., seed=seed + i)`), from `threads`
+    threads at once -> {i: (frames, f32 row, i16 row)}."""
+    out = {}
+    errs = []
+    lock = threading.Lock()
+    nxt = [0]
+
+    def work():
+        try:
+            while True:
+                with lock:
+                    i = nxt[0]
+                    nxt[0] += 1
+                if i >= len(rows):
+                    return
+                fr, f32, i16 = eng.synthesize(g, v, rows[i], 0.667, length_scale, seed=seed + i, audio_settings=audio_settings,
+                                              want_float=True, frames_per_id_guess=12.0 / max(length_scale, 0.05))
+                out[i] = (int(fr[0]), f32[0], i16[0])
+        except Exception as e:  # noqa: BLE001
+            errs.append(e)
+
+    ts = [threading.Thread(target=work) for _ in range(threads)]
+    [t.start() for t in ts]
+    [t.join() for t in ts]
+    assert not errs, errs
+    assert sorted(out) == list(range(len(rows)))
+    return out
+
+
+def check_load_independence(eng, g, v, rows, length_scale, seed, audio_settings, threads=8, need=(), label=""):
+    """The bench form with `threads` calls in flight and one call at a time: the same frames, float and int16 bits for every
+    utterance (the tile choices that depend on the load must not change a result).  `need`: kernel names the loaded pass must
+    have run.  Returns the lone pass."""
+    eng.profile_reset()
+    busy = bench_form(eng, g, v, rows, length_scale, seed, audio_settings, threads)
+    sig = kernel_signature(eng)
+    lone = bench_form(eng, g, v, rows, length_scale, seed, audio_settings, 1)
+    print(f"{label} {threads} threads in flight: {sorted(sig)}")
+    for k in need:
+        assert k in sig, (k, sorted(sig))
+    for i in range(len(rows)):
+        (fa, wa, ia), (fb, wb, ib) = busy[i], lone[i]
+        assert fa == fb and np.array_equal(wa, wb) and np.array_equal(ia, ib), (label, i, fa, fb)
+    return lone
+
+
+def check_micro_batches(eng, g, v, rows, length_scale, seed, audio_settings, batch=8):
+    """`sharding.synthesize_shard` (rank 0 of 1) at batch 1 and at `batch`: the keys 0 ... n - 1 in both, every utterance the
+    same length and within 1 int16 LSB (a padded batch picks other tiles: another summation order)."""
+    from larynx_amd import sharding
+
+    kw = dict(noise_scale=0.667, length_scale=length_scale, seed=seed, audio_settings=audio_settings)
+    one = sharding.synthesize_shard(eng, g, v, rows, 0, 1, batch=1, **kw)
+    many = sharding.synthesize_shard(eng, g, v, rows, 0, 1, batch=batch, **kw)
+    assert sorted(one) == sorted(many) == list(range(len(rows)))
+    worst = 0
+    for i in range(len(rows)):
+        assert one[i].shape == many[i].shape, (i, one[i].shape, many[i].shape)
+        d = int(np.abs(one[i].astype(np.int32) - many[i].astype(np.int32)).max()) if one[i].size else 0
+        assert d <= 1, (i, d)
+        worst = max(worst, d)
+    print(f"micro-batches of {batch} against batch 1: {len(rows)} utterances, largest difference {worst} LSB")
+    return one, many
+
+
+def check_mels(eng, g, gsd, ghp, rows, length_scale, seed, pick, exempt=(), tol=5e-5, label=""):
+    """The seeded device mel (batch 1, the stream seed + i) of every utterance in `pick` against the oracle fed the same noise
+    field (`gauss_noise(seed + i, 1, M, F + 7)`: what the seeded call draws).  Returns {i: oracle raw mel}."""
+    refs = {}
+    worst = 0.0
+    for i in pick:
+        if i in exempt:
+            continue
+        mel = eng.glow_infer(g, rows[i], 0.667, length_scale, seed=seed + i)
+        F = int(mel.frames[0])
+        raw = mel.numpy("raw")[0][:, :F]
+        mel.free()
+        noise = eng.gauss_noise(seed + i, 1, ghp.mel_channels, F + 7)[0]
+        ref = glow_tts_np.glow_tts_infer(gsd, ghp, rows[i], noise, 0.667, length_scale)
+        assert ref.shape[1] == F, (i, ref.shape, F)
+        e = float(np.abs(raw - ref).max())
+        assert e <= tol, (label, i, F, e)
+        worst = max(worst, e)
+        refs[i] = ref
+    print(f"{label} mels: {len(refs)} utterances against the oracle, largest max-abs {worst:.2e}")
+    return refs
+
+
+def check_waves_end_to_end(eng, g, v, gsd, vsd, ghp, vhp, rows, length_scale, seed, audio_settings, pick, lone, ref_mels,
+                           batch=8, bounds=F32_WAVE, label=""):
+    """The utterances in `pick` end to end against the oracle (oracle mel -> oracle vocoder) in both forms: the bench form's
+    float rows (`lone`, batch 1) and the rows of their micro-batch of `batch` (sharding.micro_batches: same grouping),
+    re-run through glow_infer(row_seeds=...) + hifigan_infer."""
+    from larynx_amd import sharding
+
+    hop = vhp.hop
+    groups = sharding.micro_batches(list(range(len(rows))), [len(r) for r in rows], batch)
+    refs = {}
+    for i in pick:
+        ref_mel = ref_mels.get(i)
+        if ref_mel is None:
+            noise = eng.gauss_noise(seed + i, 1, ghp.mel_channels, lone[i][0] + 7)[0]
+            ref_mel = glow_tts_np.glow_tts_infer(gsd, ghp, rows[i], noise, 0.667, length_scale)
+        refs[i] = hifi_gan_np.hifigan_infer(vsd, vhp, audio_np.mel_to_vocoder_input(ref_mel, audio_settings))
+        F, wav, i16 = lone[i]
+        assert F * hop == refs[i].shape[0]
+        compare_wave(wav, i16, refs[i], F * hop, bounds, f"{label} utterance {i} (F={F}) B=1")
+    for grp in groups:
+        mine = [i for i in pick if i in grp]
+        if not mine:
+            continue
+        mel = eng.glow_infer(g, [np.asarray(rows[j], np.int64) for j in grp], 0.667, length_scale,
+                             row_seeds=[seed + j for j in grp], audio_settings=audio_settings)
+        wb, ib = eng.hifigan_infer(v, mel)
+        for i in mine:
+            b = grp.index(i)
+            F = lone[i][0]
+            assert int(mel.frames[b]) == F
+            compare_wave(wb[b], ib[b], refs[i], F * hop, bounds, f"{label} utterance {i} (F={F}) row {b} of B={len(grp)}")
+        mel.free()
+    return refs
