@@ -16,10 +16,7 @@ static int run_layernorm(Worker* w, const float* x, const float* res, const floa
 
 // ---- column-owner launches (coltile.h).  Each returns 1 when the shape is not one the kernel takes (the caller then runs
 // the separate launches), 0 when launched.
-static bool glow_fuse_on(const Worker* w) {  // the option as the call saw it at its start (glow_run)
-  static const bool off = [] { const char* e = std::getenv("MI355TTS_NO_GLOW_FUSE"); return e && std::atoi(e) != 0; }();
-  return !off && w->o_glow_fuse;
-}
+static bool glow_fuse_on(const Worker* w) { return !w->opt.env.glow_fuse_off && w->opt.glow_fuse; }
 static int run_oproj_ln(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const GlowLayer& L, const float* att, float* x, int H,
                         long long bs, int ld, const int* d_len, int host_len, int B, int Pmax) {
   if (!glow_fuse_on(w) || !L.o16.ok || H > COL_MAXROWS || ld % 4 || Pmax <= 0) return 1;
@@ -88,7 +85,7 @@ static int run_wn_f16(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const G
   const double mac = (double)n * 2.0 * H * H * h.kernel_size_dec + (double)(n - 1) * 2.0 * H * H;
   ProfScope ps(ctx, w, KC_GLOW_DEC_CONV, 2.0 * mac * (double)F2max * B);
   // MI355TTS_WN_REPEAT (probe): the launch N times — it is idempotent; run 2 .. N find the block's weights in L2
-  static const int repeat = [] { const char* e = std::getenv("MI355TTS_WN_REPEAT"); return e ? std::max(1, std::atoi(e)) : 1; }();
+  const int repeat = std::max(1, w->opt.env.wn_repeat);
   for (int r = 0; r < repeat; ++r) {
     if (H == 192)
       hipLaunchKernelGGL((wn_f16_kernel<5, 24, 3, 10>), grid, dim3(256), 0, w->stream, a);
@@ -116,8 +113,7 @@ static int launch_enc_conv(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, co
 static int launch_ln_conv(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const DevConv& c, ConvArgs a, const float* raw, float* normed,
                           float* scratch, const float* gamma, const float* beta, int relu, int C, long long bs, int ld, const int* d_len,
                           int B, int Pmax, int glow_tiles, int host_len, bool solo_tiles) {
-  static const bool no_ln = [] { const char* e = std::getenv("MI355TTS_LIN16_NO_LN"); return e && std::atoi(e) != 0; }();
-  if (!no_ln && glow_fuse_on(w)) {
+  if (!w->opt.env.lin16_no_ln && glow_fuse_on(w)) {
     Lin16Ln ln{gamma, beta, relu, normed};
     a.x = raw;
     if (run_lin16(ctx, w, c, a, gm->arena, B, Pmax, KC_GLOW_ENC_CONV, host_len, solo_tiles, &ln) == 0) return 0;
@@ -260,9 +256,6 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
   const mi355tts_audio_settings* audio = call.audio;
   const uint32_t flags = call.flags;
   hipStream_t s = w->stream;
-  w->o_glow_fuse = ctx->glow_fuse.load();  // one read per call: the launch helpers below use the snapshot
-  w->o_gate16 = ctx->gate16.load();
-  w->o_gate16_wide = ctx->gate16_wide.load();
   // the `half` switch as this call saw it at its start: the decoder's WaveNets in fp16 (wn_f16.h)
   const bool glow_f16 = gm->f16_ok && gm->precision.load() == MI355TTS_PRECISION_F16;
   const float* A = gm->arena;
@@ -271,8 +264,7 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
   const bool in_dev = (flags & MI355TTS_IN_DEVICE) != 0;
   const int enc_host_len = B == 1 ? id_lens[0] : -1;
   // workgroup target per GlowTTS conv launch (tile-shape choice; tuning knob MI355TTS_GLOW_TILES)
-  static const int glow_tiles_env = [] { const char* e = std::getenv("MI355TTS_GLOW_TILES"); return e ? std::atoi(e) : 0; }();
-  const int glow_tiles = call.solo_tiles ? (1 << 30) : glow_tiles_env > 0 ? glow_tiles_env : 1024;
+  const int glow_tiles = call.solo_tiles ? (1 << 30) : w->opt.env.glow_tiles > 0 ? w->opt.env.glow_tiles : 1024;
   {
     long long sum = 0;
     for (int b = 0; b < B; ++b) sum += id_lens[b];
@@ -373,7 +365,7 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
       kn_hit(ctx, KN_ATTENTION);
       const dim3 ag((Pmax + 31) / 32, nh, B);
       const int dkh = H / nh;
-      static const bool att_big = [] { const char* e = std::getenv("MI355TTS_ATT_BIG_LDS"); return e && std::atoi(e) != 0; }();  // (A/B runs)
+      const bool att_big = w->opt.env.att_big_lds;  // (A/B runs)
 #define ATT_LAUNCH_P(NK, X, PM)                                                                                             \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(attention_mfma_kernel<NK, X, PM>), ag, dim3(512), 0, s, qkv, 3 * bsH, P, d_len, H, nh, \
                      h.window_size, A + L.ek, A + L.ev, t2, bsH, P)

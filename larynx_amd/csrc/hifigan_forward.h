@@ -217,15 +217,11 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   // same values in the same order: results do not depend on the load.
   // `serial_branches` (profiling / tests) additionally folds the average into the chains'
   // last epilogues (in-place accumulation, one output buffer).
-  // the option flags, read once: a call never mixes schedules if an option changes while it runs
-  const bool opt_serial = ctx->serial_branches.load(), opt_group = ctx->mrf_group.load(), opt_small = ctx->mrf_small.load();
-  w->o_rb_conv = ctx->rb_conv.load();
-  w->o_rb_pair = ctx->rb_pair.load();
-  w->o_group_promote = ctx->group_promote.load();
+  const CallOptions& opt = w->opt;  // as read when the worker was checked out: a call never mixes schedules if an option changes while it runs
   const int prec = hm->precision.load();
   const bool f16 = prec == MI355TTS_PRECISION_F16;  // the native fp16 generator (hifigan_f16.h): its own schedule, chains always write their own planes
   if (f16 && !hm->f16_ok) return fail(MI355TTS_ERR_INVALID, "internal: fp16 mode on a vocoder it does not cover");
-  const bool split_out = f16 || hifi_split_out(opt_serial, h);
+  const bool split_out = f16 || hifi_split_out(opt.serial_branches, h);
   // grouped (default): the chains stay on ONE stream and the same-geometry launches of a step go out as
   // one grouped launch (conv_group_kernel / pair_group_kernel) — the chip is filled from one launch, with
   // no stream fork/join and independently of what else is in flight.  "mrf_group" = 0 restores the
@@ -234,9 +230,9 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   // +3 % utterances/s at 6 calls in flight with the round-2 mid-way kernels; with the final tiles the grouped
   // launch wins under load too (f32 +1.3 %, split-bf16 +5 %, same box), so the option is off by default.
   // Every form runs the same tiles with the same code: results do not depend on the load.
-  const bool busy = ctx->adaptive_schedule.load() && ctx->active_calls.load(std::memory_order_relaxed) > 1;
-  const bool grouped = split_out && nk == 3 && opt_group && !busy;
-  const bool concurrent = split_out && !opt_group && !busy;
+  const bool busy = opt.adaptive_schedule && ctx->active_calls.load(std::memory_order_relaxed) > 1;
+  const bool grouped = split_out && nk == 3 && opt.mrf_group && !busy;
+  const bool concurrent = split_out && !opt.mrf_group && !busy;
   if (concurrent && !w->aux[0]) {
     for (int i = 0; i < 2; ++i) {
       HIPCHECK(hipStreamCreateWithFlags(&w->aux[i], hipStreamNonBlocking));
@@ -248,8 +244,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   // k-split and with it the summation order, so a load-dependent choice would make results
   // depend on the load.  (With the final tile set 300, 700 and 1024 measured the same within
   // noise for the forked schedule.)  Tuning knob: MI355TTS_RB_TILES.
-  static const int rb_env = [] { const char* e = std::getenv("MI355TTS_RB_TILES"); return e ? std::atoi(e) : 0; }();
-  const int rb_tiles = rb_env > 0 ? rb_env : 1024;
+  const int rb_tiles = opt.env.rb_tiles > 0 ? opt.env.rb_tiles : 1024;
   const int voc_host_len = B == 1 ? mel->frames[0] : -1;
   int pads = call.pad_before + call.pad_after;
   bool any_f32 = wav_f32 != nullptr, any_i16 = wav_i16 != nullptr;
@@ -275,15 +270,13 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   const size_t o_wav2 = lay.o_wav2, o_fbuf = lay.o_fbuf;
   const int* d_frames = mel->frames_dev;
 
-  static const bool voc_out_off = [] { const char* e = std::getenv("MI355TTS_NO_VOC_OUT"); return e && std::atoi(e) != 0; }();
   const long long peak_ld = (long long)(Nld / POST_TW + 2);
   bool peak_parts_ready = false;  // post_conv_kernel left the per-workgroup maxima of the FINAL waveform
   bool vo = true;
   if (f16) {
     if ((size_t)((mel->M + 7) / 8) * F * 16 > lay.plane * sizeof(float)) return fail(MI355TTS_ERR_INVALID, "internal: mel octets exceed a plane buffer");
     peak_parts_ready = any_i16 && !denoise;
-    CHECK(hifigan_body_f16(ctx, w, hm, mel, buf, wav, Nld, peak_parts_ready ? reinterpret_cast<float*>(peak) : nullptr, peak_ld, voc_host_len,
-                           opt_group, opt_group && w->o_rb_pair, s));
+    CHECK(hifigan_body_f16(ctx, w, hm, mel, buf, wav, Nld, peak_parts_ready ? reinterpret_cast<float*>(peak) : nullptr, peak_ld, voc_host_len, s));
   } else {
   // stage input: `cur[0]` alone, or the nk chain outputs cur[0..nk) still to be averaged
   float* cur[3] = {buf[0], nullptr, nullptr};
@@ -323,7 +316,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
     ch = cout;
     const long long bs = (long long)ch * ldo;
     const float inv_nk = 1.0f / (float)nk;
-    if (opt_small && !opt_serial && i < (int)hm->mrf.size() && hm->mrf[i].ok) {
+    if (opt.mrf_small && !opt.serial_branches && i < (int)hm->mrf.size() && hm->mrf[i].ok) {
       // narrow stage (C = 8 / 16): the three chains in ONE launch on LDS-resident tiles, written as two sums
       // (k = 3 + k = 7, and k = 11) that the consumer adds and divides by nk on load.  The stage-input plane and
       // the previous stage's chain outputs are dead once the upsampler has read them.
@@ -382,12 +375,12 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
       const bool fold = last && !split_out;  // serial form: the MRF average is folded into the chains' last epilogues
       sp.pair.ok = false;
       if (h.resblock_type == 1) {  // ResBlock1.forward, models.py:91-98
-        plan_pair(rc.c1, rc.c2, c.rin, sp.dst, bs, ldo, d_frames, mul, rc.dil, fold ? inv_nk : 1.0f, fold ? (j > 0) : 0, B, Lout,
+        plan_pair(opt, rc.c1, rc.c2, c.rin, sp.dst, bs, ldo, d_frames, mul, rc.dil, fold ? inv_nk : 1.0f, fold ? (j > 0) : 0, B, Lout,
                   voc_host_len, &sp.pair, prec);
         if (sp.pair.ok) return 0;
         ConvArgs a = base_args(c.rin, bs, ldo, d_frames, mul, c.tb, bs, ldo, d_frames, mul, rc.dil, (kk * rc.dil - rc.dil) / 2);
         a.in_slope = 0.1f;
-        CHECK(plan_conv(rc.c1, a, EPI_LINEAR, B, Lout, KC_RESBLOCK, rb_tiles, voc_host_len, &sp.c1, prec));
+        CHECK(plan_conv(opt, rc.c1, a, EPI_LINEAR, B, Lout, KC_RESBLOCK, rb_tiles, voc_host_len, &sp.c1, prec));
         ConvArgs c2 = base_args(c.tb, bs, ldo, d_frames, mul, sp.dst, bs, ldo, d_frames, mul, 1, (kk - 1) / 2);
         c2.in_slope = 0.1f;
         c2.res = c.rin;
@@ -395,7 +388,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
           c2.alpha = inv_nk;
           c2.accum = j > 0;
         }
-        CHECK(plan_conv(rc.c2, c2, EPI_LINEAR, B, Lout, KC_RESBLOCK, rb_tiles, voc_host_len, &sp.c2, prec));
+        CHECK(plan_conv(opt, rc.c2, c2, EPI_LINEAR, B, Lout, KC_RESBLOCK, rb_tiles, voc_host_len, &sp.c2, prec));
       } else {  // ResBlock2.forward, models.py:136-141
         ConvArgs a = base_args(c.rin, bs, ldo, d_frames, mul, sp.dst, bs, ldo, d_frames, mul, rc.dil, (kk * rc.dil - rc.dil) / 2);
         a.in_slope = 0.1f;
@@ -404,7 +397,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
           a.alpha = inv_nk;
           a.accum = j > 0;
         }
-        CHECK(plan_conv(rc.c1, a, EPI_LINEAR, B, Lout, KC_RESBLOCK, rb_tiles, voc_host_len, &sp.c1, prec));
+        CHECK(plan_conv(opt, rc.c1, a, EPI_LINEAR, B, Lout, KC_RESBLOCK, rb_tiles, voc_host_len, &sp.c1, prec));
         sp.c2.empty = true;
       }
       return 0;
@@ -423,8 +416,8 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
         if (nk == 3 && !sp[0].pair.ok && !sp[1].pair.ok && !sp[2].pair.ok) {  // tile shape of the step: before the schedule is chosen
           ConvPlan* c1s[3] = {&sp[0].c1, &sp[1].c1, &sp[2].c1};
           ConvPlan* c2s[3] = {&sp[0].c2, &sp[1].c2, &sp[2].c2};
-          promote_group_plans(ctx, w, c1s, nk);
-          promote_group_plans(ctx, w, c2s, nk);
+          promote_group_plans(opt, c1s, nk);
+          promote_group_plans(opt, c2s, nk);
         }
         bool done = false;
         if (grouped) {
@@ -491,7 +484,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   }
   // Option "voc_out" (default 1): conv_post + tanh + the rows' peaks in ONE dedicated launch and the delivery of the rows in one
   // more (voc_out.h); 0 = the generic conv tile, zero_tail, absmax, to_int16 and a copy / fill per piece of every row.
-  vo = !voc_out_off && ctx->voc_out.load() && hm->post_C == ch && hm->post.K == 7 && ldin % 4 == 0;
+  vo = !opt.env.voc_out_off && opt.voc_out && hm->post_C == ch && hm->post.K == 7 && ldin % 4 == 0;
   if (prow && !vo) return fail(MI355TTS_ERR_INVALID, "internal: per-row outputs need the voc_out tail");
   if (vo) {  // x = tanh(conv_post(leaky_relu(x)))  — default slope 0.01 (models.py:198-200)
     PostArgs a;

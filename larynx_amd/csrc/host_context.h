@@ -47,10 +47,8 @@ static inline void kn_add(int k) {
 // hipStreamQuery without sleeping for the first 60 us (short waits: the frame-count read-back on an idle GPU, a warm vocoder tail),
 // then poll every ~20 us from nanosleep, with the calling thread's timer slack lowered to 1 us for the duration of the wait
 // (the default slack of 50 us would add that much to every wake-up) and restored afterwards.
-// MI355TTS_SYNC_MODE: 0 = hipStreamSynchronize, 1 = blocking event, 2 = query + 20 us sleep (no spin phase, default slack),
-// 3 = adaptive.  Read once.
-// Option "sync_mode" (mi355tts_set_option; process-wide, like the environment variable that seeds it) selects the mode at run time.
-static std::atomic<int> g_sync_mode{[] { const char* e = std::getenv("MI355TTS_SYNC_MODE"); return e ? std::atoi(e) : 3; }()};
+// g_sync_mode (host_options.h): 0 = hipStreamSynchronize, 1 = blocking event, 2 = query + 20 us sleep (no spin phase, default
+// slack), 3 = adaptive.
 static hipError_t mi355_sync(hipStream_t s) {
   const int mode = g_sync_mode.load(std::memory_order_relaxed);
   if (mode == 1) {
@@ -101,10 +99,6 @@ static hipError_t mi355_sync(hipStream_t s) {
   return hipStreamSynchronize(s);
 }
 
-#ifndef MI355TTS_CALL_COALESCE_DEFAULT
-#define MI355TTS_CALL_COALESCE_DEFAULT 0  // lanes of host_join.h's whole-call coalescing (0 = off)
-#endif
-
 struct Worker {
   hipStream_t stream = nullptr;
   char* arena = nullptr;
@@ -128,11 +122,7 @@ struct Worker {
   hipStream_t aux[2] = {nullptr, nullptr};
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_join[2] = {nullptr, nullptr};
-  // the context's kernel-selection options as THIS call saw them at its start (glow_run / hifigan_run snapshot them once, so
-  // a mi355tts_set_option from another thread never changes a call's schedule half way through)
-  bool o_glow_fuse = true, o_gate16 = true, o_rb_conv = true, o_rb_pair = true, o_group_promote = true;
-  bool o_snake = true;  // grouped launches whose workgroups are all resident go out in the snake order (group_snake_order)
-  int o_gate16_wide = 512;  // wide passes (at least this many 16-row tiles; 0 = never): two row tiles per gate16 workgroup
+  CallOptions opt;  // what selects this call's kernels, tiles and schedule: filled when the worker is checked out (acquire_worker)
 };
 
 struct mi355tts_ctx {
@@ -144,43 +134,16 @@ struct mi355tts_ctx {
   int next_id = 1;
   std::vector<Worker*> free_workers;
   std::vector<Worker*> all_workers;
-  // option flags: written by mi355tts_set_option / _set_profiling while calls are in flight on other threads -> atomics;
-  // a call reads each flag ONCE at its start (glow_run / hifigan_run copy them: locals, and Worker::o_* for the launch
-  // helpers) so one call never mixes schedules
+  ContextOptions opts;  // mi355tts_set_option's (host_options.h); calls read them through Worker::opt
   std::atomic<bool> profiling{false};
-  std::atomic<bool> serial_branches{false};
   // calls currently holding a worker; with "adaptive_schedule" on and more than one in flight the vocoder
   // launches the members of a grouped step one by one (and never forks its MRF chains)
   std::atomic<int> active_calls{0};
   // calls in flight per hardware-queue group (index = Worker::qgroup; guarded by `mu`): acquire_worker hands out the free worker
   // whose group is the least busy
   std::vector<int> qgroup_busy;
-  std::atomic<bool> adaptive_schedule{false};
-  std::atomic<int> gate16_wide{512};  // ... with two row tiles per workgroup in passes of at least this many 16-row tiles (0 = never; same bits)
-  std::atomic<bool> gate16{true};     // GlowTTS WaveNet gate convs on 16-row tiles (gate16.h) when the launch is small
-  // GlowTTS column-owner launches (coltile.h: block tails, conv_o + LayerNorm) AND the whole-tile-in-LDS convs of
-  // gate16.h's lin16_kernel (FFN / duration predictor / prenet / 1 x 1 convs, LayerNorm prologues): 0 = the generic tiles
-  std::atomic<bool> glow_fuse{true};
-  std::atomic<bool> voc_out{true};    // conv_post + peak and the delivery of the rows as two dedicated launches (voc_out.h); 0 = round 4's ten
-  std::atomic<bool> mrf_small{true};  // narrow stages (C = 8 / 16) as one fused launch per stage (mrf_small.h)
-  std::atomic<bool> mrf_group{true};  // grouped launches of the MRF chains' same-geometry convs (hifigan_forward.h)
-  std::atomic<bool> rb_conv{true};    // grouped 128-row launches on the continuous-stream tile (rb_conv.h; same bits)
-  std::atomic<bool> group_promote{true};  // batch-1 ResBlock steps move to the 128-row tile when the snake deal is balanced (promote_group_plans)
-  // Grouped launches whose workgroups are all resident at once are laid out as a snake over the dispatcher's rounds
-  // (group_snake_order).  That order encodes an OBSERVED dispatcher rule (workgroup i -> CU i mod #CUs);
-  // mi355tts_dispatch_selfcheck times it against the plain order on this device (first 'high'-class vocoder load) and turns
-  // it off where it does not win (a partitioned GPU, another CU count, a firmware that deals differently).  The ORDER of a
-  // launch's workgroups never changes a result; the promotion rule (which picks the TILE, i.e. the summation order) is
-  // decided from the CU count and the geometry alone and is never touched by a timing.
-  std::atomic<bool> group_snake{true};
   std::atomic<int> selfcheck_state{0};  // 0 = not run, 4 = running, 1 = snake kept, 2 = snake order disabled, 3 = skipped / failed
   float selfcheck_plain_us = 0.f, selfcheck_snake_us = 0.f;
-  std::atomic<bool> rb_pair{true};    // fused ResBlock steps (64 / 32 channels) on the 4-wave tile without a k-split (rb_pair.h)
-  // Whole-call coalescing (host_join.h): concurrent batch-1 mi355tts_synthesize calls become the rows of fused padded calls,
-  // at most `call_coalesce` of them in flight (0 = off).  A caller that finds a lane free while other passes are in flight
-  // gathers for up to `call_coalesce_window_us`; a lone caller never waits.
-  std::atomic<int> call_coalesce{MI355TTS_CALL_COALESCE_DEFAULT};
-  std::atomic<int> call_coalesce_window_us{300};
   std::mutex join_mu;
   std::condition_variable join_cv;
   std::vector<struct CallReq*> join_q;  // waiting requests in arrival order (under join_mu, like everything below)
@@ -217,19 +180,6 @@ static inline void kn_hit(mi355tts_ctx* ctx, int k) {
   ctx->kn[k].fetch_add(1, std::memory_order_relaxed);
 }
 
-// The kernel-selection options as a call sees them: taken when the call checks its worker out, so EVERY entry point (the op /
-// bench entry points and the denoiser bias too, not only glow_run / hifigan_run) launches under the context's current options
-// and never under what the worker's previous call left behind.
-static void snapshot_options(mi355tts_ctx* ctx, Worker* w) {
-  w->o_glow_fuse = ctx->glow_fuse.load();
-  w->o_gate16 = ctx->gate16.load();
-  w->o_rb_conv = ctx->rb_conv.load();
-  w->o_rb_pair = ctx->rb_pair.load();
-  w->o_group_promote = ctx->group_promote.load();
-  w->o_snake = ctx->group_snake.load();
-  w->o_gate16_wide = ctx->gate16_wide.load();
-}
-
 static int acquire_worker(mi355tts_ctx* ctx, Worker** out) {
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -240,7 +190,7 @@ static int acquire_worker(mi355tts_ctx* ctx, Worker** out) {
       if (!ctx->qgroup_busy.empty()) {
         // (MI355TTS_QUEUE_POLICY = 1, probe: an idle queue first, otherwise the BUSIEST one — exclusive queues for as many calls as
         // there are queues, the rest piled on one)
-        static const int policy = [] { const char* e = std::getenv("MI355TTS_QUEUE_POLICY"); return e ? std::atoi(e) : 0; }();
+        const int policy = g_env.queue_policy;
         int best = 1 << 30;
         for (size_t i = ctx->free_workers.size(); i-- > 0;) {
           const int g = ctx->free_workers[i]->qgroup;
@@ -257,7 +207,7 @@ static int acquire_worker(mi355tts_ctx* ctx, Worker** out) {
       if ((*out)->qgroup >= 0 && (*out)->qgroup < (int)ctx->qgroup_busy.size()) ctx->qgroup_busy[(*out)->qgroup] += 1;
       (*out)->arena_pos = 0;
       (*out)->flop_scale = 1.0;
-      snapshot_options(ctx, *out);
+      snapshot_options(ctx->opts, ctx->ncu, &(*out)->opt);
       ctx->active_calls.fetch_add(1, std::memory_order_relaxed);
       return 0;
     }
@@ -281,7 +231,7 @@ static int acquire_worker(mi355tts_ctx* ctx, Worker** out) {
     ctx->all_workers.push_back(w);
   }
   ctx->active_calls.fetch_add(1, std::memory_order_relaxed);
-  snapshot_options(ctx, w);
+  snapshot_options(ctx->opts, ctx->ncu, &w->opt);
   *out = w;
   return 0;
 }

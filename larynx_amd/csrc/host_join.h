@@ -140,7 +140,7 @@ static int call_join(mi355tts_ctx* ctx, CallReq& req, int lanes) {
       // lead the next pass
       if (ctx->join_inflight > 0) {
         // other passes keep the GPU busy: gather the callers that are on their way back from the pass that just finished
-        const int window_us = ctx->call_coalesce_window_us.load();
+        const int window_us = ctx->opts.call_coalesce_window_us.load();
         if (window_us > 0) {
           ctx->join_gathering = true;
           const auto deadline = clock::now() + std::chrono::microseconds(window_us);

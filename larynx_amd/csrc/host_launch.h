@@ -67,12 +67,10 @@ template <> struct ConvCfg<11> { static constexpr int HALO = 56; };
 //           whose rows are whole 128-row groups and that yield >= 256 128-column tiles.  (Measured against the 8-wave
 //           128 x 128 form: +1.4 % on the class — finer granularity, four workgroups per CU.)
 enum TileShape { TILE_SMALL = 0, TILE_W128 = 1, TILE_NB2 = 2, TILE_TINY = 3, TILE_LAST = 3, TILE_M128 = 4 };
-static thread_local int g_pin_tile = -1;  // set by mi355tts_bench_conv1d only
 
-// option "rb_conv" as the running call saw it (set by run_plan from the worker's snapshot: launch_conv_k has no worker)
-static thread_local bool g_rb_conv_on = true;
+// rb_conv: the call's option "rb_conv" and not MI355TTS_NO_RB_CONV (the upsamplers' continuous-stream tile)
 template <int K, int EPI>
-static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const ConvArgs& a) {
+static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const ConvArgs& a, bool rb_conv) {
   constexpr int HALO = ConvCfg<K>::HALO;
   constexpr int CI_SMALL = (K == 1) ? 64 : 32;
   constexpr bool PAIRED = (EPI == EPI_GATE || EPI == EPI_COUPLING);
@@ -91,8 +89,7 @@ static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const Conv
     if (shape == TILE_M128) {  // the polyphase upsampler's virtual rows, 128 per workgroup from one staged input tile
       if constexpr (K == 2) {
         // the continuous-stream tile (rb_conv.h; same bits): taps 2 — every upsampler of the shipped vocoders (k_u = 2 u)
-        static const bool rb_off = [] { const char* e = std::getenv("MI355TTS_NO_RB_CONV"); return e && std::atoi(e) != 0; }();
-        if (!rb_off && g_rb_conv_on && a.Cin % 16 == 0 && !a.res && !a.accum && a.alpha == 1.0f) {
+        if (rb_conv && a.Cin % 16 == 0 && !a.res && !a.accum && a.alpha == 1.0f) {
           if (a.x2 && a.x3) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_conv_kernel<2, 4, EPI_UPSAMPLE, true>), grid, dim3(256), 0, s, a);
           else if (!a.x2) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_conv_kernel<2, 4, EPI_UPSAMPLE, false>), grid, dim3(256), 0, s, a);
           if ((a.x2 && a.x3) || !a.x2) {
@@ -124,12 +121,6 @@ static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const Conv
   return fail(MI355TTS_ERR_INVALID, "paired epilogues run on 32-row tiles (MB == 1)");
 }
 
-// workgroups a launch must yield before the 128-row tile is used (tests lower it to reach the shape at small sizes)
-static long long m128_min_tiles() {
-  const char* e = std::getenv("MI355TTS_M128_MIN_TILES");
-  return e ? std::atoll(e) : 256;
-}
-
 // A conv launch, decided but not yet issued: arguments, tile shape and grid.
 struct ConvPlan {
   ConvArgs a;
@@ -153,7 +144,7 @@ enum Bf16Cfg {
 
 // `a` arrives with every tensor/epilogue field filled; this picks the tile and
 // template instance.  n_max = largest GEMM-N extent over the batch rows.
-static int plan_conv(const DevConv& c, ConvArgs a, int epi, int B, int n_max, int cls, int min_tiles, int host_len, ConvPlan* out,
+static int plan_conv(const CallOptions& o, const DevConv& c, ConvArgs a, int epi, int B, int n_max, int cls, int min_tiles, int host_len, ConvPlan* out,
                      int precision = 0) {
   out->empty = true;
   out->bf16 = 0;
@@ -182,8 +173,7 @@ static int plan_conv(const DevConv& c, ConvArgs a, int epi, int B, int n_max, in
                          (c.K == 3 || c.K == 5 || c.K == 7 || c.K == 11) &&
                          (c.K - 1) * a.dil + ((4 - a.pad % 4) % 4) <= (c.K == 3 ? 16 : c.K == 5 ? 28 : c.K == 7 ? 76 : 56);
   // the polyphase upsamplers (two taps) in the split-bf16 mode too: 0.24 ms of f32 work per 'high' utterance otherwise
-  static const bool no_bf_ups = [] { const char* e = std::getenv("MI355TTS_NO_BF16_UPS"); return e && std::atoi(e) != 0; }();
-  const bool bf_ups = half_on && !no_bf_ups && epi == EPI_UPSAMPLE && c.K == 2 && (c.K - 1) * a.dil + ((4 - a.pad % 4) % 4) <= 4;
+  const bool bf_ups = half_on && !o.env.bf16_ups_off && epi == EPI_UPSAMPLE && c.K == 2 && (c.K - 1) * a.dil + ((4 - a.pad % 4) % 4) <= 4;
   if (bf_linear || bf_ups) {
     a.w16 = c.w16;
     a.nslab = c.nslab16;
@@ -197,8 +187,7 @@ static int plan_conv(const DevConv& c, ConvArgs a, int epi, int B, int n_max, in
     int cfg, rows_t, cols_t;
     if (c.mtiles16 % 4 == 0) {
       const long long tiles_a = (long long)((n_max + 127) / 128) * (c.mtiles16 / 4) * B;
-      static const bool no_k = [] { const char* e = std::getenv("MI355TTS_NO_BF_K"); return e && std::atoi(e) != 0; }();
-      cfg = tiles_a >= 256 ? BF_A : (no_k ? BF_B : BF_K);
+      cfg = tiles_a >= 256 ? BF_A : (o.env.bf_k_off ? BF_B : BF_K);
       rows_t = 128;
       cols_t = cfg == BF_B ? 32 : 128;
     } else if (c.mtiles16 == 2) {
@@ -237,14 +226,10 @@ static int plan_conv(const DevConv& c, ConvArgs a, int epi, int B, int n_max, in
   else if (tiles(128) >= want) shape = TILE_W128;
   else if (tiles(64) >= want) shape = TILE_SMALL;
   bool pinned = false;
-  {  // tuning / test knob: MI355TTS_FORCE_TILE=0|1|2 pins the tile shape
-    static const int forced = [] {
-      const char* e = std::getenv("MI355TTS_FORCE_TILE");
-      return e ? std::atoi(e) : -1;
-    }();
-    int f = forced;
-    if (const char* dyn = std::getenv("MI355TTS_FORCE_TILE_DYNAMIC")) f = std::atoi(dyn);
-    if (g_pin_tile >= 0) f = g_pin_tile;
+  {  // tuning / test knobs: MI355TTS_FORCE_TILE[_DYNAMIC]=0|1|2|3 pin the tile shape, the bench entry's pin ahead of both
+    int f = o.env.force_tile;
+    if (o.env.force_tile_dynamic != KNOB_UNSET) f = o.env.force_tile_dynamic;
+    if (o.pin_tile >= 0) f = o.pin_tile;
     if (f >= TILE_SMALL && f <= TILE_LAST) {
       shape = f;
       pinned = true;
@@ -260,20 +245,17 @@ static int plan_conv(const DevConv& c, ConvArgs a, int epi, int B, int n_max, in
     // A 64-row upsampler (the last stage of 'high': 64 -> 32 channels x 2 phases, two taps) is bound by its input planes, not
     // by its matrix work (81 MB against 1.3 GFLOP): the 128-column shape is ONE m-tile high, so two workgroups stage every
     // input tile; the 64-row x 64-column shape stages it once.  MI355TTS_UPS64=0: the shape rule above (A/B runs).
-    static const bool ups64 = [] { const char* e = std::getenv("MI355TTS_UPS64"); return !e || std::atoi(e) != 0; }();
-    if (ups64 && !pinned && epi == EPI_UPSAMPLE && c.MB == 2 && rows32 == 2 && shape == TILE_W128 && tiles(64) >= 256) shape = TILE_SMALL;
+    if (o.env.ups64 && !pinned && epi == EPI_UPSAMPLE && c.MB == 2 && rows32 == 2 && shape == TILE_W128 && tiles(64) >= 256) shape = TILE_SMALL;
   }
   if (shape == TILE_W128 && MB == 2) {
     MB = 1;
     ytiles = rows32;
   }
   {
-    static const bool no_m128 = [] { const char* e = std::getenv("MI355TTS_NO_M128"); return e && std::atoi(e) != 0; }();
-    static const bool no_m128u = [] { const char* e = std::getenv("MI355TTS_NO_M128_UPS"); return e && std::atoi(e) != 0; }();
     const bool resblock_ok = epi == EPI_LINEAR && cls == KC_RESBLOCK && c.K >= 3;
-    const bool upsample_ok = epi == EPI_UPSAMPLE && !no_m128u && c.K >= 1 && c.K <= 3;  // 32 m-tiles re-stage the same input otherwise
-    if (!no_m128 && !pinned && (resblock_ok || upsample_ok) && rows32 % 4 == 0 && c.rows == rows32 * 32 &&
-        (long long)((n_max + 127) / 128) * (rows32 / 4) * B >= m128_min_tiles()) {
+    const bool upsample_ok = epi == EPI_UPSAMPLE && !o.env.m128_ups_off && c.K >= 1 && c.K <= 3;  // 32 m-tiles re-stage the same input otherwise
+    if (!o.env.m128_off && !pinned && (resblock_ok || upsample_ok) && rows32 % 4 == 0 && c.rows == rows32 * 32 &&
+        (long long)((n_max + 127) / 128) * (rows32 / 4) * B >= o.env.m128_min_tiles) {
       shape = TILE_M128;
       MB = 1;
       ytiles = rows32 / 4;
@@ -312,7 +294,7 @@ static int run_plan(mi355tts_ctx* ctx, Worker* w, const ConvPlan& p, hipStream_t
   const int MB = p.MB, shape = p.shape;
   const dim3 grid = p.grid;
   int rc = 0;
-  g_rb_conv_on = w->o_rb_conv;
+  const bool rb_conv = w->opt.rb_conv && !w->opt.env.rb_conv_off;
   g_kn = w->quiet ? nullptr : ctx->kn;
   if (p.bf16) {
     kn_add(KN_CONV_BF16);
@@ -357,27 +339,27 @@ static int run_plan(mi355tts_ctx* ctx, Worker* w, const ConvPlan& p, hipStream_t
   }
   if (p.epi == EPI_LINEAR) {
     switch (p.K) {
-      case 1: rc = launch_conv_k<1, EPI_LINEAR>(s, MB, shape, grid, a); break;
-      case 3: rc = launch_conv_k<3, EPI_LINEAR>(s, MB, shape, grid, a); break;
-      case 5: rc = launch_conv_k<5, EPI_LINEAR>(s, MB, shape, grid, a); break;
-      case 7: rc = launch_conv_k<7, EPI_LINEAR>(s, MB, shape, grid, a); break;
-      case 11: rc = launch_conv_k<11, EPI_LINEAR>(s, MB, shape, grid, a); break;
+      case 1: rc = launch_conv_k<1, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
+      case 3: rc = launch_conv_k<3, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
+      case 5: rc = launch_conv_k<5, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
+      case 7: rc = launch_conv_k<7, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
+      case 11: rc = launch_conv_k<11, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
       default: rc = fail(MI355TTS_ERR_INVALID, "unsupported conv kernel size %d", p.K);
     }
   } else if (p.epi == EPI_GATE) {
     switch (p.K) {
-      case 3: rc = launch_conv_k<3, EPI_GATE>(s, MB, shape, grid, a); break;
-      case 5: rc = launch_conv_k<5, EPI_GATE>(s, MB, shape, grid, a); break;
+      case 3: rc = launch_conv_k<3, EPI_GATE>(s, MB, shape, grid, a, rb_conv); break;
+      case 5: rc = launch_conv_k<5, EPI_GATE>(s, MB, shape, grid, a, rb_conv); break;
       default: rc = fail(MI355TTS_ERR_INVALID, "unsupported WaveNet kernel size %d", p.K);
     }
   } else if (p.epi == EPI_COUPLING) {
-    if (p.K == 1) rc = launch_conv_k<1, EPI_COUPLING>(s, MB, shape, grid, a);
+    if (p.K == 1) rc = launch_conv_k<1, EPI_COUPLING>(s, MB, shape, grid, a, rb_conv);
     else rc = fail(MI355TTS_ERR_INVALID, "coupling conv must be 1x1");
   } else {
     switch (p.K) {
-      case 1: rc = launch_conv_k<1, EPI_UPSAMPLE>(s, MB, shape, grid, a); break;
-      case 2: rc = launch_conv_k<2, EPI_UPSAMPLE>(s, MB, shape, grid, a); break;
-      case 3: rc = launch_conv_k<3, EPI_UPSAMPLE>(s, MB, shape, grid, a); break;
+      case 1: rc = launch_conv_k<1, EPI_UPSAMPLE>(s, MB, shape, grid, a, rb_conv); break;
+      case 2: rc = launch_conv_k<2, EPI_UPSAMPLE>(s, MB, shape, grid, a, rb_conv); break;
+      case 3: rc = launch_conv_k<3, EPI_UPSAMPLE>(s, MB, shape, grid, a, rb_conv); break;
       default: rc = fail(MI355TTS_ERR_INVALID, "unsupported upsample taps %d", p.K);
     }
   }
@@ -387,7 +369,7 @@ static int run_plan(mi355tts_ctx* ctx, Worker* w, const ConvPlan& p, hipStream_t
 static int launch_conv(mi355tts_ctx* ctx, Worker* w, const DevConv& c, ConvArgs a, int epi, int B, int n_max, int cls,
                        hipStream_t stream = nullptr, int min_tiles = 1024, int host_len = -1, int precision = 0) {
   ConvPlan p;
-  CHECK(plan_conv(c, a, epi, B, n_max, cls, min_tiles, host_len, &p, precision));
+  CHECK(plan_conv(w->opt, c, a, epi, B, n_max, cls, min_tiles, host_len, &p, precision));
   return run_plan(ctx, w, p, stream);
 }
 
@@ -423,13 +405,6 @@ static bool rb_member_ok(const ConvArgs& a, int K) {
          a.rows % 128 == 0 && (K - 1) * a.dil + ((4 - a.pad % 4) % 4) <= halo;
 }
 
-// CUs of the device as the dispatch-order logic sees them (MI355TTS_GROUP_NCU overrides: tests reach the multi-round shapes at
-// emulator sizes with it)
-static int group_ncu(const mi355tts_ctx* ctx) {
-  if (const char* e = std::getenv("MI355TTS_GROUP_NCU")) return std::atoi(e);
-  return ctx->ncu;
-}
-
 // The same-geometry convs of the three MRF chains of a step (hifigan_forward.h plans them together).  At batch 1, members that
 // plan_conv left on the small tiles (a stage too short for its 128-row threshold: the 256-channel stage of 'high') move to the
 // 128-row tile when together they give every CU more than one workgroup: as ONE grouped launch of the continuous-stream tile
@@ -438,10 +413,9 @@ static int group_ncu(const mi355tts_ctx* ctx) {
 // plans, before the schedule is: the forked / one-by-one schedules then run the same tile arithmetic (same bits).  (f32 only: the
 // same move in the split-bf16 mode — 128 x 64 tiles instead of the 8-wave k-split tile — measured 56.8 us against 54.4 us,
 // profiles/r04_ab17.txt.)
-static void promote_group_plans(mi355tts_ctx* ctx, Worker* w, ConvPlan* const* plans, int n) {
+static void promote_group_plans(const CallOptions& o, ConvPlan* const* plans, int n) {
   // (option "rb_conv" = 0 / MI355TTS_NO_RB_CONV then run the chunked 128-row kernel in the plain order: same bits, slower)
-  static const bool no_promote = [] { const char* e = std::getenv("MI355TTS_NO_GROUP_PROMOTE"); return e && std::atoi(e) != 0; }();
-  if (n != 3 || no_promote || !w->o_group_promote) return;
+  if (n != 3 || o.env.group_promote_off || !o.group_promote) return;
   int total = 0, taps = 0;
   int tiles[3] = {0, 0, 0};  // by member in tap order 11, 7, 3
   for (int i = 0; i < 3; ++i) {
@@ -453,20 +427,19 @@ static void promote_group_plans(mi355tts_ctx* ctx, Worker* w, ConvPlan* const* p
     tiles[p.K == 11 ? 0 : p.K == 7 ? 1 : 2] = ((p.n_max + 63) / 64) * (p.a.rows / 128);
     total += (((p.n_max + 63) / 64) * (p.a.rows / 128) + 7) & ~7;
   }
-  const int ncu = group_ncu(ctx);
+  const int ncu = o.ncu;  // (tests reach the multi-round shapes at emulator sizes with MI355TTS_GROUP_NCU)
   if (taps != 7 || total <= ncu) return;
   if (total <= 4 * ncu) {
     // All resident at once: nothing is dealt dynamically, so the launch lasts as long as its busiest CU.  The big tile runs at
     // ~0.83 of peak against ~0.65-0.70 for the k-split tile it replaces (whose many small workgroups ARE dealt dynamically):
     // it wins while the snake keeps the busiest CU within ~1.3x of the mean (measured by utterance length, profiles/r04_ab18.txt; 1.09 at 624 frames of 'high': 121 us against 133; just above one
     // workgroup per CU — shorter utterances, narrower stages — the few second-round tiles double the busiest CUs' work).
-    const char* env = std::getenv("MI355TTS_PROMOTE_MAX_IMBALANCE");  // (read per step, like MI355TTS_GROUP_NCU: tests move it)
     // Threshold 1.35 (1.25 until round 6, chosen on lone launches, where the two tiles are even between 1.2 and 1.3): with other
     // calls in flight — when another call's workgroups fill what the deal leaves idle — the big tile wins through that band too:
     // the headline's utterances of 560-580 and ~680 frames (imbalance 1.21-1.30) promoted: 293.5 -> 297.0 utterances/s A B A B,
     // the lone call's latency unchanged (profiles/r06_promote_ab.txt).  A geometry rule, not a load rule: the tile changes the
     // summation order, so it must not depend on who else is running.
-    const double max_imbalance = env ? std::atof(env) : 1.35;
+    const double max_imbalance = o.env.promote_max_imbalance;
     ConvGroupArgs g;
     g.off[0] = 0;
     for (int m = 0; m < 3; ++m) g.off[m + 1] = g.off[m] + ((tiles[m] + 7) & ~7);
@@ -484,15 +457,14 @@ static void promote_group_plans(mi355tts_ctx* ctx, Worker* w, ConvPlan* const* p
 }
 
 static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n, hipStream_t s) {
-  static const bool off = [] { const char* e = std::getenv("MI355TTS_NO_GROUP"); return e && std::atoi(e) != 0; }();
-  if (off || n != 3) return 1;
+  const CallOptions& o = w->opt;
+  if (o.env.group_off || n != 3) return 1;
   // members ordered by tap count, longest-running first
   int ord[3] = {0, 1, 2};
   for (int i = 0; i < 3; ++i)
     for (int j = i + 1; j < 3; ++j)
       if (plans[ord[j]].K > plans[ord[i]].K) std::swap(ord[i], ord[j]);
-  static const bool rb_off = [] { const char* e = std::getenv("MI355TTS_NO_RB_CONV"); return e && std::atoi(e) != 0; }();
-  const int ncu = group_ncu(ctx);
+  const int ncu = o.ncu;
   const ConvPlan& p0 = plans[ord[0]];
   for (int i = 0; i < 3; ++i) {
     const ConvPlan& p = plans[ord[i]];
@@ -557,11 +529,11 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n,
   g_last_sub = p0.a.rows;
   // The 128-row tile with the continuous matrix stream (rb_conv.h; same bits as the chunked tile) where the launch is
   // what it was written for: plain ResBlock convs (bias, optional residual), taps 11 / 7 / 3, dilation within its halos.
-  if (p0.shape == TILE_M128 && k0 == 11 && !rb_off && w->o_rb_conv) {
+  if (p0.shape == TILE_M128 && k0 == 11 && !o.env.rb_conv_off && o.rb_conv) {
     bool rb_ok = true;
     for (int i = 0; i < 3; ++i) rb_ok = rb_ok && rb_member_ok(g.c[i], i == 0 ? 11 : i == 1 ? 7 : 3);
     if (rb_ok) {
-      static const bool no_snake = [] { const char* e = std::getenv("MI355TTS_NO_SNAKE"); return e && std::atoi(e) != 0; }();
+      const bool snake = o.group_snake && !o.env.snake_off;
       // 128-column tiles (NB = 4: half the weight-fragment bytes and staged halo per MFMA, three workgroups per CU) when the launch
       // still more than fills the chip with them.  Same chains per output element: same bits.
       // Measured A B A B (profiles/r06_nb4_ab.txt): the 128-channel stage's launch alone 240 -> 250 us (927 workgroups deal worse over
@@ -570,8 +542,7 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n,
       // only while ANOTHER call holds a worker of this context: a lone call keeps the 64-column tiles (its launch has the chip to
       // itself and is 4 % faster on them).  The choice depends on the load, the result does not (same bits), like the dispatch order.
       // MI355TTS_RB_NB4_MIN_TILES = threshold whatever the load (tests, A/B runs), 0 = never.
-      const char* nb4_env = std::getenv("MI355TTS_RB_NB4_MIN_TILES");  // (read per launch, like MI355TTS_GROUP_NCU: tests move it)
-      const int nb4_min = nb4_env ? std::atoi(nb4_env) : (ctx->active_calls.load(std::memory_order_relaxed) > 1 ? 3 * ncu : 0);
+      const int nb4_min = o.env.rb_nb4_min_tiles != KNOB_UNSET ? o.env.rb_nb4_min_tiles : (ctx->active_calls.load(std::memory_order_relaxed) > 1 ? 3 * ncu : 0);
       if (nb4_min > 0 && grid.z == 1) {
         int tiles4 = 0;
         for (int i = 0; i < 3; ++i) tiles4 += ((plans[ord[i]].n_max + 127) / 128) * g.gy[i];
@@ -584,13 +555,13 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n,
           }
           g.off[3] = o4;
           const dim3 grid4(o4, 1, 1);
-          if (!no_snake && w->o_snake) group_snake_order(g, ncu, 3 * ncu);
+          if (snake) group_snake_order(g, ncu, 3 * ncu);
           kn_add(KN_RB_GROUP_NB4);
           hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3, 4>), grid4, dim3(256), 0, s, g);
           return 0;
         }
       }
-      if (grid.z == 1 && !no_snake && w->o_snake) group_snake_order(g, ncu, 4 * ncu);  // four of these workgroups fit a CU (32 KB, <= 128 VGPRs)
+      if (grid.z == 1 && snake) group_snake_order(g, ncu, 4 * ncu);  // four of these workgroups fit a CU (32 KB, <= 128 VGPRs)
       kn_add(g.nseg ? KN_RB_GROUP_SNAKE : KN_RB_GROUP);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3>), grid, dim3(256), 0, s, g);
       return 0;
@@ -619,18 +590,16 @@ struct PairPlan {
   int bf16 = 0;     // 0 = f32 kernel (resblock_pair.h); 3 / 1 = split / plain bf16 kernel (resblock_pair_bf16.h)
   bool rb = false;  // f32: the 4-wave tile without a k-split (rb_pair.h) — launches with enough tiles (see plan_pair)
 };
-static void plan_pair(const DevConv& c1, const DevConv& c2, const float* x, float* y, long long bs, int ld, const int* len,
+static void plan_pair(const CallOptions& o, const DevConv& c1, const DevConv& c2, const float* x, float* y, long long bs, int ld, const int* len,
                       int len_mul, int dil, float alpha, int accum, int B, int Lmax, int host_len, PairPlan* out, int precision = 0) {
-  static const bool off = [] { const char* e = std::getenv("MI355TTS_NO_PAIR_FUSION"); return e && std::atoi(e) != 0; }();
   const int nb64 = 1;  // measured: 128-column tiles beat 256 at C = 64 (163 vs 197 us for the k = 11 pair)
   const int C = c1.Cout, K = c1.K;
   out->ok = false;
   const bool half = precision != MI355TTS_PRECISION_F32 && c1.w16 && c2.w16;
   if (half) {
-    static const bool no_fused = [] { const char* e = std::getenv("MI355TTS_NO_BF16_PAIR"); return e && std::atoi(e) != 0; }();
-    if (no_fused || c1.nslab16 != C / 16 || c2.nslab16 != C / 16 || c1.mtiles16 != C / 32 || c2.mtiles16 != C / 32) return;  // un-fused bf16 convs
+    if (o.env.bf16_pair_off || c1.nslab16 != C / 16 || c2.nslab16 != C / 16 || c1.mtiles16 != C / 32 || c2.mtiles16 != C / 32) return;  // un-fused bf16 convs
   }
-  if (off || (C != 32 && C != 64) || c1.Cin != C || c2.Cin != C || c2.Cout != C || c2.K != K || dil > PAIR_DMAX || dil < 1 ||
+  if (o.env.pair_fusion_off || (C != 32 && C != 64) || c1.Cin != C || c2.Cin != C || c2.Cout != C || c2.K != K || dil > PAIR_DMAX || dil < 1 ||
       (K != 3 && K != 7 && K != 11) || c1.noct != c2.noct || !c1.has_bias || !c2.has_bias || (ld % 4) || x == y || Lmax <= 0)
     return;
   PairArgs& a = out->a;
@@ -665,8 +634,7 @@ static void plan_pair(const DevConv& c1, const DevConv& c2, const float* x, floa
     // member: -5 ... -9 % per launch); with a few dozen tiles per member (the 64-channel stage of 'medium': 42 at batch 1,
     // ~150 over config 4's ragged batch) the 8-wave k-split tile finishes a tile twice as fast and wins (97 vs 132 us).  The
     // count is the k = 11 member's, so the three members of a grouped launch always agree.
-    const char* e = std::getenv("MI355TTS_RB_PAIR_MIN_TILES");  // (read per plan, like MI355TTS_M128_MIN_TILES: tests lower it)
-    const long long min_tiles = e ? std::atoll(e) : 512LL;
+    const long long min_tiles = o.env.rb_pair_min_tiles;
     const int t2_ref = 128 * out->NB - 10;
     out->rb = !half && (long long)((Lmax + t2_ref - 1) / t2_ref) * B >= min_tiles;
   }
@@ -679,7 +647,7 @@ static int run_pair(mi355tts_ctx* ctx, Worker* w, const PairPlan& p, hipStream_t
   const PairArgs& a = p.a;
   const dim3 grid = p.grid;
   g_kn = w->quiet ? nullptr : ctx->kn;
-  kn_add(p.bf16 ? KN_PAIR_BF16 : (w->o_rb_pair && p.rb) ? KN_RB_PAIR : KN_PAIR);
+  kn_add(p.bf16 ? KN_PAIR_BF16 : (w->opt.rb_pair && p.rb) ? KN_RB_PAIR : KN_PAIR);
   if (p.bf16) {
 #define PAIR16_LAUNCH(KK, TT)                                                                                                                  \
   if (p.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_kernel<KK, 1, P16_WN32, P16_NB32, TT>), grid, dim3(64 * P16_WN32), 0, s, a);     \
@@ -697,7 +665,7 @@ static int run_pair(mi355tts_ctx* ctx, Worker* w, const PairPlan& p, hipStream_t
 #undef PAIR16_LAUNCH
     return 0;
   }
-  if (w->o_rb_pair && p.rb) {  // the 4-wave tile without a k-split (rb_pair.h): same tiles and arguments
+  if (w->opt.rb_pair && p.rb) {  // the 4-wave tile without a k-split (rb_pair.h): same tiles and arguments
 #define RBP_LAUNCH(KK)                                                                                               \
   if (p.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_kernel<KK, 1>), grid, dim3(256), 0, s, a);               \
   else hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_kernel<KK, 2>), grid, dim3(256), 0, s, a)
@@ -720,8 +688,7 @@ static int run_pair(mi355tts_ctx* ctx, Worker* w, const PairPlan& p, hipStream_t
 }
 // The three chains' fused steps as ONE launch (k = 11, 7, 3 members).  0 = launched, 1 = not groupable.
 static int run_pair_group(mi355tts_ctx* ctx, Worker* w, const PairPlan* plans, int n, hipStream_t s) {
-  static const bool off = [] { const char* e = std::getenv("MI355TTS_NO_GROUP"); return e && std::atoi(e) != 0; }();
-  if (off || n != 3) return 1;
+  if (w->opt.env.group_off || n != 3) return 1;
   int ord[3] = {0, 1, 2};
   for (int i = 0; i < 3; ++i)
     for (int j = i + 1; j < 3; ++j)
@@ -749,7 +716,7 @@ static int run_pair_group(mi355tts_ctx* ctx, Worker* w, const PairPlan* plans, i
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
   g_last_sub = p0.C;
   g_kn = w->quiet ? nullptr : ctx->kn;
-  kn_add(p0.bf16 ? KN_PAIR_BF16_GROUP : (w->o_rb_pair && p0.rb) ? KN_RB_PAIR_GROUP : KN_PAIR_GROUP);
+  kn_add(p0.bf16 ? KN_PAIR_BF16_GROUP : (w->opt.rb_pair && p0.rb) ? KN_RB_PAIR_GROUP : KN_PAIR_GROUP);
   if (p0.bf16 == 3) {
     if (p0.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, 1, P16_WN32, P16_NB32, 3>), grid, dim3(64 * P16_WN32), 0, s, g);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, 2, P16_WN64, P16_NB64, 3>), grid, dim3(128 * P16_WN64), 0, s, g);
@@ -760,7 +727,7 @@ static int run_pair_group(mi355tts_ctx* ctx, Worker* w, const PairPlan* plans, i
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, 2, P16_WN64, P16_NB64, 1>), grid, dim3(128 * P16_WN64), 0, s, g);
     return 0;
   }
-  if (w->o_rb_pair && p0.rb) {
+  if (w->opt.rb_pair && p0.rb) {
     if (p0.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_group_kernel<11, 7, 3, 1>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_group_kernel<11, 7, 3, 2>), grid, dim3(256), 0, s, g);
     return 0;
@@ -797,11 +764,10 @@ static int run_mrf_small(mi355tts_ctx* ctx, Worker* w, const MrfStage& ms, const
   constexpr int T = 256;
   const dim3 grid(2 * ((Lmax + T - 1) / T), 1, B);  // two workgroups per tile
   ProfScope ps(ctx, w, KC_MRF_NARROW, 2.0 * ms.mac_per_col * (double)Lmax * B, s);
-  static const bool mrf8_off = [] { const char* e = std::getenv("MI355TTS_NO_MRF8"); return e && std::atoi(e) != 0; }();
   if (ms.C == 16) {
     kn_hit(ctx, KN_MRF_SMALL);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(mrf_small_kernel<16, T, 4, 3, 7, 11>), grid, dim3(256), 0, s, a);
-  } else if (!mrf8_off) {
+  } else if (!w->opt.env.mrf8_off) {
     // 8 channels: the 4x4x1 16-block MFMA (no padding rows), its own fragment packing; two waves per tile
     a.w = arena + ms.w8_off;
     a.tab = reinterpret_cast<const int*>(arena + ms.t8_off);
@@ -827,14 +793,13 @@ static void gate16_launch(bool wide, dim3 grid, hipStream_t s, const Gate16Args&
 // ---- the WaveNet gate conv on 16-row tiles (gate16.h).  Returns 1 when this conv / launch is not one the kernel takes
 // (the caller then launches the 32-row tile), 0 when launched, < 0 on error.  `a` is the ConvArgs of the same launch.
 static int run_gate16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const ConvArgs& a, int B, int n_max, int cls, hipStream_t s) {
-  static const bool off = [] { const char* e = std::getenv("MI355TTS_NO_GATE16"); return e && std::atoi(e) != 0; }();
-  // more 32-row tiles than this and the launch fills the chip either way (measured: profiles/NOTES.md)
-  static const long long max_tiles = [] { const char* e = std::getenv("MI355TTS_GATE16_MAX_TILES"); return e ? std::atoll(e) : 1LL << 40; }();
-  if (off || !w->o_gate16 || !c.g16_J || n_max <= 0) return 1;
+  const CallOptions& o = w->opt;
+  if (o.env.gate16_off || !o.gate16 || !c.g16_J || n_max <= 0) return 1;
   const int PA = (a.pad + 3) & ~3;
   if ((PA - a.pad) + 31 + (c.K - 1) * a.dil >= GATE16_XW || a.x_ld % 4 || a.in_mul != a.out_mul || a.in_len != a.out_len) return 1;
   const int gx = (n_max + 31) / 32, gy = (a.half + 7) / 8;
-  if ((long long)gx * ((a.half + 15) / 16) * B > max_tiles) return 1;
+  // more 32-row tiles than this and the launch fills the chip either way (measured: profiles/NOTES.md)
+  if ((long long)gx * ((a.half + 15) / 16) * B > o.env.gate16_max_tiles) return 1;
   Gate16Args g;
   std::memset(&g, 0, sizeof(g));
   g.x = a.x; g.x_bs = a.x_bs; g.x_ld = a.x_ld;
@@ -844,7 +809,7 @@ static int run_gate16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const Conv
   g.cond = a.cond; g.cond_bs = a.cond_bs;
   ProfScope ps(ctx, w, cls, 2.0 * (double)c.Cout * c.Cin * c.K * (double)n_max * B, s);
   // wide passes (padded batches, coalesced passes): two row tiles per workgroup from one staged tile — same bits (gate16.h)
-  const long long wide_min = w->o_gate16_wide;
+  const long long wide_min = o.gate16_wide;
   const bool wide = wide_min > 0 && c.g16_J == 6 && (gy % 2) == 0 && (long long)gx * gy * B >= wide_min;  // (the released voices' width)
   const dim3 grid(gx, wide ? gy / 2 : gy, B);
 #define GATE16_LAUNCH(KK, JJ) gate16_launch<KK, JJ>(wide, grid, s, g)
@@ -883,11 +848,8 @@ struct Lin16Ln {
 };
 static int run_lin16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const ConvArgs& a, const float* arena, int B, int n_max, int cls,
                      int host_len, bool solo_tiles = false, const Lin16Ln* ln = nullptr) {
-  static const bool off = [] { const char* e = std::getenv("MI355TTS_NO_LIN16"); return e && std::atoi(e) != 0; }();
-  // more tiles than this and the chunked 32-row tile fills the chip (longer rows, bigger batches)
-  static const long long max_tiles = [] { const char* e = std::getenv("MI355TTS_LIN16_MAX_TILES"); return e ? std::atoll(e) : 1LL << 40; }();
-  static const bool no_k1 = [] { const char* e = std::getenv("MI355TTS_LIN16_NO_K1"); return e && std::atoi(e) != 0; }();
-  if (off || !w->o_glow_fuse || !c.l16_J || n_max <= 0 || (c.K == 1 && no_k1)) return 1;
+  const CallOptions& o = w->opt;
+  if (o.env.lin16_off || !o.glow_fuse || !c.l16_J || n_max <= 0 || (c.K == 1 && o.env.lin16_no_k1)) return 1;
   const int PA = (a.pad + 3) & ~3;
   if ((PA - a.pad) + (c.K - 1) * a.dil > MI355TTS_G16_HALO || a.x_ld % 4 || a.in_mul != a.out_mul || a.in_len != a.out_len) return 1;
   if (a.x2 || a.alpha != 1.0f || a.accum || a.in_slope != 1.0f || (a.out_act != ACT_NONE && a.out_act != ACT_RELU)) return 1;
@@ -896,15 +858,16 @@ static int run_lin16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const ConvA
   const int nblk = c.l16_J >= 16 ? 1 : 2;
   const int TC = 16 * nblk;
   const int gx = (n_max + TC - 1) / TC, gy = (c.rows + 15) / 16;
-  if ((long long)gx * gy * B > max_tiles) return 1;
+  // more tiles than this and the chunked 32-row tile fills the chip (longer rows, bigger batches)
+  if ((long long)gx * gy * B > o.env.lin16_max_tiles) return 1;
   // 1 x 1 convs: not in big padded batches — in config 4's batch of 8 the 840 16-row tiles of a res_skip conv
   // measured 3 % faster alone and 1.2 % slower with 8 calls in flight than the 64-row tile (profiles/NOTES.md)
   // (explicit batches only: a batch-1 call always takes this form, and so does a coalesced pass, whose rows must equal
   // their batch-1 results whatever their lengths)
   // Round 5: such passes take FOUR row tiles per workgroup from one staged tile (lin16_kernel<..., RTW = 4>: same bits as the
   // 16-row launch, a quarter of the staging) — option "gate16_wide" (the pass size from which; 0 = round 4's rule)
-  const bool wide = c.K == 1 && c.l16_J == 6 && !ln && nblk == 2 && (gy % 4) == 0 && w->o_gate16_wide > 0 &&
-                    (long long)gx * gy * B >= w->o_gate16_wide;
+  const bool wide = c.K == 1 && c.l16_J == 6 && !ln && nblk == 2 && (gy % 4) == 0 && o.gate16_wide > 0 &&
+                    (long long)gx * gy * B >= o.gate16_wide;
   if (!wide && c.K == 1 && B > 1 && !solo_tiles && (long long)gx * gy * B > 512) return 1;
   Lin16Args g;
   std::memset(&g, 0, sizeof(g));

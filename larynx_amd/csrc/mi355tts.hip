@@ -14,6 +14,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -46,6 +47,7 @@
 
 using namespace mi355tts;
 #include "host_models.h"
+#include "host_options.h"
 #include "host_context.h"
 #include "host_launch.h"
 #include "hifigan_f16.h"
@@ -60,6 +62,7 @@ extern "C" int mi355tts_create(int device, mi355tts_ctx** out) {
   HIPCHECK(hipGetDeviceCount(&n));
   if (device < 0 || device >= n) return fail(MI355TTS_ERR_INVALID, "device %d out of range (%d visible)", device, n);
   HIPCHECK(hipSetDevice(device));
+  init_process_knobs();
   mi355tts_ctx* c = new mi355tts_ctx();
   c->device = device;
   {
@@ -917,9 +920,9 @@ static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const int64
   CHECK(glow_precheck(gm, g, &Pmax));
   CHECK(hifigan_precheck(ctx, hm, vocoder, nullptr, B, gm->hp.mel_channels, -1, v));  // incl. the one-time denoiser bias
   HIPCHECK(hipSetDevice(ctx->device));
-  static const bool no_coalesce = [] { const char* e = std::getenv("MI355TTS_NO_CALL_COALESCE"); return e && std::atoi(e) != 0; }();
-  const int lanes = no_coalesce ? 0 : ctx->call_coalesce.load();
-  if (lanes > 0 && B == 1 && !noise && !speaker_ids && id_lens[0] <= ATTM_MAXP && ctx->voc_out.load() && !ctx->serial_branches.load()) {
+  // (decided before a worker, and with it a CallOptions, exists: the one place that reads these options off the context)
+  const int lanes = g_env.call_coalesce_off ? 0 : ctx->opts.call_coalesce.load();
+  if (lanes > 0 && B == 1 && !noise && !speaker_ids && id_lens[0] <= ATTM_MAXP && ctx->opts.voc_out.load() && !ctx->opts.serial_branches.load()) {
     // a batch-1 call: it rides a fused padded call with whichever other batch-1 calls are waiting right now (host_join.h)
     CallReq req;
     req.gm = gm;
@@ -1019,8 +1022,7 @@ static bool streams_share_queue(hipStream_t a, hipStream_t b, int* flags) {
 }
 // groups the workers by hardware queue (Worker::qgroup) and sizes ctx->qgroup_busy; every worker in `ws` is held by the caller
 static void probe_queue_groups(mi355tts_ctx* ctx, const std::vector<Worker*>& ws) {
-  static const bool off = [] { const char* e = std::getenv("MI355TTS_NO_QUEUE_PROBE"); return e && std::atoi(e) != 0; }();
-  if (off || ws.size() < 2) return;
+  if (g_env.queue_probe_off || ws.size() < 2) return;
   int* flags = nullptr;
   if (hipHostMalloc(&flags, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return;  // fine-grained: the device sees the host's store while its kernel runs
   // every main stream used once, back to back, before anything is measured: bound to its queue
@@ -1299,10 +1301,10 @@ extern "C" int mi355tts_bench_conv1d(mi355tts_ctx* ctx, int B, int Cin, int Cout
   a.in_const = L;
   a.out_const = L;
   a.in_slope = 0.1f;
-  if (const char* ab = std::getenv("MI355TTS_BENCH_ABLATE")) a.ablate = std::atoi(ab);
+  a.ablate = w->opt.env.bench_ablate;
   const bool prof = ctx->profiling.load();
   ctx->profiling = false;
-  g_pin_tile = tile_shape;
+  w->opt.pin_tile = tile_shape;  // this call's own options: the next check-out of the worker starts from the context's again
   int rc = 0;
   for (int i = 0; i < 3 && !rc; ++i) rc = launch_conv(ctx, w, c, a, EPI_LINEAR, B, L, KC_RESBLOCK);
   hipEvent_t e0, e1;
@@ -1319,7 +1321,6 @@ extern "C" int mi355tts_bench_conv1d(mi355tts_ctx* ctx, int B, int Cin, int Cout
     hipEventDestroy(e0);
     hipEventDestroy(e1);
   }
-  g_pin_tile = -1;
   ctx->profiling = prof;
   return rc;
 }
@@ -1340,10 +1341,11 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
     }
   } skipped{ctx->selfcheck_state};
   {
-    const char* e = std::getenv("MI355TTS_NO_SELFCHECK");
+    EnvKnobs now;  // looked at when the check would run, not only when the first context was created
+    read_env_knobs(PROCESS, &now);
     hipDeviceProp_t prop;
     const bool emu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && std::strncmp(prop.gcnArchName, "hipemu", 6) == 0;
-    if ((e && std::atoi(e) != 0) || emu) return 0;  // (the CPU emulator build of the tests: nothing to measure)
+    if (now.selfcheck_off || emu) return 0;  // (the CPU emulator build of the tests: nothing to measure)
   }
   HIPCHECK(hipSetDevice(ctx->device));
   const int C = 256, L = 78 * 64;
@@ -1383,16 +1385,16 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
     ConvArgs a = base_args(dx, (long long)C * L, L, nullptr, 1, (float*)(base + o_y[m]), (long long)C * L, L, nullptr, 1, 1, (Ks[m] - 1) / 2);
     a.in_const = a.out_const = L;
     a.in_slope = 0.1f;
-    CHECK(plan_conv(cv[m], a, EPI_LINEAR, 1, L, KC_RESBLOCK, 1024, L, &plans[m], 0));
+    CHECK(plan_conv(w->opt, cv[m], a, EPI_LINEAR, 1, L, KC_RESBLOCK, 1024, L, &plans[m], 0));
   }
   struct Quiet {  // the check's launches are not a caller's: neither profiled nor counted (worker-local)
     Worker* w;
     ~Quiet() { w->quiet = false; }
   } quiet{w};
   w->quiet = true;
-  w->o_group_promote = true;
-  w->o_rb_conv = true;
-  promote_group_plans(ctx, w, pp, 3);
+  w->opt.group_promote = true;
+  w->opt.rb_conv = true;
+  promote_group_plans(w->opt, pp, 3);
   int rc = 0;
   float us[2] = {0.f, 0.f};
   if (plans[0].shape != TILE_M128) {
@@ -1402,12 +1404,12 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MI355TTS_ERR_HIP, "hipEventCreate");
     for (int warm = 0; warm < 2 && !rc; ++warm)
       for (int order = 0; order < 2 && !rc; ++order) {
-        w->o_snake = order == 1;
+        w->opt.group_snake = order == 1;
         if (run_group(ctx, w, plans, 3, s) != 0) rc = 1;
       }
     for (int rep = 0; rep < 4 && !rc; ++rep)
       for (int order = 0; order < 2 && !rc; ++order) {
-        w->o_snake = order == 1;
+        w->opt.group_snake = order == 1;
         hipEventRecord(e0, s);
         for (int i = 0; i < 2 && !rc; ++i)
           if (run_group(ctx, w, plans, 3, s) != 0) rc = 1;
@@ -1425,7 +1427,7 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
   if (us[1] > 1.02f * us[0]) {
     // only the ORDER option: it cannot change a result.  The promotion rule picks the tile (= the summation order) and stays
     // a function of the CU count and the geometry, whatever a timing on a busy device says
-    ctx->group_snake = false;
+    ctx->opts.group_snake = false;
     ctx->selfcheck_state = 2;
   } else {
     ctx->selfcheck_state = 1;
@@ -1454,68 +1456,7 @@ extern "C" int mi355tts_set_profiling(mi355tts_ctx* ctx, int enabled) {
 extern "C" int mi355tts_set_option(mi355tts_ctx* ctx, const char* name, int value) {
   if (!ctx || !name) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  if (std::strcmp(name, "adaptive_schedule") == 0) {
-    ctx->adaptive_schedule = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "mrf_small") == 0) {
-    ctx->mrf_small = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "gate16") == 0) {
-    ctx->gate16 = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "call_coalesce") == 0) {
-    ctx->call_coalesce = value < 0 ? 0 : value;
-    return 0;
-  }
-  if (std::strcmp(name, "call_coalesce_window_us") == 0) {
-    ctx->call_coalesce_window_us = value < 0 ? 0 : value;
-    return 0;
-  }
-  if (std::strcmp(name, "glow_fuse") == 0) {
-    ctx->glow_fuse = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "mrf_group") == 0) {
-    ctx->mrf_group = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "rb_conv") == 0) {
-    ctx->rb_conv = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "group_snake") == 0) {
-    ctx->group_snake = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "group_promote") == 0) {
-    ctx->group_promote = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "rb_pair") == 0) {
-    ctx->rb_pair = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "gate16_wide") == 0) {
-    ctx->gate16_wide = value < 0 ? 0 : value;
-    return 0;
-  }
-  if (std::strcmp(name, "voc_out") == 0) {
-    ctx->voc_out = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "serial_branches") == 0) {
-    ctx->serial_branches = value != 0;
-    return 0;
-  }
-  if (std::strcmp(name, "sync_mode") == 0) {  // process-wide: how a caller thread waits for its stream (host_context.h, mi355_sync)
-    if (value < 0 || value > 3) return fail(MI355TTS_ERR_INVALID, "sync_mode %d outside [0, 3]", value);
-    g_sync_mode.store(value, std::memory_order_relaxed);
-    return 0;
-  }
-  return fail(MI355TTS_ERR_INVALID, "unknown option '%s'", name);
+  return set_context_option(ctx->opts, name, value);
 }
 extern "C" int mi355tts_call_coalesce_default(void) { return MI355TTS_CALL_COALESCE_DEFAULT; }
 extern "C" int mi355tts_coalesce_stats(mi355tts_ctx* ctx, int64_t* passes, int64_t* rows) {

@@ -110,7 +110,7 @@ def main():
     ap.add_argument("--threads", type=int, default=4)
     ap.add_argument("--no-reserve", action="store_true", help="leave the workspaces grow-only (no mi355tts_reserve up front)")
     ap.add_argument("--set-option", action="append", default=[], metavar="NAME=VALUE",
-                    help="mi355tts_set_option before anything runs, e.g. glow_coalesce=1 (the fused calls then share GlowTTS passes)")
+                    help="mi355tts_set_option before anything runs, e.g. call_coalesce=2 (concurrent batch-1 calls then ride fused padded calls, two in flight)")
     args = ap.parse_args()
     eng = Engine(0)
     for kv in args.set_option:
