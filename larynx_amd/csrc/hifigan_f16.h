@@ -111,16 +111,22 @@ static void fix_h(HConvW& c, const uint16_t* arenaH, const float* arena) {
 //   SLIM : 1 x 4 waves of 32 x 64              —  32 rows x 256 columns, Cin <= 32: the one chunk
 enum HTile { HT_WIDE = 0, HT_MID, HT_SLIM };
 static int h_tile_for(int rows, int Cin) { return (rows <= 32 && Cin <= 32) ? HT_SLIM : (rows < 128 && Cin <= 64) ? HT_MID : HT_WIDE; }
-static void h_tile_dims(int t, int& trows, int& tcols) {
-  trows = t == HT_WIDE ? 128 : t == HT_MID ? 64 : 32;
-  tcols = t == HT_WIDE ? 128 : 256;
-}
-// template arguments MB, NB, WM, WN (then HALO ..., the chunk size) and the ring depth of each shape
-#define H_TILE_PARAMS_WIDE 2, 2, 2, 2
-#define H_TILE_PARAMS_MID 2, 2, 1, 4
-#define H_TILE_PARAMS_SLIM 1, 2, 1, 4
+// template arguments MB, NB, WM, WN of each shape (a tile is 32 MB WM rows x 32 NB WN columns), the depth of its chunk ring and
+// the waves per SIMD the fused pair kernel asks for
+struct HTileCfg {
+  int MB, NB, WM, WN, RING, PAIR_MINW;
+};
+constexpr HTileCfg H_TILES[3] = {{2, 2, 2, 2, 3, 3}, {2, 2, 1, 4, 2, 3}, {1, 2, 1, 4, 1, 4}};
 constexpr int H_CH = 32;
-constexpr int H_RING_WIDE = 3, H_RING_MID = 2, H_RING_SLIM = 1;
+static void h_tile_dims(int t, int& trows, int& tcols) {
+  trows = 32 * H_TILES[t].MB * H_TILES[t].WM;
+  tcols = 32 * H_TILES[t].NB * H_TILES[t].WN;
+}
+// f(tile configuration as a compile-time index); < 0 with the error set for a tile that does not exist
+template <class F>
+static int h_tile_dispatch(int tile, F&& f) {
+  return switch_const<HT_WIDE, HT_MID, HT_SLIM>(tile, f) ? 0 : fail(MI355TTS_ERR_INVALID, "internal: fp16 tile %d", tile);
+}
 
 struct HPlan {
   HConvArgs a;
@@ -133,67 +139,55 @@ struct HPlan {
 
 template <int K, int EPI, bool MRF>
 static int launch_f16_k(const HPlan& p, hipStream_t s) {
-  constexpr int HALO = ConvHalo<K>::v;
-  switch (p.tile) {
-    case HT_WIDE: hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_kernel<K, H_TILE_PARAMS_WIDE, HALO, H_CH, EPI, MRF, H_RING_WIDE>), p.grid, dim3(256), 0, s, p.a); return 0;
-    case HT_MID: hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_kernel<K, H_TILE_PARAMS_MID, HALO, H_CH, EPI, MRF, H_RING_MID>), p.grid, dim3(256), 0, s, p.a); return 0;
-    case HT_SLIM: hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_kernel<K, H_TILE_PARAMS_SLIM, HALO, H_CH, EPI, MRF, H_RING_SLIM>), p.grid, dim3(256), 0, s, p.a); return 0;
-  }
-  return fail(MI355TTS_ERR_INVALID, "internal: fp16 tile %d", p.tile);
+  return h_tile_dispatch(p.tile, [&](auto tile) {
+    constexpr HTileCfg t = H_TILES[decltype(tile)::value];
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_kernel<K, t.MB, t.NB, t.WM, t.WN, ConvHalo<K>::v, H_CH, EPI, MRF, t.RING>), p.grid, dim3(256), 0, s, p.a);
+  });
 }
 static int run_plan_f16(mi355tts_ctx* ctx, Worker* w, const HPlan& p, int cls, hipStream_t s) {
   ProfScope ps(ctx, w, cls, p.flop, s);
   kn_hit(ctx, KN_CONV_F16);
   g_last_sub = p.a.rows;
   if (p.epi == EPI_UPSAMPLE) return p.mrf ? launch_f16_k<2, EPI_UPSAMPLE, true>(p, s) : launch_f16_k<2, EPI_UPSAMPLE, false>(p, s);
-  switch (p.K) {
-    case 3: return launch_f16_k<3, EPI_LINEAR, false>(p, s);
-    case 5: return launch_f16_k<5, EPI_LINEAR, false>(p, s);
-    case 7: return launch_f16_k<7, EPI_LINEAR, false>(p, s);
-    case 11: return launch_f16_k<11, EPI_LINEAR, false>(p, s);
-  }
-  return fail(MI355TTS_ERR_INVALID, "internal: fp16 conv with %d taps", p.K);
+  int rc = 0;
+  if (!switch_const<3, 5, 7, 11>(p.K, [&](auto k) { rc = launch_f16_k<decltype(k)::value, EPI_LINEAR, false>(p, s); }))
+    rc = fail(MI355TTS_ERR_INVALID, "internal: fp16 conv with %d taps", p.K);
+  return rc;
 }
 
-template <int K0, int K1, int K2>
-static int launch_f16_group_k(int tile, dim3 grid, const HConvGroupArgs& g, hipStream_t s) {
-  constexpr int H0 = ConvHalo<K0>::v, H1 = ConvHalo<K1>::v, H2 = ConvHalo<K2>::v;
-  switch (tile) {
-    case HT_WIDE: hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_group_kernel<K0, K1, K2, H_TILE_PARAMS_WIDE, H0, H1, H2, H_CH, H_RING_WIDE>), grid, dim3(256), 0, s, g); return 0;
-    case HT_MID: hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_group_kernel<K0, K1, K2, H_TILE_PARAMS_MID, H0, H1, H2, H_CH, H_RING_MID>), grid, dim3(256), 0, s, g); return 0;
-    case HT_SLIM: hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_group_kernel<K0, K1, K2, H_TILE_PARAMS_SLIM, H0, H1, H2, H_CH, H_RING_SLIM>), grid, dim3(256), 0, s, g); return 0;
-  }
-  return fail(MI355TTS_ERR_INVALID, "internal: fp16 tile %d", tile);
-}
 // The same-geometry convs of a step's three chains in ONE launch (members longest first).  Returns 0 = launched, 1 = this tap
 // set has no grouped kernel (the caller launches the members one by one), < 0 = error.
 static int run_group_f16(mi355tts_ctx* ctx, Worker* w, const HPlan* p, int n, int B, hipStream_t s) {
   if (n != 3) return 1;
-  int ord[3] = {0, 1, 2};
-  std::sort(ord, ord + 3, [&](int x, int y) { return p[x].K > p[y].K; });
-  const int K0 = p[ord[0]].K, K1 = p[ord[1]].K, K2 = p[ord[2]].K;
-  const bool k1173 = K0 == 11 && K1 == 7 && K2 == 3, k753 = K0 == 7 && K1 == 5 && K2 == 3;
-  if (!k1173 && !k753) return 1;
+  const int K[3] = {p[0].K, p[1].K, p[2].K}, tiles[3] = {p[0].gx * p[0].gy, p[1].gx * p[1].gy, p[2].gx * p[2].gy};
+  const GroupLayout lay = group_layout(K, tiles);
+  if (!lay.k1173 && !lay.k753) return 1;
   if (p[0].tile != p[1].tile || p[0].tile != p[2].tile) return 1;
   HConvGroupArgs g;
   std::memset(&g, 0, sizeof(g));
-  int off = 0;
   double flop = 0;
   for (int m = 0; m < 3; ++m) {
-    const HPlan& q = p[ord[m]];
+    const HPlan& q = p[lay.ord[m]];
     g.c[m] = q.a;
     g.gx[m] = q.gx;
     g.gy[m] = q.gy;
-    g.off[m] = off;
-    off += (q.gx * q.gy + 7) & ~7;
     flop += q.flop;
   }
-  g.off[3] = off;
+  std::copy(lay.off, lay.off + 4, g.off);
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
   kn_hit(ctx, KN_CONV_F16_GROUP);
   g_last_sub = p[0].a.rows;
-  const dim3 grid(off, 1, B);
-  return k1173 ? launch_f16_group_k<11, 7, 3>(p[0].tile, grid, g, s) : launch_f16_group_k<7, 5, 3>(p[0].tile, grid, g, s);
+  const dim3 grid(g.off[3], 1, B);
+  int rc = 0;
+  switch_taps(lay, [&](auto k0, auto k1, auto k2) {
+    rc = h_tile_dispatch(p[0].tile, [&](auto tile) {
+      constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value, K2 = decltype(k2)::value;
+      constexpr HTileCfg t = H_TILES[decltype(tile)::value];
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f16_group_kernel<K0, K1, K2, t.MB, t.NB, t.WM, t.WN, ConvHalo<K0>::v, ConvHalo<K1>::v, ConvHalo<K2>::v, H_CH, t.RING>),
+                         grid, dim3(256), 0, s, g);
+    });
+  });
+  return rc;
 }
 
 // ---- fused ResBlock1 steps (pair_f16.h): conv1 + conv2 of a dilation step of the three chains in ONE launch.  A workgroup owns
@@ -204,45 +198,40 @@ struct HPairPlan {
   double flop = 0;
 };
 static int h_pair_tile(int C) { return C <= 32 ? HT_SLIM : C <= 64 ? HT_MID : C <= 128 ? HT_WIDE : -1; }
-template <int K0, int K1, int K2>
-static int launch_pair_group_k(int tile, dim3 grid, const HPairGroupArgs& g, hipStream_t s) {
-  constexpr int H0 = ConvHalo<K0>::v, H1 = ConvHalo<K1>::v, H2 = ConvHalo<K2>::v;
-  switch (tile) {
-    case HT_WIDE: hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_f16_group_kernel<K0, K1, K2, H_TILE_PARAMS_WIDE, H0, H1, H2, H_CH, H_RING_WIDE, 3>), grid, dim3(256), 0, s, g); return 0;
-    case HT_MID: hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_f16_group_kernel<K0, K1, K2, H_TILE_PARAMS_MID, H0, H1, H2, H_CH, H_RING_MID, 3>), grid, dim3(256), 0, s, g); return 0;
-    case HT_SLIM: hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_f16_group_kernel<K0, K1, K2, H_TILE_PARAMS_SLIM, H0, H1, H2, H_CH, H_RING_SLIM, 4>), grid, dim3(256), 0, s, g); return 0;
-  }
-  return fail(MI355TTS_ERR_INVALID, "internal: fp16 pair tile %d", tile);
-}
 // Returns 0 = launched, 1 = not covered (the caller runs conv1 and conv2 as two grouped launches), < 0 = error.
 static int run_pair_group_f16(mi355tts_ctx* ctx, Worker* w, const HPairPlan* p, int n, int C, int B, int Lmax, hipStream_t s) {
   if (n != 3) return 1;
   const int tile = h_pair_tile(C);
   if (tile < 0) return 1;
-  int ord[3] = {0, 1, 2};
-  std::sort(ord, ord + 3, [&](int x, int y) { return p[x].K > p[y].K; });
-  if (!(p[ord[0]].K == 11 && p[ord[1]].K == 7 && p[ord[2]].K == 3)) return 1;
   int tr, tc;
   h_tile_dims(tile, tr, tc);
+  int K[3], gx[3];
+  for (int j = 0; j < 3; ++j) {
+    const int to = tc - (p[j].K - 1);  // output columns of a tile
+    K[j] = p[j].K;
+    gx[j] = (Lmax + to - 1) / to;
+  }
+  const GroupLayout lay = group_layout(K, gx);
+  if (!lay.k1173) return 1;
   HPairGroupArgs g;
   std::memset(&g, 0, sizeof(g));
   g.n = 3;
-  int off = 0;
   double flop = 0;
   for (int m = 0; m < 3; ++m) {
-    const HPairPlan& q = p[ord[m]];
-    const int to = tc - (q.K - 1);
+    const HPairPlan& q = p[lay.ord[m]];
     g.p[m] = q.a;
-    g.gx[m] = (Lmax + to - 1) / to;
-    g.off[m] = off;
-    off += (g.gx[m] + 7) & ~7;
+    g.gx[m] = gx[lay.ord[m]];
     flop += q.flop;
   }
-  g.off[3] = off;
+  std::copy(lay.off, lay.off + 4, g.off);
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
   kn_hit(ctx, KN_PAIR_F16_GROUP);
   g_last_sub = C;
-  return launch_pair_group_k<11, 7, 3>(tile, dim3(off, 1, B), g, s);
+  return h_tile_dispatch(tile, [&](auto ti) {
+    constexpr HTileCfg t = H_TILES[decltype(ti)::value];
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_f16_group_kernel<11, 7, 3, t.MB, t.NB, t.WM, t.WN, ConvHalo<11>::v, ConvHalo<7>::v, ConvHalo<3>::v, H_CH, t.RING, t.PAIR_MINW>),
+                       dim3(g.off[3], 1, B), dim3(256), 0, s, g);
+  });
 }
 
 // lengths: one row with a host-known length takes it as a launch constant (no dependent load in every workgroup's prologue)

@@ -11,46 +11,6 @@ extern "C" int mi355tts_hifigan_hop(mi355tts_ctx* ctx, int vocoder) {
   return it->second->hop;
 }
 
-static int ensure_denoiser_bias(mi355tts_ctx* ctx, HifiModel* hm, int vocoder) {
-  std::lock_guard<std::mutex> lk(hm->bias_mu);
-  const int bi = hm->precision.load() == MI355TTS_PRECISION_F16 ? 1 : 0;
-  if (hm->bias_ready[bi]) return 0;
-  const int M = hm->hp.num_mels, hop = hm->hop;
-  const int zf = 88;  // the reference's all-zero mel has 88 frames (hifi_gan.py:187,198)
-  const long long N = (long long)zf * hop;
-  if (N <= DN_FFT) return fail(MI355TTS_ERR_INVALID, "vocoder hop %d too small for the 1024-point denoiser STFT", hop);
-  HIPCHECK(hipSetDevice(ctx->device));
-  std::vector<float> zeros((size_t)M * zf, 0.f);
-  int32_t fr = zf;
-  mi355tts_mel* zm = nullptr;
-  CHECK(mi355tts_mel_from_buffer(ctx, zeros.data(), &fr, 1, M, zf, nullptr, 0, &zm));
-  float* dwav = nullptr;
-  float* bias = nullptr;
-  int rc = 0;
-  if (hipMalloc(&dwav, sizeof(float) * (size_t)N) != hipSuccess || hipMalloc(&bias, sizeof(float) * (DN_FFT / 2 + 1)) != hipSuccess)
-    rc = fail(MI355TTS_ERR_NOMEM, "hipMalloc denoiser bias");
-  if (!rc) rc = mi355tts_hifigan_infer(ctx, vocoder, zm, 0.f, dwav, nullptr, N, MI355TTS_OUT_DEVICE);
-  if (!rc) {
-    Worker* w = nullptr;
-    rc = acquire_worker(ctx, &w);
-    if (!rc) {
-      WorkerGuard guard{ctx, w};
-      hipLaunchKernelGGL(stft_denoise_kernel, dim3(1, 1), dim3(256), 0, w->stream, dwav, (long long)N, zm->frames_dev, hop,
-                         (const float*)nullptr, 0.f, (float*)nullptr, 1, bias);
-      if (mi355_sync(w->stream) != hipSuccess) rc = fail(MI355TTS_ERR_HIP, "denoiser bias kernel failed");
-    }
-  }
-  mel_destroy(zm);
-  if (dwav) hipFree(dwav);
-  if (rc) {
-    if (bias) hipFree(bias);
-    return rc;
-  }
-  hm->bias_spec[bi] = bias;
-  hm->bias_ready[bi] = true;
-  return 0;
-}
-
 // One vocoder call's outputs: per row [pad_before zeros][frames[b]*hop samples][zeros up to wav_ld]
 // (the pads are the SSML pauses `_sentence_task` adds with np.pad, larynx/__init__.py:277-283).
 struct VocRow {  // one row's destinations when the rows of a call belong to different callers (host_join.h)
@@ -68,6 +28,9 @@ struct VocCall {
   int pad_before = 0, pad_after = 0;
   // optional, [B] (B <= VOC_MAX_ROWS): per-row destinations, strides and pauses; the five fields above are then unused
   const VocRow* rows = nullptr;
+  // The model's precision for this call: read ONCE, by the call's first hifigan_precheck (mi355tts_model_set_precision may run on
+  // another thread meanwhile); the bias pass, the generator and the denoiser's bias slot all follow this value.
+  int precision = -1;
 };
 
 // pins the model (see find_glow)
@@ -79,9 +42,11 @@ static int find_hifi(mi355tts_ctx* ctx, int vocoder, std::shared_ptr<HifiModel>*
   return 0;
 }
 
-// Checks that need no worker (and may run the one-time bias-spectrum pass on a worker of their own).
-static int hifigan_precheck(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, const int32_t* frames, int B, int M, int Fmax,
-                            const VocCall& c) {
+static int ensure_denoiser_bias(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, int precision);
+
+// Checks that need no worker (and may run the one-time bias-spectrum pass on a worker of their own).  Fixes the call's precision.
+static int hifigan_precheck(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, const int32_t* frames, int B, int M, int Fmax, VocCall& c) {
+  if (c.precision < 0) c.precision = hm->precision.load();
   if (M != hm->hp.num_mels) return fail(MI355TTS_ERR_INVALID, "mel has %d channels, vocoder expects %d", M, hm->hp.num_mels);
   if (c.rows) {  // per-row destinations: every row against its own frame count
     if (B > VOC_MAX_ROWS) return fail(MI355TTS_ERR_INVALID, "internal: %d rows with per-row outputs", B);
@@ -103,7 +68,7 @@ static int hifigan_precheck(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, const
       for (int b = 0; b < B; ++b)
         if ((long long)frames[b] * hm->hop <= DN_FFT)
           return fail(MI355TTS_ERR_INVALID, "utterance %d has %d frames: too short for the denoiser", b, frames[b]);
-    CHECK(ensure_denoiser_bias(ctx, hm, vocoder));
+    CHECK(ensure_denoiser_bias(ctx, hm, vocoder, c.precision));
   }
   return 0;
 }
@@ -142,71 +107,41 @@ static bool hifi_split_out(bool serial_branches, const mi355tts_hifigan_hparams&
   return !serial_branches && h.num_kernels >= 2 && h.num_kernels <= 3;
 }
 
-// The forward pass proper on worker `w` (already checked by hifigan_precheck); ends with the
-// stream synchronised and the outputs delivered.
-static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355tts_mel* mel, const VocCall& call) {
+// One dilation step of one MRF chain, planned: the fused pair if its geometry is covered, else conv1 (+ conv2)
+struct VocStep {
+  PairPlan pair;
+  ConvPlan c1, c2;
+  float* dst;
+};
+// The same step of the three chains as grouped launches on stream `s`: all fused pairs give one pair group, no pairs give one conv
+// group for conv1 and one for conv2.  Returns 0 = launched, 1 = not groupable (the caller runs the members one by one), < 0 = error.
+static int run_step_grouped(mi355tts_ctx* ctx, Worker* w, const VocStep (&sp)[3], hipStream_t s) {
+  const int npair = sp[0].pair.ok + sp[1].pair.ok + sp[2].pair.ok;
+  if (npair == 3) {
+    const PairPlan* pairs[3] = {&sp[0].pair, &sp[1].pair, &sp[2].pair};
+    return run_pair_group(ctx, w, pairs, 3, s);
+  }
+  if (npair != 0) return 1;
+  const ConvPlan* c1[3] = {&sp[0].c1, &sp[1].c1, &sp[2].c1};
+  const ConvPlan* c2[3] = {&sp[0].c2, &sp[1].c2, &sp[2].c2};
+  const int rc = run_group(ctx, w, c1, 3, s);
+  if (rc != 0 || sp[0].c2.empty) return rc;
+  const int rc2 = run_group(ctx, w, c2, 3, s);
+  if (rc2 == 1)
+    for (int j = 0; j < 3; ++j) CHECK(run_plan(ctx, w, sp[j].c2, s));
+  return rc2 < 0 ? rc2 : 0;
+}
+
+// ------------------------------------------------------------------ the f32 / split-bf16 generator, conv_pre .. conv_post + tanh
+// `buf`: the worker's plane buffers (hifi_layout).  Leaves the f32 waveform rows in `wav` ([B][Nld]) and, when asked (`voc_out`
+// tail only), the |max| of every POST_TW-sample tile in `peak` — what hifigan_body_f16 leaves.
+static int hifigan_body_f32(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355tts_mel* mel, int prec, float** buf, float* wav, size_t Nld,
+                            float* peak, long long peak_ld, bool voc_out, int voc_host_len, hipStream_t s) {
   const mi355tts_hifigan_hparams& h = hm->hp;
-  const int B = mel->B, F = mel->max_frames, hop = hm->hop;
-  const long long N = (long long)F * hop;
-  const float denoiser_strength = call.denoiser_strength;
-  float* const wav_f32 = call.wav_f32;
-  int16_t* const wav_i16 = call.wav_i16;
-  const int64_t wav_ld = call.wav_ld;
-  const bool denoise = denoiser_strength > 0.f && F > 0;
-  const bool out_dev = (call.flags & MI355TTS_OUT_DEVICE) != 0;
-  const int pad0 = call.pad_before;
-  hipStream_t s = w->stream;
-  const VocRow* const prow = call.rows;
-  if (prow && B > VOC_MAX_ROWS) return fail(MI355TTS_ERR_INVALID, "internal: %d rows with per-row outputs", B);
-  if (F == 0 && prow) {
-    for (int b = 0; b < B; ++b) {
-      const VocRow& r = prow[b];
-      if (out_dev) {
-        if (r.wav_f32) HIPCHECK(hipMemsetAsync(r.wav_f32, 0, sizeof(float) * (size_t)r.wav_ld, s));
-        if (r.wav_i16) HIPCHECK(hipMemsetAsync(r.wav_i16, 0, sizeof(int16_t) * (size_t)r.wav_ld, s));
-      } else {
-        if (r.wav_f32) std::memset(r.wav_f32, 0, sizeof(float) * (size_t)r.wav_ld);
-        if (r.wav_i16) std::memset(r.wav_i16, 0, sizeof(int16_t) * (size_t)r.wav_ld);
-      }
-    }
-    if (out_dev) HIPCHECK(mi355_sync(s));
-    return 0;
-  }
-  if (F == 0) {
-    if (out_dev) {
-      if (wav_f32) HIPCHECK(hipMemsetAsync(wav_f32, 0, sizeof(float) * (size_t)B * wav_ld, s));
-      if (wav_i16) HIPCHECK(hipMemsetAsync(wav_i16, 0, sizeof(int16_t) * (size_t)B * wav_ld, s));
-      HIPCHECK(mi355_sync(s));
-    } else {
-      if (wav_f32) std::memset(wav_f32, 0, sizeof(float) * (size_t)B * wav_ld);
-      if (wav_i16) std::memset(wav_i16, 0, sizeof(int16_t) * (size_t)B * wav_ld);
-    }
-    return 0;
-  }
-  // an error return after kernels were queued must not hand the worker (its arena!) to the
-  // next call while they still run — possibly on the side streams
-  struct DrainOnError {
-    Worker* w;
-    bool ok = false;
-    ~DrainOnError() {
-      if (ok) return;
-      mi355_sync(w->stream);
-      for (int i = 0; i < 2; ++i)
-        if (w->aux[i]) mi355_sync(w->aux[i]);
-    }
-  } drain{w};
-  const int C0 = h.upsample_initial_channel;
-  const int Fp = (F + 3) & ~3;
-  const int nk = h.num_kernels;
-  struct FlopScale {  // profiled FLOP of a ragged batch count the rows' real frames, not B x the longest row
-    Worker* w;
-    ~FlopScale() { w->flop_scale = 1.0; }
-  } fscale{w};
-  {
-    long long sum = 0;
-    for (int b = 0; b < B; ++b) sum += mel->frames[b];
-    w->flop_scale = (double)sum / ((double)B * F);
-  }
+  const CallOptions& opt = w->opt;
+  const int B = mel->B, F = mel->max_frames, Fp = (F + 3) & ~3;
+  const int C0 = h.upsample_initial_channel, nk = h.num_kernels;
+  const int* d_frames = mel->frames_dev;
   // The nk ResBlock chains of a stage are independent (MRF).  Each chain writes its own
   // output and the average is taken by the consumer's staging load (`split_out`).  A call
   // that has the GPU to itself also runs the chains on separate streams so their workgroups
@@ -217,11 +152,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   // same values in the same order: results do not depend on the load.
   // `serial_branches` (profiling / tests) additionally folds the average into the chains'
   // last epilogues (in-place accumulation, one output buffer).
-  const CallOptions& opt = w->opt;  // as read when the worker was checked out: a call never mixes schedules if an option changes while it runs
-  const int prec = hm->precision.load();
-  const bool f16 = prec == MI355TTS_PRECISION_F16;  // the native fp16 generator (hifigan_f16.h): its own schedule, chains always write their own planes
-  if (f16 && !hm->f16_ok) return fail(MI355TTS_ERR_INVALID, "internal: fp16 mode on a vocoder it does not cover");
-  const bool split_out = f16 || hifi_split_out(opt.serial_branches, h);
+  const bool split_out = hifi_split_out(opt.serial_branches, h);
   // grouped (default): the chains stay on ONE stream and the same-geometry launches of a step go out as
   // one grouped launch (conv_group_kernel / pair_group_kernel) — the chip is filled from one launch, with
   // no stream fork/join and independently of what else is in flight.  "mrf_group" = 0 restores the
@@ -245,39 +176,6 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   // depend on the load.  (With the final tile set 300, 700 and 1024 measured the same within
   // noise for the forked schedule.)  Tuning knob: MI355TTS_RB_TILES.
   const int rb_tiles = opt.env.rb_tiles > 0 ? opt.env.rb_tiles : 1024;
-  const int voc_host_len = B == 1 ? mel->frames[0] : -1;
-  int pads = call.pad_before + call.pad_after;
-  bool any_f32 = wav_f32 != nullptr, any_i16 = wav_i16 != nullptr;
-  if (prow) {
-    pads = 0;
-    any_f32 = any_i16 = false;
-    for (int b = 0; b < B; ++b) {
-      pads = std::max(pads, prow[b].pad_before + prow[b].pad_after);
-      any_f32 = any_f32 || prow[b].wav_f32;
-      any_i16 = any_i16 || prow[b].wav_i16;
-    }
-  }
-  const HifiLayout lay = hifi_layout(h, hop, B, F, denoise, split_out, pads);
-  const size_t Nld = lay.Nld;
-  const int nbuf = lay.nbuf, Tmax = lay.Tmax;
-  CHECK(reserve(w, lay.total));
-  char* base = w->arena;
-  float* buf[2 + 4 * 3];
-  for (int i = 0; i < nbuf; ++i) buf[i] = (float*)(base + lay.o_buf[i]);
-  float* wav = (float*)(base + lay.o_wav);
-  short* i16 = (short*)(base + lay.o_i16);
-  unsigned* peak = (unsigned*)(base + lay.o_peak);
-  const size_t o_wav2 = lay.o_wav2, o_fbuf = lay.o_fbuf;
-  const int* d_frames = mel->frames_dev;
-
-  const long long peak_ld = (long long)(Nld / POST_TW + 2);
-  bool peak_parts_ready = false;  // post_conv_kernel left the per-workgroup maxima of the FINAL waveform
-  bool vo = true;
-  if (f16) {
-    if ((size_t)((mel->M + 7) / 8) * F * 16 > lay.plane * sizeof(float)) return fail(MI355TTS_ERR_INVALID, "internal: mel octets exceed a plane buffer");
-    peak_parts_ready = any_i16 && !denoise;
-    CHECK(hifigan_body_f16(ctx, w, hm, mel, buf, wav, Nld, peak_parts_ready ? reinterpret_cast<float*>(peak) : nullptr, peak_ld, voc_host_len, s));
-  } else {
   // stage input: `cur[0]` alone, or the nk chain outputs cur[0..nk) still to be averaged
   float* cur[3] = {buf[0], nullptr, nullptr};
   int ncur = 1;
@@ -359,13 +257,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
       outs[j] = c.dst_last;
     }
     const int nd = h.num_dilations;
-    // One dilation step of chain j, planned: the fused pair if its geometry is covered, else conv1 (+ conv2)
-    struct Step {
-      PairPlan pair;
-      ConvPlan c1, c2;
-      float* dst;
-    };
-    auto plan_step = [&](int j, int d, Step& sp) -> int {
+    auto plan_step = [&](int j, int d, VocStep& sp) -> int {
       const HifiResConv& rc = hm->rb[i][j][d];
       const int kk = h.resblock_kernel_sizes[j];
       Chain& c = chn[j];
@@ -402,7 +294,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
       }
       return 0;
     };
-    auto run_step_alone = [&](int j, const Step& sp) -> int {
+    auto run_step_alone = [&](int j, const VocStep& sp) -> int {
       if (sp.pair.ok) return run_pair(ctx, w, sp.pair, chn[j].st);
       CHECK(run_plan(ctx, w, sp.c1, chn[j].st));
       return run_plan(ctx, w, sp.c2, chn[j].st);
@@ -411,7 +303,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
       // dilation-major: step d of every chain before step d + 1 of any — the chains have their own
       // buffers, and the same-geometry launches of a step can go out as ONE grouped launch
       for (int d = 0; d < nd; ++d) {
-        Step sp[3];
+        VocStep sp[3];
         for (int j = 0; j < nk; ++j) CHECK(plan_step(j, d, sp[j]));
         if (nk == 3 && !sp[0].pair.ok && !sp[1].pair.ok && !sp[2].pair.ok) {  // tile shape of the step: before the schedule is chosen
           ConvPlan* c1s[3] = {&sp[0].c1, &sp[1].c1, &sp[2].c1};
@@ -419,35 +311,9 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
           promote_group_plans(opt, c1s, nk);
           promote_group_plans(opt, c2s, nk);
         }
-        bool done = false;
-        if (grouped) {
-          bool all_pair = true, none_pair = true;
-          for (int j = 0; j < nk; ++j) {
-            all_pair = all_pair && sp[j].pair.ok;
-            none_pair = none_pair && !sp[j].pair.ok;
-          }
-          if (all_pair) {
-            PairPlan pp[3] = {sp[0].pair, sp[1].pair, sp[2].pair};
-            const int rc = run_pair_group(ctx, w, pp, nk, s);
-            if (rc < 0) return rc;
-            done = rc == 0;
-          } else if (none_pair) {
-            ConvPlan a[3] = {sp[0].c1, sp[1].c1, sp[2].c1};
-            const int rc = run_group(ctx, w, a, nk, s);
-            if (rc < 0) return rc;
-            if (rc == 0) {
-              if (!sp[0].c2.empty) {
-                ConvPlan b2[3] = {sp[0].c2, sp[1].c2, sp[2].c2};
-                const int rc2 = run_group(ctx, w, b2, nk, s);
-                if (rc2 < 0) return rc2;
-                if (rc2 != 0)
-                  for (int j = 0; j < nk; ++j) CHECK(run_plan(ctx, w, sp[j].c2, chn[j].st));
-              }
-              done = true;
-            }
-          }
-        }
-        if (!done)
+        const int rc = grouped ? run_step_grouped(ctx, w, sp, s) : 1;
+        if (rc < 0) return rc;
+        if (rc == 1)
           for (int j = 0; j < nk; ++j) CHECK(run_step_alone(j, sp[j]));
         for (int j = 0; j < nk; ++j) chn[j].rin = sp[j].dst;
       }
@@ -455,7 +321,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
       // chain-major (the chains share their scratch planes and accumulate into one output)
       for (int j = 0; j < nk; ++j)
         for (int d = 0; d < nd; ++d) {
-          Step sp;
+          VocStep sp;
           CHECK(plan_step(j, d, sp));
           CHECK(run_step_alone(j, sp));
           chn[j].rin = sp.dst;
@@ -482,11 +348,7 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
     Lin = Lout;
     ldin = ldo;
   }
-  // Option "voc_out" (default 1): conv_post + tanh + the rows' peaks in ONE dedicated launch and the delivery of the rows in one
-  // more (voc_out.h); 0 = the generic conv tile, zero_tail, absmax, to_int16 and a copy / fill per piece of every row.
-  vo = !opt.env.voc_out_off && opt.voc_out && hm->post_C == ch && hm->post.K == 7 && ldin % 4 == 0;
-  if (prow && !vo) return fail(MI355TTS_ERR_INVALID, "internal: per-row outputs need the voc_out tail");
-  if (vo) {  // x = tanh(conv_post(leaky_relu(x)))  — default slope 0.01 (models.py:198-200)
+  if (voc_out) {  // x = tanh(conv_post(leaky_relu(x)))  — default slope 0.01 (models.py:198-200)
     PostArgs a;
     std::memset(&a, 0, sizeof(a));
     a.x = cur[0];
@@ -505,10 +367,9 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
     a.C = ch;
     a.y = wav;
     a.y_bs = (long long)Nld;
-    if (any_i16 && !denoise) {
-      a.peak = reinterpret_cast<float*>(peak);
+    if (peak) {
+      a.peak = peak;
       a.peak_ld = peak_ld;
-      peak_parts_ready = true;
     }
     ProfScope ps(ctx, w, KC_VOC_IO, 2.0 * (double)ch * 7 * (double)Lin * B);
     kn_hit(ctx, KN_POST_CONV);
@@ -523,12 +384,122 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
     a.out_act = ACT_TANH;
     CHECK(launch_conv(ctx, w, hm->post, a, EPI_LINEAR, B, Lin, KC_VOC_IO, nullptr, 1024, voc_host_len));
   }
-  }  // !f16
+  return 0;
+}
+
+// The forward pass proper on worker `w` (already checked by hifigan_precheck); ends with the
+// stream synchronised and the outputs delivered.
+static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355tts_mel* mel, const VocCall& call) {
+  const mi355tts_hifigan_hparams& h = hm->hp;
+  const int B = mel->B, F = mel->max_frames, hop = hm->hop;
+  const long long N = (long long)F * hop;
+  const float denoiser_strength = call.denoiser_strength;
+  float* const wav_f32 = call.wav_f32;
+  int16_t* const wav_i16 = call.wav_i16;
+  const int64_t wav_ld = call.wav_ld;
+  const bool denoise = denoiser_strength > 0.f && F > 0;
+  const bool out_dev = (call.flags & MI355TTS_OUT_DEVICE) != 0;
+  const int pad0 = call.pad_before;
+  hipStream_t s = w->stream;
+  const VocRow* const prow = call.rows;
+  if (prow && B > VOC_MAX_ROWS) return fail(MI355TTS_ERR_INVALID, "internal: %d rows with per-row outputs", B);
+  if (F == 0 && prow) {
+    for (int b = 0; b < B; ++b) {
+      const VocRow& r = prow[b];
+      if (out_dev) {
+        if (r.wav_f32) HIPCHECK(hipMemsetAsync(r.wav_f32, 0, sizeof(float) * (size_t)r.wav_ld, s));
+        if (r.wav_i16) HIPCHECK(hipMemsetAsync(r.wav_i16, 0, sizeof(int16_t) * (size_t)r.wav_ld, s));
+      } else {
+        if (r.wav_f32) std::memset(r.wav_f32, 0, sizeof(float) * (size_t)r.wav_ld);
+        if (r.wav_i16) std::memset(r.wav_i16, 0, sizeof(int16_t) * (size_t)r.wav_ld);
+      }
+    }
+    if (out_dev) HIPCHECK(mi355_sync(s));
+    return 0;
+  }
+  if (F == 0) {
+    if (out_dev) {
+      if (wav_f32) HIPCHECK(hipMemsetAsync(wav_f32, 0, sizeof(float) * (size_t)B * wav_ld, s));
+      if (wav_i16) HIPCHECK(hipMemsetAsync(wav_i16, 0, sizeof(int16_t) * (size_t)B * wav_ld, s));
+      HIPCHECK(mi355_sync(s));
+    } else {
+      if (wav_f32) std::memset(wav_f32, 0, sizeof(float) * (size_t)B * wav_ld);
+      if (wav_i16) std::memset(wav_i16, 0, sizeof(int16_t) * (size_t)B * wav_ld);
+    }
+    return 0;
+  }
+  // an error return after kernels were queued must not hand the worker (its arena!) to the
+  // next call while they still run — possibly on the side streams
+  struct DrainOnError {
+    Worker* w;
+    bool ok = false;
+    ~DrainOnError() {
+      if (ok) return;
+      mi355_sync(w->stream);
+      for (int i = 0; i < 2; ++i)
+        if (w->aux[i]) mi355_sync(w->aux[i]);
+    }
+  } drain{w};
+  struct FlopScale {  // profiled FLOP of a ragged batch count the rows' real frames, not B x the longest row
+    Worker* w;
+    ~FlopScale() { w->flop_scale = 1.0; }
+  } fscale{w};
+  {
+    long long sum = 0;
+    for (int b = 0; b < B; ++b) sum += mel->frames[b];
+    w->flop_scale = (double)sum / ((double)B * F);
+  }
+  const CallOptions& opt = w->opt;  // as read when the worker was checked out: a call never mixes schedules if an option changes while it runs
+  const int prec = call.precision;  // as hifigan_precheck read it: the generator, the bias slot and the bias pass all see this value
+  const bool f16 = prec == MI355TTS_PRECISION_F16;  // the native fp16 generator (hifigan_f16.h): its own schedule, chains always write their own planes
+  if (f16 && !hm->f16_ok) return fail(MI355TTS_ERR_INVALID, "internal: fp16 mode on a vocoder it does not cover");
+  const float* const bias_spec = hm->bias_spec[f16 ? 1 : 0];
+  if (denoise && !bias_spec) return fail(MI355TTS_ERR_INVALID, "internal: no denoiser bias for this precision");
+  const bool split_out = f16 || hifi_split_out(opt.serial_branches, h);
+  // Option "voc_out" (default 1): conv_post + tanh + the rows' peaks in ONE dedicated launch and the delivery of the rows in one
+  // more (voc_out.h); 0 = the generic conv tile, zero_tail, absmax, to_int16 and a copy / fill per piece of every row.
+  const bool vo = f16 || (!opt.env.voc_out_off && opt.voc_out && hm->post_C == (h.upsample_initial_channel >> h.num_upsamples) && hm->post.K == 7);
+  if (prow && !vo) return fail(MI355TTS_ERR_INVALID, "internal: per-row outputs need the voc_out tail");
+  const int voc_host_len = B == 1 ? mel->frames[0] : -1;
+  int pads = call.pad_before + call.pad_after;
+  bool any_f32 = wav_f32 != nullptr, any_i16 = wav_i16 != nullptr;
+  if (prow) {
+    pads = 0;
+    any_f32 = any_i16 = false;
+    for (int b = 0; b < B; ++b) {
+      pads = std::max(pads, prow[b].pad_before + prow[b].pad_after);
+      any_f32 = any_f32 || prow[b].wav_f32;
+      any_i16 = any_i16 || prow[b].wav_i16;
+    }
+  }
+  const HifiLayout lay = hifi_layout(h, hop, B, F, denoise, split_out, pads);
+  const size_t Nld = lay.Nld;
+  const int nbuf = lay.nbuf, Tmax = lay.Tmax;
+  CHECK(reserve(w, lay.total));
+  char* base = w->arena;
+  float* buf[2 + 4 * 3];
+  for (int i = 0; i < nbuf; ++i) buf[i] = (float*)(base + lay.o_buf[i]);
+  float* wav = (float*)(base + lay.o_wav);
+  short* i16 = (short*)(base + lay.o_i16);
+  unsigned* peak = (unsigned*)(base + lay.o_peak);
+  const size_t o_wav2 = lay.o_wav2, o_fbuf = lay.o_fbuf;
+  const int* d_frames = mel->frames_dev;
+
+  // the dedicated conv_post kernels leave the per-workgroup maxima of the FINAL waveform (not behind the denoiser)
+  const long long peak_ld = (long long)(Nld / POST_TW + 2);
+  const bool peak_parts_ready = vo && any_i16 && !denoise;
+  float* const peak_parts = peak_parts_ready ? reinterpret_cast<float*>(peak) : nullptr;
+  if (f16) {
+    if ((size_t)((mel->M + 7) / 8) * F * 16 > lay.plane * sizeof(float)) return fail(MI355TTS_ERR_INVALID, "internal: mel octets exceed a plane buffer");
+    CHECK(hifigan_body_f16(ctx, w, hm, mel, buf, wav, Nld, peak_parts, peak_ld, voc_host_len, s));
+  } else {
+    CHECK(hifigan_body_f32(ctx, w, hm, mel, prec, buf, wav, Nld, peak_parts, peak_ld, vo, voc_host_len, s));
+  }
   if (denoise) {  // HiFiGanVocoder.denoise (larynx/hifi_gan.py:171-179)
     ProfScope ps(ctx, w, KC_SMALL, 0);
     float* wav2 = (float*)(base + o_wav2);
     float* fbuf = (float*)(base + o_fbuf);
-    hipLaunchKernelGGL(stft_denoise_kernel, dim3(Tmax, B), dim3(256), 0, s, wav, (long long)Nld, d_frames, hop, hm->bias_spec[f16 ? 1 : 0],
+    hipLaunchKernelGGL(stft_denoise_kernel, dim3(Tmax, B), dim3(256), 0, s, wav, (long long)Nld, d_frames, hop, bias_spec,
                        denoiser_strength, fbuf, Tmax, (float*)nullptr);
     hipLaunchKernelGGL(overlap_add_kernel, dim3(256, B), dim3(256), 0, s, fbuf, Tmax, d_frames, hop, wav2, (long long)Nld,
                        (long long)Nld);
@@ -676,17 +647,69 @@ static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355t
   return 0;
 }
 
-static int hifigan_call(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, const VocCall& call) {
-  if (!ctx || !mel) return fail(MI355TTS_ERR_INVALID, "null argument");
-  std::shared_ptr<HifiModel> vpin;
-  CHECK(find_hifi(ctx, vocoder, &vpin));
-  HifiModel* hm = vpin.get();
+// One vocoder call on a pinned model and a worker of its own; `call.precision` >= 0: the precision is already fixed
+static int hifigan_call_on(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, const mi355tts_mel* mel, VocCall call) {
   CHECK(hifigan_precheck(ctx, hm, vocoder, mel->frames.data(), mel->B, mel->M, mel->max_frames, call));
   HIPCHECK(hipSetDevice(ctx->device));
   Worker* w = nullptr;
   CHECK(acquire_worker(ctx, &w));
   WorkerGuard guard{ctx, w};
   return hifigan_run(ctx, w, hm, mel, call);
+}
+
+// The denoiser's bias spectrum of the generator of `precision` (the model keeps one per generator), computed on first use
+static int ensure_denoiser_bias(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, int precision) {
+  std::lock_guard<std::mutex> lk(hm->bias_mu);
+  const int bi = precision == MI355TTS_PRECISION_F16 ? 1 : 0;
+  if (hm->bias_ready[bi]) return 0;
+  const int M = hm->hp.num_mels, hop = hm->hop;
+  const int zf = 88;  // the reference's all-zero mel has 88 frames (hifi_gan.py:187,198)
+  const long long N = (long long)zf * hop;
+  if (N <= DN_FFT) return fail(MI355TTS_ERR_INVALID, "vocoder hop %d too small for the 1024-point denoiser STFT", hop);
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<float> zeros((size_t)M * zf, 0.f);
+  int32_t fr = zf;
+  mi355tts_mel* zm = nullptr;
+  CHECK(mi355tts_mel_from_buffer(ctx, zeros.data(), &fr, 1, M, zf, nullptr, 0, &zm));
+  float* dwav = nullptr;
+  float* bias = nullptr;
+  int rc = 0;
+  if (hipMalloc(&dwav, sizeof(float) * (size_t)N) != hipSuccess || hipMalloc(&bias, sizeof(float) * (DN_FFT / 2 + 1)) != hipSuccess)
+    rc = fail(MI355TTS_ERR_NOMEM, "hipMalloc denoiser bias");
+  if (!rc) {
+    VocCall c;
+    c.wav_f32 = dwav;
+    c.wav_ld = N;
+    c.flags = MI355TTS_OUT_DEVICE;
+    c.precision = precision;
+    rc = hifigan_call_on(ctx, hm, vocoder, zm, c);
+  }
+  if (!rc) {
+    Worker* w = nullptr;
+    rc = acquire_worker(ctx, &w);
+    if (!rc) {
+      WorkerGuard guard{ctx, w};
+      hipLaunchKernelGGL(stft_denoise_kernel, dim3(1, 1), dim3(256), 0, w->stream, dwav, (long long)N, zm->frames_dev, hop,
+                         (const float*)nullptr, 0.f, (float*)nullptr, 1, bias);
+      if (mi355_sync(w->stream) != hipSuccess) rc = fail(MI355TTS_ERR_HIP, "denoiser bias kernel failed");
+    }
+  }
+  mel_destroy(zm);
+  if (dwav) hipFree(dwav);
+  if (rc) {
+    if (bias) hipFree(bias);
+    return rc;
+  }
+  hm->bias_spec[bi] = bias;
+  hm->bias_ready[bi] = true;
+  return 0;
+}
+
+static int hifigan_call(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, const VocCall& call) {
+  if (!ctx || !mel) return fail(MI355TTS_ERR_INVALID, "null argument");
+  std::shared_ptr<HifiModel> vpin;
+  CHECK(find_hifi(ctx, vocoder, &vpin));
+  return hifigan_call_on(ctx, vpin.get(), vocoder, mel, call);
 }
 
 extern "C" int mi355tts_hifigan_infer(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, float denoiser_strength,

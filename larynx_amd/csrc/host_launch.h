@@ -43,15 +43,6 @@ static void launch_conv_inst(hipStream_t s, dim3 grid, const ConvArgs& a) {
   hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_mfma_kernel<K, CI_C, MB, NB, WN, KS, HALO, EPI>), grid, dim3(64 * WN * KS), 0, s, a);
 }
 
-// LDS halo capacity per tap count (max (K-1)*dilation the reference configs need)
-template <int K> struct ConvCfg;
-template <> struct ConvCfg<1> { static constexpr int HALO = 0; };
-template <> struct ConvCfg<2> { static constexpr int HALO = 4; };
-template <> struct ConvCfg<3> { static constexpr int HALO = 16; };
-template <> struct ConvCfg<5> { static constexpr int HALO = 28; };
-template <> struct ConvCfg<7> { static constexpr int HALO = 76; };
-template <> struct ConvCfg<11> { static constexpr int HALO = 56; };
-
 // Tile shapes (all 512 threads):
 // (2-column-block-per-wave variants at 64/128 columns, a 256-thread variant without
 //  k-split, and one-m-tile "wide" tiles with 2 or 4 column blocks per wave were measured
@@ -71,11 +62,10 @@ enum TileShape { TILE_SMALL = 0, TILE_W128 = 1, TILE_NB2 = 2, TILE_TINY = 3, TIL
 // rb_conv: the call's option "rb_conv" and not MI355TTS_NO_RB_CONV (the upsamplers' continuous-stream tile)
 template <int K, int EPI>
 static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const ConvArgs& a, bool rb_conv) {
-  constexpr int HALO = ConvCfg<K>::HALO;
+  constexpr int HALO = conv_halo(K);
   constexpr int CI_SMALL = (K == 1) ? 64 : 32;
   constexpr bool PAIRED = (EPI == EPI_GATE || EPI == EPI_COUPLING);
-  // the staged tile starts at the 4-aligned column t0 - roundup(pad, 4)
-  if ((K - 1) * a.dil + ((4 - a.pad % 4) % 4) > HALO)
+  if (!halo_fits(K, a.dil, a.pad, HALO))
     return fail(MI355TTS_ERR_INVALID, "conv K=%d dilation=%d exceeds the staged halo", K, a.dil);
   if (a.x_ld % 4) return fail(MI355TTS_ERR_INVALID, "internal: activation row stride %d is not a multiple of 4", a.x_ld);
   if constexpr (EPI == EPI_LINEAR && K >= 3) {
@@ -141,6 +131,28 @@ enum Bf16Cfg {
   BF_D = 3,  // 1 x 4 waves, NB = 1:  32 rows x 128 columns (32-channel stages; 256 columns would need 85 KB of LDS)
   BF_K = 4,  // 4 x 1 waves x 2 k-groups, NB = 4: 128 rows x 128 columns by 8 waves (few-tile launches with >= 64 channels in)
 };
+// their template arguments (conv_bf16_kernel<K, 1, NB, WM, WN, HALO, TERMS, KS, EPI>), by Bf16Cfg; 64 x WM x WN x KS threads
+struct Bf16Tile {
+  int NB, WM, WN, KS;
+};
+constexpr Bf16Tile BF16_TILES[5] = {{4, 4, 1, 1}, {1, 4, 1, 1}, {2, 2, 2, 1}, {1, 1, 4, 1}, {4, 4, 1, 2}};
+// f(tile, terms) with the plan's tile configuration and operand split (TERMS = 3: split bf16, 1: plain) as compile-time values
+template <class F>
+static bool bf16_dispatch(int cfg, int bf16, F&& f) {
+  return switch_const<BF_A, BF_B, BF_C, BF_D, BF_K>(cfg, [&](auto c) {
+    if (bf16 == 3) f(c, int_c<3>{});
+    else f(c, int_c<1>{});
+  });
+}
+template <int K, int EPI>
+static int launch_bf16_k(int cfg, int bf16, dim3 grid, hipStream_t s, const ConvArgs& a) {
+  const bool known = bf16_dispatch(cfg, bf16, [&](auto c, auto terms) {
+    constexpr Bf16Tile t = BF16_TILES[decltype(c)::value];
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<K, 1, t.NB, t.WM, t.WN, conv_halo(K), decltype(terms)::value, t.KS, EPI>), grid,
+                       dim3(64 * t.WM * t.WN * t.KS), 0, s, a);
+  });
+  return known ? 0 : fail(MI355TTS_ERR_INVALID, "internal: bf16 tile %d", cfg);
+}
 
 // `a` arrives with every tensor/epilogue field filled; this picks the tile and
 // template instance.  n_max = largest GEMM-N extent over the batch rows.
@@ -170,10 +182,9 @@ static int plan_conv(const CallOptions& o, const DevConv& c, ConvArgs a, int epi
   a.rows = c.rows;
   const bool half_on = (precision == MI355TTS_PRECISION_BF16X3 || precision == MI355TTS_PRECISION_BF16) && c.w16 && (a.x_ld % 4) == 0;
   const bool bf_linear = half_on && epi == EPI_LINEAR && !a.x2 && !a.y2 && a.split >= c.rows && a.out_act == ACT_NONE &&
-                         (c.K == 3 || c.K == 5 || c.K == 7 || c.K == 11) &&
-                         (c.K - 1) * a.dil + ((4 - a.pad % 4) % 4) <= (c.K == 3 ? 16 : c.K == 5 ? 28 : c.K == 7 ? 76 : 56);
+                         (c.K == 3 || c.K == 5 || c.K == 7 || c.K == 11) && halo_fits(c.K, a.dil, a.pad, conv_halo(c.K));
   // the polyphase upsamplers (two taps) in the split-bf16 mode too: 0.24 ms of f32 work per 'high' utterance otherwise
-  const bool bf_ups = half_on && !o.env.bf16_ups_off && epi == EPI_UPSAMPLE && c.K == 2 && (c.K - 1) * a.dil + ((4 - a.pad % 4) % 4) <= 4;
+  const bool bf_ups = half_on && !o.env.bf16_ups_off && epi == EPI_UPSAMPLE && c.K == 2 && halo_fits(2, a.dil, a.pad, conv_halo(2));
   if (bf_linear || bf_ups) {
     a.w16 = c.w16;
     a.nslab = c.nslab16;
@@ -285,85 +296,36 @@ static int plan_conv(const CallOptions& o, const DevConv& c, ConvArgs a, int epi
   return 0;
 }
 
+// the f32 tile of plan `p` for one epilogue and the tap counts it is built for
+template <int EPI, int... Ks>
+static int launch_conv_taps(const ConvPlan& p, const char* unsupported, hipStream_t s, bool rb_conv) {
+  int rc = 0;
+  if (!switch_const<Ks...>(p.K, [&](auto k) { rc = launch_conv_k<decltype(k)::value, EPI>(s, p.MB, p.shape, p.grid, p.a, rb_conv); }))
+    rc = fail(MI355TTS_ERR_INVALID, unsupported, p.K);
+  return rc;
+}
 static int run_plan(mi355tts_ctx* ctx, Worker* w, const ConvPlan& p, hipStream_t stream = nullptr) {
   if (p.empty) return 0;
   hipStream_t s = stream ? stream : w->stream;
   ProfScope ps(ctx, w, p.cls, p.flop, s);
   g_last_sub = p.a.rows;
-  const ConvArgs& a = p.a;
-  const int MB = p.MB, shape = p.shape;
-  const dim3 grid = p.grid;
-  int rc = 0;
   const bool rb_conv = w->opt.rb_conv && !w->opt.env.rb_conv_off;
   g_kn = w->quiet ? nullptr : ctx->kn;
   if (p.bf16) {
     kn_add(KN_CONV_BF16);
-#define BF16_LAUNCH_T(KK, TT)                                                                                                      \
-  if (shape == BF_A) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<KK, 1, 4, 4, 1, ConvCfg<KK>::HALO, TT>), grid, dim3(256), 0, s, a);      \
-  else if (shape == BF_B) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<KK, 1, 1, 4, 1, ConvCfg<KK>::HALO, TT>), grid, dim3(256), 0, s, a); \
-  else if (shape == BF_C) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<KK, 1, 2, 2, 2, ConvCfg<KK>::HALO, TT>), grid, dim3(256), 0, s, a); \
-  else if (shape == BF_K) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<KK, 1, 4, 4, 1, ConvCfg<KK>::HALO, TT, 2>), grid, dim3(512), 0, s, a); \
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<KK, 1, 1, 1, 4, ConvCfg<KK>::HALO, TT>), grid, dim3(256), 0, s, a)
-#define BF16_LAUNCH(KK)            \
-  if (p.bf16 == 3) {               \
-    BF16_LAUNCH_T(KK, 3);          \
-  } else {                         \
-    BF16_LAUNCH_T(KK, 1);          \
-  }
-#define BF16_UPS_T(TT)                                                                                                                              \
-  if (shape == BF_A) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<2, 1, 4, 4, 1, 4, TT, 1, EPI_UPSAMPLE>), grid, dim3(256), 0, s, a);      \
-  else if (shape == BF_B) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<2, 1, 1, 4, 1, 4, TT, 1, EPI_UPSAMPLE>), grid, dim3(256), 0, s, a); \
-  else if (shape == BF_C) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<2, 1, 2, 2, 2, 4, TT, 1, EPI_UPSAMPLE>), grid, dim3(256), 0, s, a); \
-  else if (shape == BF_K) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<2, 1, 4, 4, 1, 4, TT, 2, EPI_UPSAMPLE>), grid, dim3(512), 0, s, a); \
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_kernel<2, 1, 1, 1, 4, 4, TT, 1, EPI_UPSAMPLE>), grid, dim3(256), 0, s, a)
     if (p.epi == EPI_UPSAMPLE) {
       if (p.K != 2) return fail(MI355TTS_ERR_INVALID, "bf16 upsampler needs two taps");
-      if (p.bf16 == 3) {
-        BF16_UPS_T(3);
-      } else {
-        BF16_UPS_T(1);
-      }
-      return 0;
+      return launch_bf16_k<2, EPI_UPSAMPLE>(p.shape, p.bf16, p.grid, s, p.a);
     }
-#undef BF16_UPS_T
-    switch (p.K) {
-      case 3: BF16_LAUNCH(3); break;
-      case 5: BF16_LAUNCH(5); break;
-      case 7: BF16_LAUNCH(7); break;
-      case 11: BF16_LAUNCH(11); break;
-      default: rc = fail(MI355TTS_ERR_INVALID, "unsupported conv kernel size %d in bf16 mode", p.K);
-    }
-#undef BF16_LAUNCH_T
-#undef BF16_LAUNCH
+    int rc = 0;
+    if (!switch_const<3, 5, 7, 11>(p.K, [&](auto k) { rc = launch_bf16_k<decltype(k)::value, EPI_LINEAR>(p.shape, p.bf16, p.grid, s, p.a); }))
+      rc = fail(MI355TTS_ERR_INVALID, "unsupported conv kernel size %d in bf16 mode", p.K);
     return rc;
   }
-  if (p.epi == EPI_LINEAR) {
-    switch (p.K) {
-      case 1: rc = launch_conv_k<1, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
-      case 3: rc = launch_conv_k<3, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
-      case 5: rc = launch_conv_k<5, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
-      case 7: rc = launch_conv_k<7, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
-      case 11: rc = launch_conv_k<11, EPI_LINEAR>(s, MB, shape, grid, a, rb_conv); break;
-      default: rc = fail(MI355TTS_ERR_INVALID, "unsupported conv kernel size %d", p.K);
-    }
-  } else if (p.epi == EPI_GATE) {
-    switch (p.K) {
-      case 3: rc = launch_conv_k<3, EPI_GATE>(s, MB, shape, grid, a, rb_conv); break;
-      case 5: rc = launch_conv_k<5, EPI_GATE>(s, MB, shape, grid, a, rb_conv); break;
-      default: rc = fail(MI355TTS_ERR_INVALID, "unsupported WaveNet kernel size %d", p.K);
-    }
-  } else if (p.epi == EPI_COUPLING) {
-    if (p.K == 1) rc = launch_conv_k<1, EPI_COUPLING>(s, MB, shape, grid, a, rb_conv);
-    else rc = fail(MI355TTS_ERR_INVALID, "coupling conv must be 1x1");
-  } else {
-    switch (p.K) {
-      case 1: rc = launch_conv_k<1, EPI_UPSAMPLE>(s, MB, shape, grid, a, rb_conv); break;
-      case 2: rc = launch_conv_k<2, EPI_UPSAMPLE>(s, MB, shape, grid, a, rb_conv); break;
-      case 3: rc = launch_conv_k<3, EPI_UPSAMPLE>(s, MB, shape, grid, a, rb_conv); break;
-      default: rc = fail(MI355TTS_ERR_INVALID, "unsupported upsample taps %d", p.K);
-    }
-  }
-  return rc;
+  if (p.epi == EPI_LINEAR) return launch_conv_taps<EPI_LINEAR, 1, 3, 5, 7, 11>(p, "unsupported conv kernel size %d", s, rb_conv);
+  if (p.epi == EPI_GATE) return launch_conv_taps<EPI_GATE, 3, 5>(p, "unsupported WaveNet kernel size %d", s, rb_conv);
+  if (p.epi == EPI_COUPLING) return launch_conv_taps<EPI_COUPLING, 1>(p, "coupling conv must be 1x1", s, rb_conv);
+  return launch_conv_taps<EPI_UPSAMPLE, 1, 2, 3>(p, "unsupported upsample taps %d", s, rb_conv);
 }
 
 static int launch_conv(mi355tts_ctx* ctx, Worker* w, const DevConv& c, ConvArgs a, int epi, int B, int n_max, int cls,
@@ -376,7 +338,7 @@ static int launch_conv(mi355tts_ctx* ctx, Worker* w, const DevConv& c, ConvArgs 
 // ---- grouped launch: the same-geometry convs of the MRF chains of a stage in ONE launch
 template <int K0, int K1, int K2, int CI_C, int MB, int NB, int WN, int KS>
 static void launch_group_inst(hipStream_t s, dim3 grid, const ConvGroupArgs& g) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_group_kernel<K0, K1, K2, CI_C, MB, NB, WN, KS, ConvCfg<K0>::HALO, ConvCfg<K1>::HALO, ConvCfg<K2>::HALO>),
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_group_kernel<K0, K1, K2, CI_C, MB, NB, WN, KS, conv_halo(K0), conv_halo(K1), conv_halo(K2)>),
                      grid, dim3(64 * WN * KS), 0, s, g);
 }
 template <int K0, int K1, int K2>
@@ -389,7 +351,7 @@ static int launch_group_k(hipStream_t s, int MB, int shape, dim3 grid, const Con
   else if (shape == TILE_W128 && MB == 1) launch_group_inst<K0, K1, K2, 32, 1, 2, 2, 4>(s, grid, g);
   else if (shape == TILE_NB2 && MB == 2) launch_group_inst<K0, K1, K2, 16, 2, 2, 4, 2>(s, grid, g);
   else if (shape == TILE_M128)  // 16-channel chunks, one time-wave: <= 128 VGPRs, four 4-wave workgroups per CU
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_group_kernel<K0, K1, K2, 16, 1, 2, 1, 1, ConvCfg<K0>::HALO, ConvCfg<K1>::HALO, ConvCfg<K2>::HALO, 4>),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_group_kernel<K0, K1, K2, 16, 1, 2, 1, 1, conv_halo(K0), conv_halo(K1), conv_halo(K2), 4>),
                        grid, dim3(256), 0, s, g);
   else {
     if (g_kn) g_kn[KN_CONV_GROUP].fetch_sub(1, std::memory_order_relaxed);
@@ -402,7 +364,7 @@ static int launch_group_k(hipStream_t s, int MB, int shape, dim3 grid, const Con
 static bool rb_member_ok(const ConvArgs& a, int K) {
   const int halo = K == 11 ? RbCfg<11>::HALO : K == 7 ? RbCfg<7>::HALO : RbCfg<3>::HALO;
   return !a.x2 && !a.x3 && a.bias && a.alpha == 1.0f && !a.accum && a.out_act == ACT_NONE && a.split >= a.rows && !a.y2 &&
-         a.rows % 128 == 0 && (K - 1) * a.dil + ((4 - a.pad % 4) % 4) <= halo;
+         a.rows % 128 == 0 && halo_fits(K, a.dil, a.pad, halo);
 }
 
 // The same-geometry convs of the three MRF chains of a step (hifigan_forward.h plans them together).  At batch 1, members that
@@ -416,19 +378,18 @@ static bool rb_member_ok(const ConvArgs& a, int K) {
 static void promote_group_plans(const CallOptions& o, ConvPlan* const* plans, int n) {
   // (option "rb_conv" = 0 / MI355TTS_NO_RB_CONV then run the chunked 128-row kernel in the plain order: same bits, slower)
   if (n != 3 || o.env.group_promote_off || !o.group_promote) return;
-  int total = 0, taps = 0;
-  int tiles[3] = {0, 0, 0};  // by member in tap order 11, 7, 3
+  int K[3], tiles[3];
   for (int i = 0; i < 3; ++i) {
     const ConvPlan& p = *plans[i];
     if (p.empty || p.bf16 || p.pinned || p.epi != EPI_LINEAR || p.cls != KC_RESBLOCK || p.shape == TILE_M128 || p.grid.z != 1 ||
         p.n_max <= 0 || (p.a.x_ld % 4) || (p.K != 11 && p.K != 7 && p.K != 3) || !rb_member_ok(p.a, p.K))
       return;
-    taps |= p.K == 11 ? 1 : p.K == 7 ? 2 : 4;
-    tiles[p.K == 11 ? 0 : p.K == 7 ? 1 : 2] = ((p.n_max + 63) / 64) * (p.a.rows / 128);
-    total += (((p.n_max + 63) / 64) * (p.a.rows / 128) + 7) & ~7;
+    K[i] = p.K;
+    tiles[i] = ((p.n_max + 63) / 64) * (p.a.rows / 128);
   }
-  const int ncu = o.ncu;  // (tests reach the multi-round shapes at emulator sizes with MI355TTS_GROUP_NCU)
-  if (taps != 7 || total <= ncu) return;
+  const GroupLayout lay = group_layout(K, tiles);
+  const int ncu = o.ncu, total = lay.off[3];  // (tests reach the multi-round shapes at emulator sizes with MI355TTS_GROUP_NCU)
+  if (!lay.k1173 || total <= ncu) return;
   if (total <= 4 * ncu) {
     // All resident at once: nothing is dealt dynamically, so the launch lasts as long as its busiest CU.  The big tile runs at
     // ~0.83 of peak against ~0.65-0.70 for the k-split tile it replaces (whose many small workgroups ARE dealt dynamically):
@@ -441,11 +402,11 @@ static void promote_group_plans(const CallOptions& o, ConvPlan* const* plans, in
     // summation order, so it must not depend on who else is running.
     const double max_imbalance = o.env.promote_max_imbalance;
     ConvGroupArgs g;
-    g.off[0] = 0;
-    for (int m = 0; m < 3; ++m) g.off[m + 1] = g.off[m] + ((tiles[m] + 7) & ~7);
+    std::copy(lay.off, lay.off + 4, g.off);
     group_snake_order(g, ncu, 4 * ncu);
+    const int real[3] = {tiles[lay.ord[0]], tiles[lay.ord[1]], tiles[lay.ord[2]]};
     const double cost[3] = {11.0, 7.0, 3.0};
-    if (group_order_imbalance(g, ncu, tiles, cost) > max_imbalance) return;
+    if (group_order_imbalance(g, ncu, real, cost) > max_imbalance) return;
   }
   for (int i = 0; i < 3; ++i) {
     ConvPlan& p = *plans[i];
@@ -456,71 +417,48 @@ static void promote_group_plans(const CallOptions& o, ConvPlan* const* plans, in
   }
 }
 
-static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n, hipStream_t s) {
+static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* const* plans, int n, hipStream_t s) {
   const CallOptions& o = w->opt;
   if (o.env.group_off || n != 3) return 1;
-  // members ordered by tap count, longest-running first
-  int ord[3] = {0, 1, 2};
-  for (int i = 0; i < 3; ++i)
-    for (int j = i + 1; j < 3; ++j)
-      if (plans[ord[j]].K > plans[ord[i]].K) std::swap(ord[i], ord[j]);
+  const int K[3] = {plans[0]->K, plans[1]->K, plans[2]->K};
+  int tiles[3];
+  for (int i = 0; i < 3; ++i) tiles[i] = (int)(plans[i]->grid.x * plans[i]->grid.y);
+  const GroupLayout lay = group_layout(K, tiles);
   const int ncu = o.ncu;
-  const ConvPlan& p0 = plans[ord[0]];
-  for (int i = 0; i < 3; ++i) {
-    const ConvPlan& p = plans[ord[i]];
-    if (p.empty || p.epi != EPI_LINEAR || p.shape != p0.shape || p.MB != p0.MB || p.grid.z != p0.grid.z || p.bf16 != p0.bf16) return 1;
-    if ((p.K - 1) * p.a.dil + ((4 - p.a.pad % 4) % 4) > (p.K == 3 ? 16 : p.K == 5 ? 28 : p.K == 7 ? 76 : p.K == 11 ? 56 : -1)) return 1;
-    if (p.a.x_ld % 4) return 1;
-  }
+  const ConvPlan* m[3] = {plans[lay.ord[0]], plans[lay.ord[1]], plans[lay.ord[2]]};  // the members in launch order
+  const ConvPlan& p0 = *m[0];
   ConvGroupArgs g;
   double flop = 0;
-  int off_wg = 0;
   for (int i = 0; i < 3; ++i) {
-    const ConvPlan& p = plans[ord[i]];
+    const ConvPlan& p = *m[i];
+    if (p.empty || p.epi != EPI_LINEAR || p.shape != p0.shape || p.MB != p0.MB || p.grid.z != p0.grid.z || p.bf16 != p0.bf16) return 1;
+    if (!halo_fits(p.K, p.a.dil, p.a.pad, conv_halo(p.K))) return 1;
+    if (p.a.x_ld % 4) return 1;
     g.c[i] = p.a;
     g.gx[i] = (int)p.grid.x;
     g.gy[i] = (int)p.grid.y;
-    g.off[i] = off_wg;
-    off_wg += ((int)(p.grid.x * p.grid.y) + 7) & ~7;
     flop += p.flop;
   }
-  g.off[3] = off_wg;
-  const dim3 grid(off_wg, 1, p0.grid.z);
-  const int k0 = plans[ord[0]].K, k1 = plans[ord[1]].K, k2 = plans[ord[2]].K;
-  const bool taps_ok = (k0 == 11 && k1 == 7 && k2 == 3) || (k0 == 7 && k1 == 5 && k2 == 3);
+  std::copy(lay.off, lay.off + 4, g.off);
+  const dim3 grid(g.off[3], 1, p0.grid.z);
+  const bool taps_ok = lay.k1173 || lay.k753;
   g_kn = w->quiet ? nullptr : ctx->kn;
   if (p0.bf16) {
     if (!taps_ok) return 1;
     ProfScope ps(ctx, w, p0.cls, flop, s);
     g_last_sub = p0.a.rows;
     kn_add(KN_CONV_BF16_GROUP);
-#define BF16_GROUP_T(KA, KB, KC, TT)                                                                                                                \
-  if (p0.shape == BF_A)                                                                                                                            \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_group_kernel<KA, KB, KC, 1, 4, 4, 1, ConvCfg<KA>::HALO, ConvCfg<KB>::HALO, ConvCfg<KC>::HALO, TT>), \
-                       grid, dim3(256), 0, s, g);                                                                                                  \
-  else if (p0.shape == BF_B)                                                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_group_kernel<KA, KB, KC, 1, 1, 4, 1, ConvCfg<KA>::HALO, ConvCfg<KB>::HALO, ConvCfg<KC>::HALO, TT>), \
-                       grid, dim3(256), 0, s, g);                                                                                                  \
-  else if (p0.shape == BF_C)                                                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_group_kernel<KA, KB, KC, 1, 2, 2, 2, ConvCfg<KA>::HALO, ConvCfg<KB>::HALO, ConvCfg<KC>::HALO, TT>), \
-                       grid, dim3(256), 0, s, g);                                                                                                  \
-  else if (p0.shape == BF_K)                                                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_group_kernel<KA, KB, KC, 1, 4, 4, 1, ConvCfg<KA>::HALO, ConvCfg<KB>::HALO, ConvCfg<KC>::HALO, TT, 2>), \
-                       grid, dim3(512), 0, s, g);                                                                                                  \
-  else                                                                                                                                             \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_group_kernel<KA, KB, KC, 1, 1, 1, 4, ConvCfg<KA>::HALO, ConvCfg<KB>::HALO, ConvCfg<KC>::HALO, TT>), \
-                       grid, dim3(256), 0, s, g)
-#define BF16_GROUP(KA, KB, KC)      \
-  if (p0.bf16 == 3) {               \
-    BF16_GROUP_T(KA, KB, KC, 3);    \
-  } else {                          \
-    BF16_GROUP_T(KA, KB, KC, 1);    \
-  }
-    if (k0 == 11) { BF16_GROUP(11, 7, 3); }
-    else { BF16_GROUP(7, 5, 3); }
-#undef BF16_GROUP_T
-#undef BF16_GROUP
-    return 0;
+    bool known = false;
+    switch_taps(lay, [&](auto k0, auto k1, auto k2) {
+      constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value, K2 = decltype(k2)::value;
+      known = bf16_dispatch(p0.shape, p0.bf16, [&](auto c, auto terms) {
+        constexpr Bf16Tile t = BF16_TILES[decltype(c)::value];
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_bf16_group_kernel<K0, K1, K2, 1, t.NB, t.WM, t.WN, conv_halo(K0), conv_halo(K1), conv_halo(K2),
+                                                                  decltype(terms)::value, t.KS>),
+                           grid, dim3(64 * t.WM * t.WN * t.KS), 0, s, g);
+      });
+    });
+    return known ? 0 : fail(MI355TTS_ERR_INVALID, "internal: bf16 tile %d", p0.shape);
   }
   const bool shape_ok = (p0.shape == TILE_TINY) || (p0.shape == TILE_SMALL && p0.MB == 2) || (p0.shape == TILE_W128 && p0.MB == 1) ||
                         (p0.shape == TILE_NB2 && p0.MB == 2) || p0.shape == TILE_M128;
@@ -529,7 +467,7 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n,
   g_last_sub = p0.a.rows;
   // The 128-row tile with the continuous matrix stream (rb_conv.h; same bits as the chunked tile) where the launch is
   // what it was written for: plain ResBlock convs (bias, optional residual), taps 11 / 7 / 3, dilation within its halos.
-  if (p0.shape == TILE_M128 && k0 == 11 && !o.env.rb_conv_off && o.rb_conv) {
+  if (p0.shape == TILE_M128 && lay.k1173 && !o.env.rb_conv_off && o.rb_conv) {
     bool rb_ok = true;
     for (int i = 0; i < 3; ++i) rb_ok = rb_ok && rb_member_ok(g.c[i], i == 0 ? 11 : i == 1 ? 7 : 3);
     if (rb_ok) {
@@ -544,17 +482,12 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n,
       // MI355TTS_RB_NB4_MIN_TILES = threshold whatever the load (tests, A/B runs), 0 = never.
       const int nb4_min = o.env.rb_nb4_min_tiles != KNOB_UNSET ? o.env.rb_nb4_min_tiles : (ctx->active_calls.load(std::memory_order_relaxed) > 1 ? 3 * ncu : 0);
       if (nb4_min > 0 && grid.z == 1) {
-        int tiles4 = 0;
-        for (int i = 0; i < 3; ++i) tiles4 += ((plans[ord[i]].n_max + 127) / 128) * g.gy[i];
-        if (tiles4 >= nb4_min) {
-          int o4 = 0;
-          for (int i = 0; i < 3; ++i) {
-            g.gx[i] = (plans[ord[i]].n_max + 127) / 128;
-            g.off[i] = o4;
-            o4 += (g.gx[i] * g.gy[i] + 7) & ~7;
-          }
-          g.off[3] = o4;
-          const dim3 grid4(o4, 1, 1);
+        int gx4[3], tiles4[3];
+        for (int i = 0; i < 3; ++i) tiles4[i] = (gx4[i] = (m[i]->n_max + 127) / 128) * g.gy[i];
+        if (tiles4[0] + tiles4[1] + tiles4[2] >= nb4_min) {
+          std::copy(gx4, gx4 + 3, g.gx);
+          group_offsets(tiles4, g.off);
+          const dim3 grid4(g.off[3], 1, 1);
           if (snake) group_snake_order(g, ncu, 3 * ncu);
           kn_add(KN_RB_GROUP_NB4);
           hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3, 4>), grid4, dim3(256), 0, s, g);
@@ -567,19 +500,25 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* plans, int n,
       return 0;
     }
   }
-  if (k0 == 11) return launch_group_k<11, 7, 3>(s, p0.MB, p0.shape, grid, g);
-  return launch_group_k<7, 5, 3>(s, p0.MB, p0.shape, grid, g);
+  int rc = 1;
+  switch_taps(lay, [&](auto k0, auto k1, auto k2) {
+    rc = launch_group_k<decltype(k0)::value, decltype(k1)::value, decltype(k2)::value>(s, p0.MB, p0.shape, grid, g);
+  });
+  return rc;
 }
 
-// Tile of the fused split-bf16 pair kernel (resblock_pair_bf16.h): time-waves x column blocks per wave, 256 columns in all
-#ifndef P16_WN64
-#define P16_WN64 4
-#define P16_NB64 2
-#endif
-#ifndef P16_WN32
-#define P16_WN32 4
-#define P16_NB32 2
-#endif
+// Tiles of the fused pair kernels by channel count (32, 64): CB 32-channel row blocks; f32 (resblock_pair.h) NB column blocks
+// per wave; split-bf16 (resblock_pair_bf16.h) WN16 time-waves x NB16 column blocks per wave, 256 columns in all, 64 CB WN16 threads
+struct PairTile {
+  int CB, NB, WN16, NB16;
+};
+constexpr PairTile PAIR_TILES[2] = {{1, 2, 4, 2}, {2, 1, 4, 2}};
+// f(tile index) for a plan's channel count
+template <class F>
+static void pair_tile_dispatch(int C, F&& f) {
+  if (C == 32) f(int_c<0>{});
+  else f(int_c<1>{});
+}
 // Fused ResBlock1 step (conv1 -> lrelu -> conv2 -> + x) for the 32/64-channel stages.
 struct PairPlan {
   PairArgs a;
@@ -647,93 +586,52 @@ static int run_pair(mi355tts_ctx* ctx, Worker* w, const PairPlan& p, hipStream_t
   const PairArgs& a = p.a;
   const dim3 grid = p.grid;
   g_kn = w->quiet ? nullptr : ctx->kn;
-  kn_add(p.bf16 ? KN_PAIR_BF16 : (w->opt.rb_pair && p.rb) ? KN_RB_PAIR : KN_PAIR);
-  if (p.bf16) {
-#define PAIR16_LAUNCH(KK, TT)                                                                                                                  \
-  if (p.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_kernel<KK, 1, P16_WN32, P16_NB32, TT>), grid, dim3(64 * P16_WN32), 0, s, a);     \
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_kernel<KK, 2, P16_WN64, P16_NB64, TT>), grid, dim3(128 * P16_WN64), 0, s, a)
-#define PAIR16_K(KK)          \
-  if (p.bf16 == 3) {          \
-    PAIR16_LAUNCH(KK, 3);     \
-  } else {                    \
-    PAIR16_LAUNCH(KK, 1);     \
-  }
-    if (p.K == 3) { PAIR16_K(3); }
-    else if (p.K == 7) { PAIR16_K(7); }
-    else { PAIR16_K(11); }
-#undef PAIR16_K
-#undef PAIR16_LAUNCH
-    return 0;
-  }
-  if (w->opt.rb_pair && p.rb) {  // the 4-wave tile without a k-split (rb_pair.h): same tiles and arguments
-#define RBP_LAUNCH(KK)                                                                                               \
-  if (p.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_kernel<KK, 1>), grid, dim3(256), 0, s, a);               \
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_kernel<KK, 2>), grid, dim3(256), 0, s, a)
-    if (p.K == 3) { RBP_LAUNCH(3); }
-    else if (p.K == 7) { RBP_LAUNCH(7); }
-    else { RBP_LAUNCH(11); }
-#undef RBP_LAUNCH
-    return 0;
-  }
-#define PAIR_LAUNCH(KK, CB, NBB) hipLaunchKernelGGL(HIP_KERNEL_NAME(resblock_pair_kernel<KK, CB, NBB>), grid, dim3(512), 0, s, a)
-#define PAIR_K(KK)                                  \
-  if (p.C == 32) PAIR_LAUNCH(KK, 1, 2);             \
-  else PAIR_LAUNCH(KK, 2, 1)
-  if (p.K == 3) { PAIR_K(3); }
-  else if (p.K == 7) { PAIR_K(7); }
-  else { PAIR_K(11); }
-#undef PAIR_K
-#undef PAIR_LAUNCH
-  return 0;
+  const bool rb = w->opt.rb_pair && p.rb;  // the 4-wave tile without a k-split (rb_pair.h): same tiles and arguments
+  kn_add(p.bf16 ? KN_PAIR_BF16 : rb ? KN_RB_PAIR : KN_PAIR);
+  const bool known = switch_const<3, 7, 11>(p.K, [&](auto k) {
+    pair_tile_dispatch(p.C, [&](auto c) {
+      constexpr int K = decltype(k)::value;
+      constexpr PairTile t = PAIR_TILES[decltype(c)::value];
+      if (p.bf16 == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_kernel<K, t.CB, t.WN16, t.NB16, 3>), grid, dim3(64 * t.CB * t.WN16), 0, s, a);
+      else if (p.bf16) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_kernel<K, t.CB, t.WN16, t.NB16, 1>), grid, dim3(64 * t.CB * t.WN16), 0, s, a);
+      else if (rb) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_kernel<K, t.CB>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(HIP_KERNEL_NAME(resblock_pair_kernel<K, t.CB, t.NB>), grid, dim3(512), 0, s, a);
+    });
+  });
+  return known ? 0 : fail(MI355TTS_ERR_INVALID, "internal: fused pair with %d taps", p.K);
 }
 // The three chains' fused steps as ONE launch (k = 11, 7, 3 members).  0 = launched, 1 = not groupable.
-static int run_pair_group(mi355tts_ctx* ctx, Worker* w, const PairPlan* plans, int n, hipStream_t s) {
+static int run_pair_group(mi355tts_ctx* ctx, Worker* w, const PairPlan* const* plans, int n, hipStream_t s) {
   if (w->opt.env.group_off || n != 3) return 1;
-  int ord[3] = {0, 1, 2};
-  for (int i = 0; i < 3; ++i)
-    for (int j = i + 1; j < 3; ++j)
-      if (plans[ord[j]].K > plans[ord[i]].K) std::swap(ord[i], ord[j]);
-  const PairPlan& p0 = plans[ord[0]];
-  for (int i = 0; i < 3; ++i) {
-    const PairPlan& p = plans[ord[i]];
-    if (!p.ok || p.C != p0.C || p.NB != p0.NB || p.grid.z != p0.grid.z || p.bf16 != p0.bf16 || p.rb != p0.rb) return 1;
-  }
-  if (!(plans[ord[0]].K == 11 && plans[ord[1]].K == 7 && plans[ord[2]].K == 3)) return 1;
-  if (!p0.bf16 && !((p0.C == 32 && p0.NB == 2) || (p0.C == 64 && p0.NB == 1))) return 1;
+  const int K[3] = {plans[0]->K, plans[1]->K, plans[2]->K};
+  const int tiles[3] = {(int)plans[0]->grid.x, (int)plans[1]->grid.x, (int)plans[2]->grid.x};
+  const GroupLayout lay = group_layout(K, tiles);
+  const PairPlan& p0 = *plans[lay.ord[0]];
   PairGroupArgs g;
   double flop = 0;
-  int off_wg = 0;
   for (int i = 0; i < 3; ++i) {
-    const PairPlan& p = plans[ord[i]];
+    const PairPlan& p = *plans[lay.ord[i]];
+    if (!p.ok || p.C != p0.C || p.NB != p0.NB || p.grid.z != p0.grid.z || p.bf16 != p0.bf16 || p.rb != p0.rb) return 1;
     g.p[i] = p.a;
     g.gx[i] = (int)p.grid.x;
-    g.off[i] = off_wg;
-    off_wg += ((int)p.grid.x + 7) & ~7;
     flop += p.flop;
   }
-  g.off[3] = off_wg;
-  const dim3 grid(off_wg, 1, p0.grid.z);
+  if (!lay.k1173) return 1;
+  if (!p0.bf16 && !((p0.C == 32 && p0.NB == 2) || (p0.C == 64 && p0.NB == 1))) return 1;
+  std::copy(lay.off, lay.off + 4, g.off);
+  const dim3 grid(g.off[3], 1, p0.grid.z);
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
   g_last_sub = p0.C;
   g_kn = w->quiet ? nullptr : ctx->kn;
-  kn_add(p0.bf16 ? KN_PAIR_BF16_GROUP : (w->opt.rb_pair && p0.rb) ? KN_RB_PAIR_GROUP : KN_PAIR_GROUP);
-  if (p0.bf16 == 3) {
-    if (p0.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, 1, P16_WN32, P16_NB32, 3>), grid, dim3(64 * P16_WN32), 0, s, g);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, 2, P16_WN64, P16_NB64, 3>), grid, dim3(128 * P16_WN64), 0, s, g);
-    return 0;
-  }
-  if (p0.bf16 == 1) {
-    if (p0.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, 1, P16_WN32, P16_NB32, 1>), grid, dim3(64 * P16_WN32), 0, s, g);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, 2, P16_WN64, P16_NB64, 1>), grid, dim3(128 * P16_WN64), 0, s, g);
-    return 0;
-  }
-  if (w->opt.rb_pair && p0.rb) {
-    if (p0.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_group_kernel<11, 7, 3, 1>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_group_kernel<11, 7, 3, 2>), grid, dim3(256), 0, s, g);
-    return 0;
-  }
-  if (p0.C == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_group_kernel<11, 7, 3, 1, 2>), grid, dim3(512), 0, s, g);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_group_kernel<11, 7, 3, 2, 1>), grid, dim3(512), 0, s, g);
+  const bool rb = w->opt.rb_pair && p0.rb;
+  kn_add(p0.bf16 ? KN_PAIR_BF16_GROUP : rb ? KN_RB_PAIR_GROUP : KN_PAIR_GROUP);
+  pair_tile_dispatch(p0.C, [&](auto c) {
+    constexpr PairTile t = PAIR_TILES[decltype(c)::value];
+    if (p0.bf16 == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, t.CB, t.WN16, t.NB16, 3>), grid, dim3(64 * t.CB * t.WN16), 0, s, g);
+    else if (p0.bf16 == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, t.CB, t.WN16, t.NB16, 1>), grid, dim3(64 * t.CB * t.WN16), 0, s, g);
+    else if (rb) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_group_kernel<11, 7, 3, t.CB>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_group_kernel<11, 7, 3, t.CB, t.NB>), grid, dim3(512), 0, s, g);
+  });
   return 0;
 }
 
@@ -812,26 +710,11 @@ static int run_gate16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const Conv
   const long long wide_min = o.gate16_wide;
   const bool wide = wide_min > 0 && c.g16_J == 6 && (gy % 2) == 0 && (long long)gx * gy * B >= wide_min;  // (the released voices' width)
   const dim3 grid(gx, wide ? gy / 2 : gy, B);
-#define GATE16_LAUNCH(KK, JJ) gate16_launch<KK, JJ>(wide, grid, s, g)
-#define GATE16_J(KK)                      \
-  switch (c.g16_J) {                      \
-    case 1: GATE16_LAUNCH(KK, 1); break;  \
-    case 2: GATE16_LAUNCH(KK, 2); break;  \
-    case 3: GATE16_LAUNCH(KK, 3); break;  \
-    case 4: GATE16_LAUNCH(KK, 4); break;  \
-    case 6: GATE16_LAUNCH(KK, 6); break;  \
-    case 8: GATE16_LAUNCH(KK, 8); break;  \
-    default: return 1;                    \
-  }
-  if (c.K == 3) {
-    GATE16_J(3)
-  } else if (c.K == 5) {
-    GATE16_J(5)
-  } else {
-    return 1;
-  }
-#undef GATE16_J
-#undef GATE16_LAUNCH
+  bool known = false;
+  switch_const<3, 5>(c.K, [&](auto k) {
+    known = switch_const<1, 2, 3, 4, 6, 8>(c.g16_J, [&](auto j) { gate16_launch<decltype(k)::value, decltype(j)::value>(wide, grid, s, g); });
+  });
+  if (!known) return 1;
   kn_hit(ctx, wide ? KN_GATE16_WIDE : KN_GATE16);
   return 0;
 }

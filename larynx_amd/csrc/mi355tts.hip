@@ -49,6 +49,7 @@ using namespace mi355tts;
 #include "host_models.h"
 #include "host_options.h"
 #include "host_context.h"
+#include "host_group.h"
 #include "host_launch.h"
 #include "hifigan_f16.h"
 
@@ -1085,7 +1086,7 @@ extern "C" int mi355tts_reserve(mi355tts_ctx* ctx, int workers, int glow, int vo
     need = std::max(need, std::max(a.total, b.total));
     M = std::max(M, (int)hm->hp.num_mels);
     out_bytes = (size_t)max_batch * ((size_t)max_frames * hm->hop + max_pad_samples) * (sizeof(float) + sizeof(short));
-    if (dn) CHECK(ensure_denoiser_bias(ctx, hm, vocoder));
+    if (dn) CHECK(ensure_denoiser_bias(ctx, hm, vocoder, hm->precision.load()));
   }
   mel_bytes = (size_t)max_batch * M * (size_t)((max_frames + 3) & ~3) * sizeof(float);
   HIPCHECK(hipSetDevice(ctx->device));
@@ -1405,14 +1406,14 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
     for (int warm = 0; warm < 2 && !rc; ++warm)
       for (int order = 0; order < 2 && !rc; ++order) {
         w->opt.group_snake = order == 1;
-        if (run_group(ctx, w, plans, 3, s) != 0) rc = 1;
+        if (run_group(ctx, w, pp, 3, s) != 0) rc = 1;
       }
     for (int rep = 0; rep < 4 && !rc; ++rep)
       for (int order = 0; order < 2 && !rc; ++order) {
         w->opt.group_snake = order == 1;
         hipEventRecord(e0, s);
         for (int i = 0; i < 2 && !rc; ++i)
-          if (run_group(ctx, w, plans, 3, s) != 0) rc = 1;
+          if (run_group(ctx, w, pp, 3, s) != 0) rc = 1;
         hipEventRecord(e1, s);
         float ms = 0.f;
         if (mi355_sync(s) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = 1;

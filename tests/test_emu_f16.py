@@ -150,3 +150,51 @@ def test_f16_is_refused_with_a_reason_where_it_does_not_apply(emu_engine):
         assert emu_engine.set_precision(g, ffi.PRECISION_F32) == 0
     finally:
         emu_engine.unload(g)
+
+
+def test_precision_switched_during_denoised_calls_never_mixes_generators_and_biases(emu_engine):
+    """mi355tts_model_set_precision may run on another thread while a denoised call is in flight.  A call reads the model's
+    precision once: its bias pass, its generator and the bias slot it hands the denoiser all follow that one value.  So every
+    call gives exactly what a model nobody switches gives in f32 or in fp16 (or a clean error), and afterwards each
+    precision's bias is its own generator's — none was computed by one generator and kept in the other's slot."""
+    import threading
+
+    hp = HP.TINY_HIFIGAN_RB2  # hop 16: the bias pass's 88 zero frames are longer than one 1024-sample STFT frame
+    sd = synthetic.make_hifigan_state_dict(hp, seed=21)
+    rng = np.random.default_rng(3)
+    mel_np = (rng.standard_normal((1, hp.num_mels, 96)) * 1.5 - 4).astype(np.float32)
+    mel = emu_engine.mel_from_numpy(mel_np)
+    strength = 0.5
+    quiet = emu_engine.load_hifigan(hp, sd)
+    ref = {}
+    for prec in (ffi.PRECISION_F32, ffi.PRECISION_F16):
+        emu_engine.set_precision(quiet, prec)
+        ref[prec] = emu_engine.hifigan_infer(quiet, mel, denoiser_strength=strength)[0]
+    assert not np.array_equal(ref[ffi.PRECISION_F32], ref[ffi.PRECISION_F16])
+    v = emu_engine.load_hifigan(hp, sd)
+    emu_engine.hifigan_infer(v, mel, denoiser_strength=strength)  # the f32 bias exists, the fp16 one does not yet
+    stop = threading.Event()
+
+    def flip():
+        while not stop.is_set():
+            emu_engine.set_precision(v, ffi.PRECISION_F16)
+            emu_engine.set_precision(v, ffi.PRECISION_F32)
+
+    t = threading.Thread(target=flip)
+    t.start()
+    try:
+        for _ in range(60):
+            try:
+                wav = emu_engine.hifigan_infer(v, mel, denoiser_strength=strength)[0]
+            except ffi.Mi355ttsError as e:
+                assert e.code == -1, e  # MI355TTS_ERR_INVALID: refused before any launch
+                continue
+            assert any(np.array_equal(wav, r) for r in ref.values()), "a call mixed the two precisions"
+    finally:
+        stop.set()
+        t.join()
+    for prec in (ffi.PRECISION_F32, ffi.PRECISION_F16):
+        emu_engine.set_precision(v, prec)
+        assert np.array_equal(emu_engine.hifigan_infer(v, mel, denoiser_strength=strength)[0], ref[prec])
+    emu_engine.unload(v)
+    emu_engine.unload(quiet)
