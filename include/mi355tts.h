@@ -211,6 +211,39 @@ int mi355tts_hifigan_infer_padded(mi355tts_ctx* ctx, int vocoder, const mi355tts
                                   float* wav_f32, int16_t* wav_i16, int64_t wav_ld, uint32_t flags, int32_t pad_before,
                                   int32_t pad_after);
 
+/* ---- Griffin-Lim: replaces GriffinLimVocoder.mels_to_audio -------------------
+ * (larynx/griffin_lim.py:22-76 on the STFT helpers of larynx/audio.py:232-306): a vocoder without weights.  The
+ * magnitudes are exp(mel) @ mel_basis * mel_scaling with the last mel frame dropped, the phase starts uniform and
+ * `iterations` rounds of transform + inverse refine it — 1024-point frames every 256 samples, symmetric Hann window on
+ * analysis and synthesis, no window-sum normalisation: the reference's hard-wired conventions (fft and hop are NOT
+ * parameters: audio.py:284,297; a voice whose filter_length / hop_length differ is rejected by the Python wrapper).
+ * `mel_basis` is the host array [num_mels][513] (larynx_amd.audio.mel_basis builds the reference's Slaney filter bank).
+ * mi355tts_unload frees the model.  Added in ABI version 2 (additive: the version number is unchanged). */
+typedef struct {
+  int32_t num_mels;    /* 1 .. 256 */
+  float mel_scaling;   /* the reference's 1000.0 */
+  int32_t iterations;  /* the reference's 60; >= 0 */
+} mi355tts_griffin_lim_params;
+int mi355tts_load_griffin_lim(mi355tts_ctx* ctx, const mi355tts_griffin_lim_params* params, const float* mel_basis,
+                              int* model_out);
+/* A mel row of F frames gives T = F - 1 STFT frames and (F - 1) * 256 + 1024 samples (F < 2: an empty signal); the row's
+ * tail up to wav_ld is zero-filled; wav_ld >= (max_frames - 1) * 256 + 1024.  The mel is the vocoder-input plane of `mel`
+ * (ln domain, what dynamic_range_decompression expects).
+ * phase0 (optional): the initial phase [B][513][max_frames - 1] standing in for the reference's np.random.rand draw
+ *   (griffin_lim.py:68) — parity mode.  NULL draws it on the device: u = a 24-bit uniform from the counter hash of the
+ *   noise generator keyed by (`seed` + row, bin, frame), phase = np.angle(np.exp(2j pi u)) in (-pi, pi).
+ * phase_out (optional, same shape): the initial phase the call used; a call that injects it as phase0 reproduces the
+ *   seeded call bit for bit.  Entries past a row's T frames are zero.
+ * wav_f32 (optional): the float signal (the reference returns it as float64; this is float32).  wav_i16 (optional): its
+ *   audio_float_to_int16 (larynx/audio.py:118-125), computed on the device.
+ * iterations <= 0: the model's.  One launch per iteration; the signal lives as overlapping synthesis frames in between
+ *   (csrc/griffin_lim.h).  flags: MI355TTS_IN_DEVICE — phase0 is device memory; MI355TTS_OUT_DEVICE — phase_out and the
+ *   waveform pointers are.  All arithmetic is f32: a mel whose magnitudes leave the f32 range (one that is not in the ln
+ *   domain: spectra beyond ~1e30) is out of scope — the result is then unspecified, not an error. */
+int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi355tts_mel* mel, const float* phase0, uint64_t seed,
+                               float* phase_out, float* wav_f32, int16_t* wav_i16, int64_t wav_ld, int iterations,
+                               uint32_t flags);
+
 /* ---- fused call: replaces the model half of _sentence_task -------------------
  * (larynx/__init__.py:229-283: phonemes_to_mels -> mel transforms -> mels_to_audio -> pause
  * padding) with ONE call on one stream: arguments as in mi355tts_glow_infer +

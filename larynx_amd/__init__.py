@@ -58,6 +58,11 @@ def load_vocoder_model(model_type, model_path, backend=InferenceBackend.HIP, no_
         from .hifi_gan import HipHiFiGanVocoder
 
         return HipHiFiGanVocoder(config, executor=executor, **kwargs)
+    if model_type == VocoderType.GRIFFIN_LIM:
+        # no weights: `model_path` is ignored, as in the reference (`larynx/__init__.py:498-501`)
+        from .griffin_lim import HipGriffinLimVocoder
+
+        return HipGriffinLimVocoder(config, **kwargs)
     raise ValueError(f"Unknown vocoder model type: {model_type}")
 
 

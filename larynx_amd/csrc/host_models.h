@@ -308,6 +308,17 @@ struct HifiModel {
   }
 };
 
+// The Griffin-Lim vocoder (griffin_lim.h) has no weights: its "model" is the mel filter bank [num_mels][513] and three numbers
+struct GriffinLimModel {
+  mi355tts_griffin_lim_params p;
+  int device = 0;
+  float* basis = nullptr;
+  ~GriffinLimModel() {
+    DeviceScope ds(device);
+    if (basis) hipFree(basis);
+  }
+};
+
 static std::vector<std::pair<std::string, int64_t>> glow_manifest(const mi355tts_glow_hparams& h) {
   std::vector<std::pair<std::string, int64_t>> m;
   auto add = [&](const std::string& n, int64_t e) { m.emplace_back(n, e); };

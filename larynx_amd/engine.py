@@ -389,6 +389,50 @@ class Engine:
         )
         return f32, i16
 
+    # ---- Griffin-Lim -----------------------------------------------------------
+    def load_griffin_lim(self, mel_basis: np.ndarray, mel_scaling: float = 1000.0, iterations: int = 60) -> int:
+        """`mi355tts_load_griffin_lim`: the weight-free vocoder (`larynx/griffin_lim.py:22-38`); `mel_basis` is
+        [num_mels, 513] (`larynx_amd.audio.mel_basis`).  `unload` frees it."""
+        basis = np.ascontiguousarray(mel_basis, np.float32)
+        if basis.ndim != 2 or basis.shape[1] != 513:
+            raise ValueError(f"mel_basis must be [num_mels, 513] (1024-point frames), got {basis.shape}")
+        p = ffi.GriffinLimParamsC(int(basis.shape[0]), float(mel_scaling), int(iterations))
+        model = C.c_int()
+        ffi.check(self.lib, self.lib.mi355tts_load_griffin_lim(self._ctx, C.byref(p), basis.ctypes.data, C.byref(model)))
+        return int(model.value)
+
+    def griffin_lim_infer(self, model: int, mel: MelBatch, phase0: typing.Optional[np.ndarray] = None, seed: int = 0,
+                          iterations: int = 0, want_float: bool = True, want_int16: bool = False, want_phase: bool = False):
+        """Returns (wav_f32 [B, N] or None, wav_i16 [B, N] or None, phase [B, 513, T] or None), T = max_frames - 1 and
+        N = T * 256 + 1024 (0 when T = 0); row b holds (frames[b] - 1) * 256 + 1024 samples, then zeros.  `phase0`
+        ([B, 513, T] or [513, T]) stands in for the reference's `np.random.rand` draw; without it the device draws from
+        `seed` (row b: seed + b).  `iterations` <= 0: the model's."""
+        T = max(mel.max_frames - 1, 0)
+        n = T * 256 + 1024 if T else 0
+        B = mel.batch
+        if phase0 is not None:
+            phase0 = np.ascontiguousarray(phase0, np.float32)
+            if phase0.ndim == 2:
+                phase0 = phase0[None]
+            if phase0.shape != (B, 513, T):
+                raise ValueError(f"phase0 must be [{B}, 513, {T}], got {phase0.shape}")
+        f32 = np.empty((B, n), np.float32) if want_float else None
+        i16 = np.empty((B, n), np.int16) if want_int16 else None
+        ph = np.empty((B, 513, T), np.float32) if want_phase else None
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_griffin_lim_infer(self._ctx, int(model), mel.handle, ffi.ptr(phase0), int(seed) & (2 ** 64 - 1),
+                                                ffi.ptr(ph), ffi.ptr(f32), ffi.ptr(i16), n, int(iterations), 0),
+        )
+        return f32, i16, ph
+
+    def griffin_lim_infer_raw(self, model: int, mel: MelBatch, phase0_ptr, seed, phase_out_ptr, f32_ptr, i16_ptr, wav_ld,
+                              iterations=0, flags=0):
+        """Pointer-level entry (`flags`: ffi.IN_DEVICE for phase0, ffi.OUT_DEVICE for phase_out and the waveforms)."""
+        ffi.check(self.lib, self.lib.mi355tts_griffin_lim_infer(self._ctx, int(model), mel.handle, phase0_ptr,
+                                                                int(seed) & (2 ** 64 - 1), phase_out_ptr, f32_ptr, i16_ptr,
+                                                                int(wav_ld), int(iterations), int(flags)))
+
     # ---- single operators ------------------------------------------------------
     def conv1d(self, x, w, bias=None, dilation=1, in_slope=1.0, out_act=0, lens=None) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

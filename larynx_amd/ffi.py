@@ -72,6 +72,10 @@ class AudioSettingsC(C.Structure):
     ]
 
 
+class GriffinLimParamsC(C.Structure):
+    _fields_ = [("num_mels", C.c_int32), ("mel_scaling", C.c_float), ("iterations", C.c_int32)]
+
+
 class Mi355ttsError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"mi355tts error {code}: {message}")
@@ -120,6 +124,8 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
     "mi355tts_hifigan_hop": (C.c_int, [_VP, C.c_int]),
     "mi355tts_hifigan_infer": (C.c_int, [_VP, C.c_int, _VP, C.c_float, _VP, _VP, C.c_int64, C.c_uint32]),
     "mi355tts_hifigan_infer_padded": (C.c_int, [_VP, C.c_int, _VP, C.c_float, _VP, _VP, C.c_int64, C.c_uint32, C.c_int32, C.c_int32]),
+    "mi355tts_load_griffin_lim": (C.c_int, [_VP, C.POINTER(GriffinLimParamsC), _VP, C.POINTER(C.c_int)]),
+    "mi355tts_griffin_lim_infer": (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_uint32]),
     "mi355tts_synthesize": (
         C.c_int,
         [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,
