@@ -180,6 +180,42 @@ int mi355tts_glow_infer_speakers(mi355tts_ctx* ctx, int glow, const int64_t* ids
                                  const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
                                  uint32_t flags, mi355tts_mel** out);
 
+/* Phoneme timings out, per-id timing control in (glow_tts/models.py:323-335: w, w_ceil, generate_path; :350-354: the `attn`
+ * FlowGenerator.forward returns next to the mel — attn[b, 0, t, :].sum() is the number of mel frames id t occupies).
+ * All three arrays are HOST memory [B][ld] whatever `flags` says, ld >= the longest row; entries past a row's length are
+ * not read (inputs) and written as 0 (output).
+ *   id_scales     a rate per id: w = (exp(logw) * length_scale) * id_scales[t] in f32, in this order, then ceil as in the
+ *                 reference.  Finite and >= 0.  Exactly 1.0f gives the duration of a call without it (an all-ones array is
+ *                 bit-identical to no prosody); 0 gives the id no frames (generate_path handles zero durations).
+ *   durations_in  stands in for ceil(w) altogether, each in [0, 2^28]: logw, length_scale and id_scales are not read for the
+ *                 durations; the cumulative sum, the frame count and everything behind them are unchanged.  Excludes id_scales.
+ *   durations_out what every id got.  TRUNCATION RULE: the row's frame count F is max(sum, 1) cut down to a multiple of n_sqz,
+ *                 and the reference masks the path to F frames (sequence_mask(y_lengths) in attn_mask, models.py:329-335), so
+ *                 durations_out[t] = min(cum[t], F) - min(cum[t-1], F), not simply ceil(w): when the sum is odd at n_sqz = 2
+ *                 the last id that has frames loses one.  The row sums to F (except: every duration 0 at n_sqz = 1, where
+ *                 F = 1 and the sum is 0).  All durations 0 at n_sqz = 2 gives F = 0: an empty mel.
+ * ROUND TRIP: feeding a call's durations_out back as durations_in, with the same noise or seed, reproduces its mel bit for
+ * bit and the same durations.
+ * mi355tts_glow_infer_prosody: the arguments of mi355tts_glow_infer_speakers (speaker_ids NULL for a single-speaker voice, same
+ * rules as there), then `prosody`.  NULL behaves exactly like that call.  Otherwise the mel keeps the per-id durations
+ * (mi355tts_mel_durations), and durations_out, when given, receives them as well.
+ * A call without prosody pays nothing: same launches, copies and host synchronisations as before; with it, the same launches
+ * (the durations are written by the launch that computes them) and one more small copy each way.
+ * Added in ABI version 2 (additive: the version number is unchanged). */
+typedef struct {
+  const float* id_scales;     /* host [B][ld] or NULL */
+  const int32_t* durations_in; /* host [B][ld] or NULL; excludes id_scales */
+  int32_t* durations_out;     /* host [B][ld] or NULL */
+  int32_t ld;
+} mi355tts_prosody;
+int mi355tts_glow_infer_prosody(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
+                                float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
+                                const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
+                                uint32_t flags, const mi355tts_prosody* prosody, mi355tts_mel** out);
+/* dst host [B][ld], ld >= the ld the call was made with (columns past it: 0).  MI355TTS_ERR_INVALID for a mel that has no
+ * durations: one wrapped by mi355tts_mel_from_buffer, or made by a call without prosody. */
+int mi355tts_mel_durations(const mi355tts_mel* mel, int32_t* dst, int ld);
+
 int mi355tts_mel_batch(const mi355tts_mel* mel);
 int mi355tts_mel_channels(const mi355tts_mel* mel);
 int mi355tts_mel_max_frames(const mi355tts_mel* mel);
@@ -264,6 +300,17 @@ int mi355tts_synthesize_speakers(mi355tts_ctx* ctx, int glow, int vocoder, const
                                  uint64_t seed, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
                                  float denoiser_strength, int32_t pad_before, int32_t pad_after, int32_t* frames_out,
                                  float* wav_f32, int16_t* wav_i16, int64_t wav_ld, uint32_t flags);
+
+/* The fused call with mi355tts_prosody (see mi355tts_glow_infer_prosody): the arguments of mi355tts_synthesize_speakers
+ * (speaker_ids NULL for a single-speaker voice), then `prosody`; NULL, or a struct with three NULL arrays, behaves exactly like
+ * that call.  durations_out is filled before the call returns, also when it returns MI355TTS_ERR_TOO_SMALL, like frames_out.
+ * A call that passes any of the three arrays runs on its own (like one with explicit noise, it never shares a coalesced pass). */
+int mi355tts_synthesize_prosody(mi355tts_ctx* ctx, int glow, int vocoder, const int64_t* ids, const int32_t* id_lens, int B,
+                                int ids_ld, float noise_scale, float length_scale, const float* noise, int noise_ld,
+                                uint64_t seed, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
+                                float denoiser_strength, int32_t pad_before, int32_t pad_after, int32_t* frames_out,
+                                float* wav_f32, int16_t* wav_i16, int64_t wav_ld, uint32_t flags,
+                                const mi355tts_prosody* prosody);
 
 /* Serving set-up (the reference warms its model caches the same way, larynx/__init__.py:290,412):
  * pre-create `workers` per-call workers (stream, side streams, pinned staging) and size

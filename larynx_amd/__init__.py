@@ -33,7 +33,7 @@ _LOGGER = logging.getLogger("larynx_amd")
 
 __all__ = [
     "AudioSettings", "InferenceBackend", "TextToSpeechResult", "load_tts_model", "load_vocoder_model",
-    "sentence_task", "phonemes_to_speech",
+    "sentence_task", "sentence_task_aligned", "phonemes_to_speech",
 ]
 
 
@@ -72,8 +72,36 @@ def sentence_task(text: str, phoneme_ids, audio_settings, tts_model, tts_setting
     `_sentence_task` (`larynx/__init__.py:214-285`): GlowTTS, the mel transforms
     (numpy here only if the model did not already fuse them), the vocoder, the
     three debug log lines and the SSML pause padding."""
+    return _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                     pause_before_ms, pause_after_ms)[0]
+
+
+def sentence_task_aligned(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                          pause_before_ms: int = 0, pause_after_ms: int = 0) -> typing.Tuple[np.ndarray, np.ndarray]:
+    """`sentence_task` that also returns where every phoneme id sounds: `(audio, spans)`, spans int64 [P, 2] in samples
+    of `audio`, leading pause included (`larynx_amd.alignment.phoneme_spans`).  The TTS model must be one whose mels
+    carry durations (`HipGlowTextToSpeech`); the audio is what `sentence_task` gives for the same settings.  With a
+    Griffin-Lim vocoder the spans are nominal frame positions (hop 256), see `phoneme_spans`."""
+    settings = dict(tts_settings or {})
+    settings["alignment"] = True
+    audio, mels, before = _sentence(text, phoneme_ids, audio_settings, tts_model, settings, vocoder_model, vocoder_settings,
+                                    pause_before_ms, pause_after_ms)
+    from .alignment import phoneme_spans
+
+    durations = getattr(mels, "durations", None)
+    if durations is None:
+        raise ValueError("the text-to-speech model's mels carry no per-phoneme durations")
+    hparams = getattr(vocoder_model, "hparams", None)
+    hop = int(hparams.hop) if hparams is not None else 256  # Griffin-Lim: hard-wired 256 (larynx/audio.py:284,297)
+    return audio, phoneme_spans(durations[0], hop, pad_before=before)
+
+
+def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
+              pause_after_ms):
+    """-> (audio, the mels the vocoder consumed, leading pause in samples)"""
     t0 = time.perf_counter()
     mels = tts_model.phonemes_to_mels(phoneme_ids, settings=tts_settings)
+    tts_mels = mels
     t1 = time.perf_counter()
     _LOGGER.debug("Got mels in %s second(s) (shape=%s, text='%s')", t1 - t0, getattr(mels, "shape", None), text)
     if audio_settings is not None and (audio_settings.signal_norm or audio_settings.convert_db_to_amp
@@ -86,6 +114,7 @@ def sentence_task(text: str, phoneme_ids, audio_settings, tts_model, tts_setting
     sample_rate = audio_settings.sample_rate if audio_settings is not None else 22050
     before = max(0, (pause_before_ms * sample_rate) // 1000)
     after = max(0, (pause_after_ms * sample_rate) // 1000)
+    lead = before
     t2 = time.perf_counter()
     padded = getattr(vocoder_model, "mels_to_audio_padded", None)
     if padded is not None and (before or after):
@@ -100,7 +129,7 @@ def sentence_task(text: str, phoneme_ids, audio_settings, tts_model, tts_setting
     _LOGGER.debug("Real-time factor: %0.2f (infer=%0.2f sec, audio=%0.2f sec)", (t3 - t0) / dur if dur > 0 else 0.0, t3 - t0, dur)
     if before or after:
         audio = np.pad(audio, pad_width=(before, after), constant_values=0)
-    return audio
+    return audio, tts_mels, lead
 
 
 def _ensure_pool_workers(executor, *models):
@@ -118,10 +147,11 @@ def _ensure_pool_workers(executor, *models):
 def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Sequence[int]]], tts_model, vocoder_model,
                        tts_settings: typing.Optional[SettingsType] = None,
                        vocoder_settings: typing.Optional[SettingsType] = None,
-                       executor: typing.Optional[Executor] = None) -> typing.Iterable[TextToSpeechResult]:
+                       executor: typing.Optional[Executor] = None, alignment: bool = False) -> typing.Iterable[TextToSpeechResult]:
     """`text_to_speech` (`larynx/__init__.py:47-190`) from the point where gruut /
     phonemes2ids have produced ids: one task per sentence on an executor, results
-    yielded in submission order."""
+    yielded in submission order.  `alignment`: every result also carries `phoneme_spans`, the start and end sample
+    of each phoneme id in its audio (`sentence_task_aligned`); the audio is the same either way."""
     own = executor is None
     executor = executor or ThreadPoolExecutor()
     _ensure_pool_workers(executor, tts_model, vocoder_model)
@@ -129,12 +159,13 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
         audio_settings = getattr(tts_model, "audio_settings", None)
         futures = []
         for text, ids in sentences:
-            fut = executor.submit(sentence_task, text, np.asarray(ids, np.int64), audio_settings, tts_model, tts_settings,
+            fut = executor.submit(sentence_task_aligned if alignment else sentence_task, text, np.asarray(ids, np.int64), audio_settings, tts_model, tts_settings,
                                   vocoder_model, vocoder_settings)
             futures.append((text, fut))
         sr = audio_settings.sample_rate if audio_settings is not None else 22050
         for text, fut in futures:
-            yield TextToSpeechResult(text=text, audio=fut.result(), sample_rate=sr)
+            audio, spans = fut.result() if alignment else (fut.result(), None)
+            yield TextToSpeechResult(text=text, audio=audio, sample_rate=sr, phoneme_spans=spans)
     finally:
         if own:
             executor.shutdown(wait=True)

@@ -1,0 +1,22 @@
+"""Phoneme timings: from the frames every phoneme id occupies (`MelBatch.durations`, the reference's
+`attn.sum(-1)`, glow_tts/models.py:350-354) to sample positions in the delivered audio."""
+from __future__ import annotations
+
+import numpy as np
+
+
+def phoneme_spans(durations, hop: int, pad_before: int = 0) -> np.ndarray:
+    """`durations` [P] (frames per id) -> int64 [P, 2]: id t sounds in samples [start, end) of the audio, with
+    start = pad_before + hop * (frames before t) and end = pad_before + hop * (frames up to and including t).
+    `pad_before` is the leading pause in samples (`_sentence_task`'s pause_before_ms).  An id without frames has
+    an empty span (start == end) at its position; the last end is pad_before + F * hop.
+
+    With the HiFi-GAN vocoder these are exact: frame j becomes samples [j * hop, (j + 1) * hop).  Griffin-Lim audio
+    has (F - 1) * 256 + 1024 samples (overlapping 1024-sample frames every 256): the spans there are NOMINAL frame
+    positions, hop 256 — the last ends can lie past the middle of the final frame's window."""
+    d = np.asarray(durations, np.int64).reshape(-1)
+    if np.any(d < 0):
+        raise ValueError("durations must be >= 0")
+    end = np.cumsum(d)
+    spans = np.stack([end - d, end], axis=1) * int(hop) + int(pad_before)
+    return spans.astype(np.int64)

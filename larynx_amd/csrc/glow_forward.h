@@ -145,6 +145,22 @@ struct GlowCall {
   bool solo_tiles = false;
   const mi355tts_audio_settings* audio = nullptr;
   uint32_t flags = 0;
+  // prosody (mi355tts_prosody), all host [B][pros_ld] like speaker_ids: a rate per id, or durations that stand in for the
+  // predictor's; want_durations: the mel keeps what every id got (durations_out, when given, receives a copy)
+  const float* id_scales = nullptr;
+  const int32_t* durations_in = nullptr;
+  int32_t* durations_out = nullptr;
+  int pros_ld = 0;
+  bool want_durations = false;
+  void set_prosody(const mi355tts_prosody* p, bool keep) {
+    if (!p) return;
+    id_scales = p->id_scales;
+    durations_in = p->durations_in;
+    durations_out = p->durations_out;
+    pros_ld = p->ld;
+    want_durations = keep || p->durations_out;
+  }
+  bool has_prosody() const { return id_scales || durations_in || want_durations; }
 };
 
 // pins the model: the caller's shared_ptr keeps it alive until the call returns, whatever mi355tts_unload does meanwhile
@@ -183,6 +199,20 @@ static int glow_precheck(const GlowModel* gm, const GlowCall& c, int* Pmax_out) 
         if (id < 0 || id >= gm->hp.num_symbols)
           return fail(MI355TTS_ERR_INVALID, "phoneme id %lld at [%d][%d] outside [0,%d)", (long long)id, b, t, gm->hp.num_symbols);
       }
+  }
+  if (c.has_prosody()) {
+    if (c.id_scales && c.durations_in) return fail(MI355TTS_ERR_INVALID, "prosody: id_scales and durations_in exclude each other");
+    for (int b = 0; b < c.B; ++b) {
+      if (c.pros_ld < c.id_lens[b])
+        return fail(MI355TTS_ERR_INVALID, "prosody: ld %d < id_lens[%d]=%d", c.pros_ld, b, c.id_lens[b]);
+      for (int t = 0; t < c.id_lens[b]; ++t) {
+        const size_t i = (size_t)b * c.pros_ld + t;
+        if (c.id_scales && !(std::isfinite(c.id_scales[i]) && c.id_scales[i] >= 0.f))
+          return fail(MI355TTS_ERR_INVALID, "prosody: id_scales[%d][%d]=%g is not a finite value >= 0", b, t, (double)c.id_scales[i]);
+        if (c.durations_in && (c.durations_in[i] < 0 || c.durations_in[i] > (1 << 28)))
+          return fail(MI355TTS_ERR_INVALID, "prosody: durations_in[%d][%d]=%d outside [0, 2^28]", b, t, c.durations_in[i]);
+      }
+    }
   }
   *Pmax_out = Pmax;
   return 0;
@@ -277,7 +307,11 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
   const int att_rows = el.att_rows;
   const size_t enc_bytes = el.total;
   const size_t o_len = el.o_len, o_xm = el.o_xm, o_cum = el.o_cum;
-  CHECK(reserve(w, enc_bytes));
+  // a call's id_scales or durations_in (one of them, 4-byte entries, row stride P) sit right behind the encoder's region, where
+  // the decoder's workspace is appended later: duration_kernel has consumed them by then.  No other call's layout changes.
+  const void* pros_src = call.id_scales ? (const void*)call.id_scales : (const void*)call.durations_in;
+  const size_t o_pros = (enc_bytes + 255) & ~(size_t)255;
+  CHECK(reserve(w, pros_src ? o_pros + sizeof(float) * (size_t)B * P : enc_bytes));
   char* base = w->arena;
   int* d_len = (int*)(base + el.o_len);
   long long* d_ids = (long long*)(base + el.o_ids);
@@ -305,6 +339,12 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
   } else {
     HIPCHECK(hipMemcpyAsync(d_ids, ids, sizeof(long long) * (size_t)B * ids_ld, in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   }
+
+  // prosody inputs go up with the ids
+  void* d_pros = pros_src ? (void*)(base + o_pros) : nullptr;
+  if (pros_src)
+    HIPCHECK(hipMemcpy2DAsync(d_pros, sizeof(float) * P, pros_src, sizeof(float) * call.pros_ld, sizeof(float) * Pmax, (size_t)B,
+                              hipMemcpyHostToDevice, s));
 
   // multi-speaker voices: everything the speaker vector feeds, once per call (small_kernels.h: speaker_cond_kernel)
   const int gin = gm->gin();
@@ -463,6 +503,15 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
       delete m;
       return fail(MI355TTS_ERR_NOMEM, "hipMalloc frames");
     }
+    if (call.want_durations) {  // only a call that asks pays for the block, the copy behind the frame counts and the host vector
+      m->dur_ld = call.pros_ld;
+      m->dur_dev = (int*)pool_alloc(ctx, sizeof(int) * (size_t)B * m->dur_ld);
+      if (!m->dur_dev) {
+        mel_destroy(m);
+        return fail(MI355TTS_ERR_NOMEM, "hipMalloc durations");
+      }
+      m->durations.assign((size_t)B * m->dur_ld, 0);
+    }
     mel = m;
   }
   struct MelGuard {  // error exits: nothing queued on the stream may still write the blocks that go back to the pool
@@ -477,11 +526,15 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
   {
     ProfScope ps(ctx, w, KC_SMALL, 0);
     hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(64), 0, s, logw, (long long)P, d_len, length_scale, h.n_sqz, cum, P,
-                       mel->frames_dev, 1 << 28);
+                       mel->frames_dev, 1 << 28, call.id_scales ? (const float*)d_pros : nullptr,
+                       call.durations_in ? (const int*)d_pros : nullptr, P, mel->dur_dev, mel->dur_ld);
   }
   if ((size_t)B > w->pinned_ints) return fail(MI355TTS_ERR_INVALID, "batch too large");
   HIPCHECK(hipMemcpyAsync(w->pinned, mel->frames_dev, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+  if (mel->dur_dev)
+    HIPCHECK(hipMemcpyAsync(mel->durations.data(), mel->dur_dev, sizeof(int) * mel->durations.size(), hipMemcpyDeviceToHost, s));
   HIPCHECK(mi355_sync(s));
+  if (call.durations_out) std::memcpy(call.durations_out, mel->durations.data(), sizeof(int32_t) * mel->durations.size());
   int Fmax = 0;
   for (int b = 0; b < B; ++b) {
     mel->frames[b] = w->pinned[b];
@@ -649,7 +702,7 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
 static int glow_infer_impl(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
                            float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
                            const uint64_t* row_seeds, const mi355tts_audio_settings* audio, uint32_t flags, mi355tts_mel** out,
-                           const int32_t* speaker_ids = nullptr) {
+                           const int32_t* speaker_ids = nullptr, const mi355tts_prosody* prosody = nullptr) {
   if (!ctx || !out) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GlowModel> gpin;
   CHECK(find_glow(ctx, glow, &gpin));
@@ -668,6 +721,7 @@ static int glow_infer_impl(mi355tts_ctx* ctx, int glow, const int64_t* ids, cons
   c.speaker_ids = speaker_ids;
   c.audio = audio;
   c.flags = flags;
+  c.set_prosody(prosody, true);  // the two-call form: the mel always keeps the durations
   int Pmax = 0;
   CHECK(glow_precheck(gm, c, &Pmax));
   HIPCHECK(hipSetDevice(ctx->device));
@@ -695,4 +749,11 @@ extern "C" int mi355tts_glow_infer_rows(mi355tts_ctx* ctx, int glow, const int64
                                         const mi355tts_audio_settings* audio, uint32_t flags, mi355tts_mel** out) {
   if (!row_seeds) return fail(MI355TTS_ERR_INVALID, "row_seeds null");
   return glow_infer_impl(ctx, glow, ids, id_lens, B, ids_ld, noise_scale, length_scale, nullptr, 0, 0, row_seeds, audio, flags, out);
+}
+extern "C" int mi355tts_glow_infer_prosody(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
+                                           float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
+                                           const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
+                                           uint32_t flags, const mi355tts_prosody* prosody, mi355tts_mel** out) {
+  return glow_infer_impl(ctx, glow, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, row_seeds, audio, flags, out,
+                         speaker_ids, prosody);
 }

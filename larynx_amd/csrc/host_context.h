@@ -176,6 +176,11 @@ struct mi355tts_mel {
   std::vector<int32_t> frames;
   int max_frames = 0;
   size_t raw_bytes = 0;  // allocation size of raw / voc (pool bookkeeping)
+  // per-id durations [B][dur_ld] (frames each id occupies: duration_kernel's durations_out), only for a call that asked: the
+  // device block the kernel wrote and its host copy, made behind the frame counts (mi355tts_mel_durations reads the latter)
+  int* dur_dev = nullptr;
+  int dur_ld = 0;
+  std::vector<int32_t> durations;
 };
 
 static inline void kn_hit(mi355tts_ctx* ctx, int k) {

@@ -791,6 +791,7 @@ static void mel_destroy(mi355tts_mel* m) {
   pool_free(m->ctx, m->raw, m->raw_bytes);
   pool_free(m->ctx, m->voc, m->raw_bytes);
   pool_free(m->ctx, m->frames_dev, sizeof(int) * (size_t)m->B);
+  pool_free(m->ctx, m->dur_dev, sizeof(int) * (size_t)m->B * (size_t)m->dur_ld);
   delete m;
 }
 extern "C" void mi355tts_mel_free(mi355tts_mel* m) { mel_destroy(m); }
@@ -800,6 +801,14 @@ extern "C" int mi355tts_mel_max_frames(const mi355tts_mel* m) { return m ? m->ma
 extern "C" int mi355tts_mel_frames(const mi355tts_mel* m, int32_t* frames) {
   if (!m || !frames) return fail(MI355TTS_ERR_INVALID, "null argument");
   for (int b = 0; b < m->B; ++b) frames[b] = m->frames[b];
+  return 0;
+}
+extern "C" int mi355tts_mel_durations(const mi355tts_mel* m, int32_t* dst, int ld) {
+  if (!m || !dst) return fail(MI355TTS_ERR_INVALID, "null argument");
+  if (m->durations.empty()) return fail(MI355TTS_ERR_INVALID, "this mel carries no durations (a wrapped buffer, or a call that did not ask)");
+  if (ld < m->dur_ld) return fail(MI355TTS_ERR_INVALID, "ld %d < the %d columns the durations were made with", ld, m->dur_ld);
+  for (int b = 0; b < m->B; ++b)
+    for (int t = 0; t < ld; ++t) dst[(size_t)b * ld + t] = t < m->dur_ld ? m->durations[(size_t)b * m->dur_ld + t] : 0;
   return 0;
 }
 extern "C" int mi355tts_mel_copy(const mi355tts_mel* m, int which, float* dst, int ld) {
@@ -896,7 +905,7 @@ static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const int64
                            float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
                            const int32_t* speaker_ids, const mi355tts_audio_settings* audio, float denoiser_strength,
                            int32_t pad_before, int32_t pad_after, int32_t* frames_out, float* wav_f32, int16_t* wav_i16,
-                           int64_t wav_ld, uint32_t flags) {
+                           int64_t wav_ld, uint32_t flags, const mi355tts_prosody* prosody = nullptr) {
   if (!ctx || !frames_out) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GlowModel> gpin;
   std::shared_ptr<HifiModel> vpin;
@@ -917,6 +926,7 @@ static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const int64
   g.speaker_ids = speaker_ids;
   g.audio = audio;
   g.flags = flags & MI355TTS_IN_DEVICE;
+  g.set_prosody(prosody, false);
   VocCall v;
   v.denoiser_strength = denoiser_strength;
   v.wav_f32 = wav_f32;
@@ -931,7 +941,7 @@ static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const int64
   HIPCHECK(hipSetDevice(ctx->device));
   // (decided before a worker, and with it a CallOptions, exists: the one place that reads these options off the context)
   const int lanes = g_env.call_coalesce_off ? 0 : ctx->opts.call_coalesce.load();
-  if (lanes > 0 && B == 1 && !noise && !speaker_ids && id_lens[0] <= ATTM_MAXP && ctx->opts.voc_out.load() && !ctx->opts.serial_branches.load()) {
+  if (lanes > 0 && B == 1 && !noise && !speaker_ids && !g.has_prosody() && id_lens[0] <= ATTM_MAXP && ctx->opts.voc_out.load() && !ctx->opts.serial_branches.load()) {
     // a batch-1 call: it rides a fused padded call with whichever other batch-1 calls are waiting right now (host_join.h)
     CallReq req;
     req.gm = gm;
@@ -993,6 +1003,17 @@ extern "C" int mi355tts_synthesize_speakers(mi355tts_ctx* ctx, int glow, int voc
   if (!speaker_ids) return fail(MI355TTS_ERR_INVALID, "speaker_ids null");
   return synthesize_impl(ctx, glow, vocoder, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, speaker_ids, audio,
                          denoiser_strength, pad_before, pad_after, frames_out, wav_f32, wav_i16, wav_ld, flags);
+}
+
+// the same with per-id timing control and read-out (mi355tts_prosody); speaker_ids NULL for a single-speaker voice
+extern "C" int mi355tts_synthesize_prosody(mi355tts_ctx* ctx, int glow, int vocoder, const int64_t* ids, const int32_t* id_lens, int B,
+                                           int ids_ld, float noise_scale, float length_scale, const float* noise, int noise_ld,
+                                           uint64_t seed, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
+                                           float denoiser_strength, int32_t pad_before, int32_t pad_after, int32_t* frames_out,
+                                           float* wav_f32, int16_t* wav_i16, int64_t wav_ld, uint32_t flags,
+                                           const mi355tts_prosody* prosody) {
+  return synthesize_impl(ctx, glow, vocoder, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, speaker_ids, audio,
+                         denoiser_strength, pad_before, pad_after, frames_out, wav_f32, wav_i16, wav_ld, flags, prosody);
 }
 
 // Pre-create `workers` workers (streams, pinned staging, side streams) and size their

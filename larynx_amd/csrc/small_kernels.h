@@ -532,8 +532,15 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const float* qkv, l
 // G9a: durations.  w = exp(logw)*length_scale, w_ceil = ceil(w); cum = inclusive
 // cumsum; frames = max(sum,1) truncated to a multiple of n_sqz
 // (glow_tts/models.py:323-336).  One workgroup per batch row.
+// Prosody (all three optional; all null = the plain path):
+//   id_scales[B][in_ld]     w = (exp(logw)*length_scale) * id_scales[t]: a rate per id (1.0f: today's duration, 0: no frames)
+//   durations_in[B][in_ld]  stands in for ceil(w) (logw, length_scale and id_scales are then not read)
+//   durations_out[B][out_ld] what the reference's attn[b, 0, t, :].sum() is (models.py:329-335, :350-354): the frames id t
+//                            keeps once the path is masked to the row's final frame count F — min(cum[t], F) - min(cum[t-1], F),
+//                            0 past the row's length
 __global__ void duration_kernel(const float* logw, long long bs, const int* len, float length_scale, int n_sqz,
-                                int* cum, int cum_ld, int* frames, int max_frames_cap) {
+                                int* cum, int cum_ld, int* frames, int max_frames_cap, const float* id_scales,
+                                const int* durations_in, int in_ld, int* durations_out, int out_ld) {
   GLOW_PRIO();
   // one wave per row: lane l owns the contiguous run [l*per, (l+1)*per) of ids, sums its
   // durations, the 64 run totals are scanned with __shfl_up, and the run is walked a second
@@ -547,8 +554,16 @@ __global__ void duration_kernel(const float* logw, long long bs, const int* len,
   const int t0 = lane * per;
   const int t1 = t0 + per < P ? t0 + per : P;
   const float* lw = logw + (long long)b * bs;
+  const float* sc = id_scales ? id_scales + (long long)b * in_ld : nullptr;
+  const int* din = durations_in ? durations_in + (long long)b * in_ld : nullptr;
   const float capf = (float)max_frames_cap;  // <= 2^28: two capped terms still fit an int
-  auto dur = [&](int t) { return (int)fminf(fmaxf(ceilf(expf(lw[t]) * length_scale), 0.f), capf); };
+  // (the pointers are kernel arguments: both branches are uniform over the wave)
+  auto dur = [&](int t) {
+    if (din) return din[t] < 0 ? 0 : din[t] < max_frames_cap ? din[t] : max_frames_cap;
+    float w = expf(lw[t]) * length_scale;
+    if (sc) w = w * sc[t];
+    return (int)fminf(fmaxf(ceilf(w), 0.f), capf);
+  };
   // the scan runs UNCLAMPED in 64 bits (exact for any input: <= 2^28 per id) and only what is written is capped, so
   // cum[] stays monotone also when the sum overflows the cap (the call then fails with NOMEM on the host side)
   long long run = 0;
@@ -567,11 +582,23 @@ __global__ void duration_kernel(const float* logw, long long bs, const int* len,
   }
   const long long total64 = ((long long)__shfl((unsigned)(incl >> 32), 63) << 32) | (long long)__shfl((unsigned)(incl & 0xffffffffLL), 63);
   const int total = (int)(total64 < (long long)max_frames_cap ? total64 : (long long)max_frames_cap);
-  if (lane == 0) {
-    int y = total > 1 ? total : 1;
-    y = (y / n_sqz) * n_sqz;
-    if (y > max_frames_cap) y = (max_frames_cap / n_sqz) * n_sqz;
-    frames[b] = y;
+  // every lane knows the total: the row's final frame count in all of them
+  int y = total > 1 ? total : 1;
+  y = (y / n_sqz) * n_sqz;
+  if (y > max_frames_cap) y = (max_frames_cap / n_sqz) * n_sqz;
+  if (lane == 0) frames[b] = y;
+  if (durations_out) {  // uniform; a third walk of the lane's run, no shuffle inside
+    int* dout = durations_out + (long long)b * out_ld;
+    const long long F = y;
+    long long a2 = incl - run;
+    long long prev = a2 < F ? a2 : F;
+    for (int t = t0; t < t1; ++t) {
+      a2 += dur(t);
+      const long long cur = a2 < F ? a2 : F;
+      dout[t] = (int)(cur - prev);
+      prev = cur;
+    }
+    for (int t = P + lane; t < out_ld; t += 64) dout[t] = 0;
   }
 }
 

@@ -20,9 +20,11 @@ class MelBatch:
     round trip (the reference crosses host<->runtime twice per sentence,
     `larynx/__init__.py:231-256`)."""
 
-    def __init__(self, engine: "Engine", handle: int):
+    def __init__(self, engine: "Engine", handle: int, durations_ld: int = 0):
         self._engine = engine
         self._h = C.c_void_p(handle)
+        self._durations: typing.Optional[np.ndarray] = None  # fetched on first use
+        self._durations_ld = int(durations_ld)
         engine._live_mels.add(self)
         lib = engine.lib
         self.batch = ffi.check(lib, lib.mi355tts_mel_batch(self._h))
@@ -50,6 +52,20 @@ class MelBatch:
     @property
     def shape(self):
         return (self.batch, self.channels, self.max_frames)
+
+    @property
+    def durations(self) -> np.ndarray:
+        """[B, P] int32: the mel frames every phoneme id occupies (the reference's `attn.sum(-1)`,
+        glow_tts/models.py:350-354), zeros past a row's length; row b sums to `frames[b]`.  Only a mel made with
+        `want_durations`, `id_scales` or `durations` carries them: anything else (a wrapped array) raises ValueError."""
+        if self._durations is None:
+            P = self._durations_ld
+            out = np.zeros((self.batch, max(P, 1)), np.int32)
+            lib = self._engine.lib
+            if lib.mi355tts_mel_durations(self.handle, out.ctypes.data_as(C.POINTER(C.c_int32)), out.shape[1]) < 0:
+                raise ValueError("this mel batch carries no durations (ask for them: want_durations=True)")
+            self._durations = out[:, :P]
+        return self._durations
 
     def __array__(self, dtype=None, copy=None):
         a = self.numpy("raw")
@@ -155,6 +171,9 @@ class Engine:
         audio_settings=None,
         row_seeds: typing.Optional[typing.Sequence[int]] = None,
         speaker_ids: typing.Union[None, int, typing.Sequence[int]] = None,
+        id_scales=None,
+        durations=None,
+        want_durations: bool = False,
     ) -> MelBatch:
         """`ids`: one int64 vector [P] or a list of them (variable length batch).
         `speaker_ids`: a multi-speaker voice's speaker per row (one int = every row; the reference's `speaker_id`
@@ -162,7 +181,11 @@ class Engine:
         `noise`: optional [B, M, >=F] (or [M, >=F] for B=1) standing in for the
         reference's `torch.randn_like` draw.  Without it the device generator draws: row b from
         the stream `row_seeds[b]` (default `seed + b`: successive BATCHED calls must advance `seed` by the batch size)
-        — the field a batch-1 call with that seed draws."""
+        — the field a batch-1 call with that seed draws.
+        `id_scales`: a duration factor per id ([P] floats, or one vector per row): `ceil(exp(logw) * length_scale * scale)`;
+        1.0 changes nothing, 0 gives the id no frames.  `durations`: the frames per id outright ([P] ints or one vector
+        per row), instead of the duration predictor's.  Either of them, or `want_durations`, makes `MelBatch.durations`
+        available."""
         rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
         if isinstance(ids, np.ndarray) and ids.ndim == 2:
             rows = [np.asarray(r, np.int64) for r in ids]
@@ -184,6 +207,22 @@ class Engine:
         out = C.c_void_p()
         if row_seeds is not None and (noise is not None or len(row_seeds) != B):
             raise ValueError("row_seeds: one seed per row, and no explicit noise")
+        if id_scales is not None or durations is not None or want_durations:
+            pros, keep = self._prosody(lens, packed.shape[1], id_scales, durations, False)
+            spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
+            rs = None if row_seeds is None else np.array([int(x) & (2 ** 64 - 1) for x in row_seeds], np.uint64)
+            ffi.check(
+                self.lib,
+                self.lib.mi355tts_glow_infer_prosody(
+                    self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, packed.shape[1],
+                    float(noise_scale), float(length_scale), nz_ptr, nz_ld, int(seed) & (2 ** 64 - 1),
+                    rs.ctypes.data_as(C.POINTER(C.c_uint64)) if rs is not None else None,
+                    spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
+                    C.byref(a) if a is not None else None, 0, C.byref(pros), C.byref(out),
+                ),
+            )
+            del keep
+            return MelBatch(self, out.value, durations_ld=packed.shape[1])
         if speaker_ids is not None:
             spk = self._speaker_array(speaker_ids, B)
             rs = None if row_seeds is None else np.array([int(x) & (2 ** 64 - 1) for x in row_seeds], np.uint64)
@@ -217,6 +256,33 @@ class Engine:
             ),
         )
         return MelBatch(self, out.value)
+
+    @staticmethod
+    def _prosody(lens: np.ndarray, ld: int, id_scales, durations, want_out: bool):
+        """The `mi355tts_prosody` of a call and the arrays it points into (keep them alive until the call returns;
+        the last one is the durations_out array or None)."""
+        B = len(lens)
+
+        def pack(v, dtype, name):
+            if v is None:
+                return None
+            rows = [np.asarray(v, dtype)] if B == 1 and np.ndim(v[0]) == 0 else [np.asarray(r, dtype) for r in v]
+            if len(rows) != B or any(r.ndim != 1 or len(r) != n for r, n in zip(rows, lens)):
+                raise ValueError(f"{name}: one value per phoneme id of every row")
+            out = np.zeros((B, ld), dtype)
+            for b, r in enumerate(rows):
+                out[b, : len(r)] = r
+            return out
+
+        sc = pack(id_scales, np.float32, "id_scales")
+        din = pack(durations, np.int32, "durations")
+        dout = np.zeros((B, ld), np.int32) if want_out else None
+        p = ffi.ProsodyC()
+        p.id_scales = sc.ctypes.data_as(C.POINTER(C.c_float)) if sc is not None else None
+        p.durations_in = din.ctypes.data_as(C.POINTER(C.c_int32)) if din is not None else None
+        p.durations_out = dout.ctypes.data_as(C.POINTER(C.c_int32)) if dout is not None else None
+        p.ld = ld
+        return p, (sc, din, dout)
 
     @staticmethod
     def _speaker_array(speaker_ids, B: int) -> np.ndarray:
@@ -267,8 +333,10 @@ class Engine:
     def synthesize(self, glow: int, vocoder: int, ids, noise_scale: float = 0.667, length_scale: float = 1.0,
                    noise: typing.Optional[np.ndarray] = None, seed: int = 0, audio_settings=None,
                    denoiser_strength: float = 0.0, pad_before: int = 0, pad_after: int = 0, want_float: bool = False,
-                   frames_per_id_guess: float = 8.0, speaker_ids: typing.Union[None, int, typing.Sequence[int]] = None):
-        """ids -> (frames [B], wav_f32 [B, n] or None, wav_i16 [B, n]) through ONE fused call
+                   frames_per_id_guess: float = 8.0, speaker_ids: typing.Union[None, int, typing.Sequence[int]] = None,
+                   id_scales=None, durations=None, return_durations: bool = False):
+        """ids -> (frames [B], wav_f32 [B, n] or None, wav_i16 [B, n]) through ONE fused call; with `return_durations` a
+        fourth item, the frames per phoneme id [B, P] int32 (see `glow_infer` for `id_scales` / `durations`)
         (`mi355tts_synthesize`): row b holds pad_before zeros, frames[b]*hop samples, then zeros.
         The frame count is data dependent; the output buffer is sized from a guess and the call
         is repeated once with the exact size in the rare case the guess was too small."""
@@ -288,6 +356,11 @@ class Engine:
         hop = self.hop(vocoder)
         pads = int(pad_before) + int(pad_after)
         cap = int(ld * frames_per_id_guess * max(length_scale, 0.05)) * hop + pads
+        pros = keep = None
+        if id_scales is not None or durations is not None or return_durations:
+            pros, keep = self._prosody(lens, ld, id_scales, durations, return_durations)
+            if durations is not None:  # the frame count is known: no guessing
+                cap = max(int(keep[1].sum(axis=1).max()), 1) * hop + pads
         lens_c = lens.ctypes.data_as(C.POINTER(C.c_int32))
         a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
         frames = np.zeros(B, np.int32)
@@ -299,7 +372,10 @@ class Engine:
                     nz_ld, int(seed) & (2 ** 64 - 1))
             tail = (C.byref(a) if a is not None else None, float(denoiser_strength), int(pad_before), int(pad_after),
                     frames.ctypes.data_as(C.POINTER(C.c_int32)), ffi.ptr(f32), i16.ctypes.data, cap, 0)
-            if spk is not None:
+            if pros is not None:
+                rc = self.lib.mi355tts_synthesize_prosody(*head, spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
+                                                          *tail, C.byref(pros))
+            elif spk is not None:
                 rc = self.lib.mi355tts_synthesize_speakers(*head, spk.ctypes.data_as(C.POINTER(C.c_int32)), *tail)
             else:
                 rc = self.lib.mi355tts_synthesize(*head, *tail)
@@ -308,7 +384,8 @@ class Engine:
                 cap = n
                 continue
             ffi.check(self.lib, rc)
-            return frames, (f32[:, :n] if f32 is not None else None), i16[:, :n]
+            res = (frames, (f32[:, :n] if f32 is not None else None), i16[:, :n])
+            return res + (keep[2],) if return_durations else res
         raise AssertionError("unreachable")
 
     def reserve(self, workers: int, glow: int = 0, vocoder: int = 0, max_batch: int = 1, max_ids: int = 256,

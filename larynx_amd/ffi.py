@@ -76,6 +76,13 @@ class GriffinLimParamsC(C.Structure):
     _fields_ = [("num_mels", C.c_int32), ("mel_scaling", C.c_float), ("iterations", C.c_int32)]
 
 
+class ProsodyC(C.Structure):
+    """`mi355tts_prosody`: host arrays [B][ld] (or NULL): a rate per id, durations in, durations out."""
+
+    _fields_ = [("id_scales", C.POINTER(C.c_float)), ("durations_in", C.POINTER(C.c_int32)),
+                ("durations_out", C.POINTER(C.c_int32)), ("ld", C.c_int32)]
+
+
 class Mi355ttsError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"mi355tts error {code}: {message}")
@@ -111,6 +118,12 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
         [_VP, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,
          C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(AudioSettingsC), C.c_uint32, C.POINTER(_VP)],
     ),
+    "mi355tts_glow_infer_prosody": (
+        C.c_int,
+        [_VP, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,
+         C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(AudioSettingsC), C.c_uint32, C.POINTER(ProsodyC), C.POINTER(_VP)],
+    ),
+    "mi355tts_mel_durations": (C.c_int, [_VP, C.POINTER(C.c_int32), C.c_int]),
     "mi355tts_mel_batch": (C.c_int, [_VP]),
     "mi355tts_mel_channels": (C.c_int, [_VP]),
     "mi355tts_mel_max_frames": (C.c_int, [_VP]),
@@ -136,6 +149,12 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
         [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,
          C.POINTER(C.c_int32), C.POINTER(AudioSettingsC), C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _VP, _VP,
          C.c_int64, C.c_uint32],
+    ),
+    "mi355tts_synthesize_prosody": (
+        C.c_int,
+        [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,
+         C.POINTER(C.c_int32), C.POINTER(AudioSettingsC), C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _VP, _VP,
+         C.c_int64, C.c_uint32, C.POINTER(ProsodyC)],
     ),
     "mi355tts_reserve": (C.c_int, [_VP] + [C.c_int] * 8),
     "mi355tts_worker_queue_groups": (C.c_int, [_VP, C.POINTER(C.c_int32), C.c_int]),

@@ -36,7 +36,11 @@ class HipGlowTextToSpeech(TextToSpeechModel):
     * extra settings `noise` (explicit N(0,1) tensor `[80, >=F]`, the parity mode)
       and `seed` (device RNG; default: a fresh seed per call, as the reference draws
       fresh noise per call) — the reference's noise is not reproducible from the
-      host (`torch.randn_like`, `glow_tts/models.py:348`).
+      host (`torch.randn_like`, `glow_tts/models.py:348`);
+    * extra settings for timing: `id_length_scales` (P floats, a `length_scale` per phoneme id on top of the global
+      one; 0 drops the id), `durations` (P ints: the mel frames of every id outright, e.g. an earlier take's
+      `MelBatch.durations`; excludes `id_length_scales`) and `alignment` (truthy: only keep the timings).  With any of
+      them the returned `MelBatch.durations` holds the frames every id occupies (`larynx_amd.alignment`).
     """
 
     def __init__(self, config: TextToSpeechModelConfig, device: int = 0, library_path=None, state_dict=None,
@@ -93,7 +97,12 @@ class HipGlowTextToSpeech(TextToSpeechModel):
         noise_scale, length_scale = self.noise_scale, self.length_scale
         noise, seed = None, None
         speaker_idx: typing.Optional[int] = None
+        id_scales = durations = None
+        want_durations = False
         if settings:
+            id_scales = settings.get("id_length_scales")
+            durations = settings.get("durations")
+            want_durations = bool(settings.get("alignment")) or id_scales is not None or durations is not None
             noise_scale = float(settings.get("noise_scale", noise_scale))
             length_scale = float(settings.get("length_scale", length_scale))
             speaker_idx = settings.get("speaker_id")  # larynx/glow_tts.py:121
@@ -108,6 +117,9 @@ class HipGlowTextToSpeech(TextToSpeechModel):
         return self.engine.glow_infer(
             self.model_id, ids, noise_scale, length_scale, noise=noise, seed=seed, audio_settings=self._audio_settings,
             speaker_ids=None if speaker_idx is None else int(speaker_idx),
+            id_scales=None if id_scales is None else np.asarray(id_scales, np.float32).reshape(-1),
+            durations=None if durations is None else np.asarray(durations, np.int32).reshape(-1),
+            want_durations=want_durations,
         )
 
 

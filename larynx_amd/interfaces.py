@@ -84,3 +84,6 @@ class TextToSpeechResult:
     sample_rate: int
     marks_before: typing.Optional[typing.Sequence[str]] = None
     marks_after: typing.Optional[typing.Sequence[str]] = None
+    # int64 [P, 2]: start and end sample of every phoneme id in `audio` (larynx_amd.alignment.phoneme_spans); only with
+    # phonemes_to_speech(alignment=True).  Not in the reference's record.
+    phoneme_spans: typing.Optional[np.ndarray] = None
