@@ -1,131 +1,70 @@
 // mi355tts host runtime — mi355tts_glow_infer: the GlowTTS layer schedule (glow_tts/models.py:118-140, :191-209, :308-354)
 // (one translation unit: included once by mi355tts.hip, after the kernel headers)
+// GlowPass (what a run of launches shares; the launch helpers are its members), the call struct, the workspace layouts and their
+// views, the fused launches, then the stages of a pass — encoder, durations, decoder (a function per flow block) — and glow_run.
 #pragma once
 
 // ------------------------------------------------------------------ GlowTTS forward
-static int run_layernorm(Worker* w, const float* x, const float* res, const float* g, const float* b, float* y, int C,
-                         long long bs, int ld, const int* len, int B, int Pmax, int post_relu) {
-  if (C <= 256)
-    hipLaunchKernelGGL(layernorm16_kernel, dim3((Pmax + 15) / 16, B), dim3(256), 0, w->stream, x, res, g, b, y, C, bs, ld, len, 0,
-                       post_relu, 1e-4f);
-  else
-    hipLaunchKernelGGL(layernorm_kernel, dim3((Pmax + 63) / 64, B), dim3(256), 0, w->stream, x, res, g, b, y, C, bs, ld, len, 0,
-                       post_relu, 1e-4f);
-  return 0;
-}
-
-// ---- column-owner launches (coltile.h).  Each returns 1 when the shape is not one the kernel takes (the caller then runs
-// the separate launches), 0 when launched.
 static bool glow_fuse_on(const Worker* w) { return !w->opt.env.glow_fuse_off && w->opt.glow_fuse; }
-static int run_oproj_ln(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const GlowLayer& L, const float* att, float* x, int H,
-                        long long bs, int ld, const int* d_len, int host_len, int B, int Pmax) {
-  if (!glow_fuse_on(w) || !L.o16.ok || H > COL_MAXROWS || ld % 4 || Pmax <= 0) return 1;
-  const float* A = gm->arena;
-  OprojLnArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.x = att; a.res = x; a.y = x; a.bs = bs; a.ld = ld;
-  if (B == 1 && host_len >= 0) { a.len = nullptr; a.len_const = host_len; } else { a.len = d_len; }
-  a.len_mul = 1;
-  a.w = A + L.o16.w_off; a.b = A + L.o16.b_off; a.gamma = A + L.g1; a.beta = A + L.b1;
-  a.H = H; a.eps = 1e-4f;
-  ProfScope ps(ctx, w, KC_GLOW_ENC_CONV, 2.0 * (double)H * H * (double)Pmax * B);
-  kn_hit(ctx, KN_OPROJ_LN);
-  hipLaunchKernelGGL(oproj_ln_kernel, dim3((Pmax + COL_T - 1) / COL_T, B), dim3(512), 0, w->stream, a);
-  return 0;
-}
-// the tail of block `Bk` and the start of `next` (nullptr after the last block in reverse order)
-static int run_glow_tail(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const GlowBlock& Bk, const GlowBlock* next, const float* acts,
-                         const float* skip, float* hbuf, long long bsD, float* z, long long bsZ, int F2, const int* d_f2, int host_len,
-                         int B, int F2max) {
-  const mi355tts_glow_hparams& h = gm->hp;
-  const int H = h.hidden_channels, half = h.mel_channels * h.n_sqz / 2;
-  if (!glow_fuse_on(w) || !Bk.t_rs.ok || !Bk.t_end.ok || !Bk.t_st.ok || (next && !next->t_st.ok) || h.n_split != 4 || (half % 2) || F2 % 4 ||
-      F2max <= 0)
-    return 1;
-  const float* A = gm->arena;
-  GlowTailArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.acts = acts; a.skip = h.n_block_layers > 1 ? skip : nullptr; a.hnext = next ? hbuf : nullptr; a.h_bs = bsD; a.h_ld = F2;
-  a.z = z; a.z_bs = bsZ; a.z_ld = F2;
-  if (B == 1 && host_len >= 0) { a.len = nullptr; a.len_const = host_len; } else { a.len = d_f2; }
-  a.len_mul = 1;
-  a.w_rs = A + Bk.t_rs.w_off; a.b_rs = A + Bk.t_rs.b_off;
-  a.w_end = A + Bk.t_end.w_off; a.b_end = A + Bk.t_end.b_off;
-  const GlowBlock& stb = next ? *next : Bk;  // the last block has no successor: its own start stands in (loaded, never used)
-  a.w_st = A + stb.t_st.w_off; a.b_st = A + stb.t_st.b_off;
-  a.mix_w = A + Bk.winv; a.mix_bias = A + Bk.an_bias; a.mix_scale = A + Bk.an_scale;
-  a.H = H; a.half = half;
-  const double mac = (double)H * H + 2.0 * half * H + (next ? (double)H * half : 0.0);
-  ProfScope ps(ctx, w, KC_GLOW_DEC_CONV, 2.0 * mac * (double)F2max * B);
-  kn_hit(ctx, KN_GLOW_TAIL);
-  hipLaunchKernelGGL(glow_tail_kernel, dim3((F2max + COL_T - 1) / COL_T, B), dim3(512), 0, w->stream, a);
-  return 0;
-}
 
-// the fp16 mode's WaveNet of block `Bk` (wn_f16.h): every layer's gate conv and res_skip but the last res_skip in ONE launch;
-// leaves `acts` (last layer's gated activations) and `skip` (layers 0 .. n - 2) as the f32 chain would.  1 = not taken.
-static int run_wn_f16(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const GlowBlock& Bk, const float* hcur, float* acts, float* skip,
-                      long long bsD, int F2, const int* d_f2, int host_len, int B, int F2max) {
-  const mi355tts_glow_hparams& h = gm->hp;
-  const int H = h.hidden_channels, n = h.n_block_layers;
-  if (!gm->f16_ok || (int)Bk.h_in.size() != n || (int)Bk.h_rs.size() != n - 1 || F2max <= 0 || (H != 192 && H != 32)) return 1;
-  WnF16Args a;
-  std::memset(&a, 0, sizeof(a));
-  a.h = hcur; a.bs = bsD; a.ld = F2;
-  if (B == 1 && host_len >= 0) { a.len = nullptr; a.len_const = host_len; } else { a.len = d_f2; }
-  for (int j = 0; j < n; ++j) {
-    a.w_in[j] = Bk.h_in[j].w; a.b_in[j] = Bk.h_in[j].bias;
-    if (j < n - 1) { a.w_rs[j] = Bk.h_rs[j].w; a.b_rs[j] = Bk.h_rs[j].bias; }
+// What is constant over a run of GlowTTS launches; one instance serves the encoder, one the decoder.  A launch helper then
+// takes only what differs per launch: the conv, its ConvArgs, the norm's parameters.
+struct GlowPass {
+  mi355tts_ctx* ctx;
+  Worker* w;
+  const GlowModel* gm;
+  const float* A;  // gm->arena
+  hipStream_t s;
+  int B, n_max, ld;  // rows, the longest row (Pmax / F2max), the row stride of every activation
+  const int* d_len;  // device, [B]
+  int host_len;      // the row's length at batch 1, else -1
+  int glow_tiles;    // workgroup target per conv launch (tile-shape choice; tuning knob MI355TTS_GLOW_TILES)
+  // every launch on the smallest tile whatever the batch size, so that a row of a coalesced pass would be computed by exactly
+  // the launches of its own batch-1 call.  No caller sets it (profiles/NOTES.md, open items).
+  bool solo_tiles;
+  int cls;  // profile class: KC_GLOW_ENC_CONV / KC_GLOW_DEC_CONV
+
+  RowLen rows() const { return row_len(B, host_len, d_len); }
+  ProfScope small() const { return ProfScope(ctx, w, KC_SMALL, 0); }
+  // a conv over this pass's activations: x [B][.][ld] -> y [B][.][ld]
+  ConvArgs args(const float* x, long long x_bs, float* y, long long y_bs, int dil = 1, int pad = 0) const {
+    return base_args(x, x_bs, ld, d_len, 1, y, y_bs, ld, d_len, 1, dil, pad);
   }
-  a.n_layers = n;
-  a.margin = (h.kernel_size_dec - 1) / 2 * n;
-  a.acts = acts; a.skip = skip;
-  const int to = WN_W - 2 * a.margin;
-  const dim3 grid((F2max + to - 1) / to, B);
-  const double mac = (double)n * 2.0 * H * H * h.kernel_size_dec + (double)(n - 1) * 2.0 * H * H;
-  ProfScope ps(ctx, w, KC_GLOW_DEC_CONV, 2.0 * mac * (double)F2max * B);
-  // MI355TTS_WN_REPEAT (probe): the launch N times — it is idempotent; run 2 .. N find the block's weights in L2
-  const int repeat = std::max(1, w->opt.env.wn_repeat);
-  for (int r = 0; r < repeat; ++r) {
-    if (H == 192)
-      hipLaunchKernelGGL((wn_f16_kernel<5, 24, 3, 10>), grid, dim3(256), 0, w->stream, a);
+  int conv(const DevConv& c, const ConvArgs& a, int epi = EPI_LINEAR) const {
+    return launch_conv(ctx, w, c, a, epi, B, n_max, cls, nullptr, glow_tiles, host_len);
+  }
+  int lin16(const DevConv& c, const ConvArgs& a, const Lin16Ln* ln = nullptr) const {
+    return run_lin16(ctx, w, c, a, A, B, n_max, cls, host_len, solo_tiles, ln);
+  }
+  int gate16(const DevConv& c, const ConvArgs& a) const { return run_gate16(ctx, w, c, a, B, n_max, cls, s); }
+
+  void layernorm(const float* x, const float* g, const float* b, float* y, int C, long long bs, int post_relu) const {
+    ProfScope ps = small();
+    const float* res = nullptr;
+    if (C <= 256)
+      hipLaunchKernelGGL(layernorm16_kernel, dim3((n_max + 15) / 16, B), dim3(256), 0, s, x, res, g, b, y, C, bs, ld, d_len, 0, post_relu,
+                         1e-4f);
     else
-      hipLaunchKernelGGL((wn_f16_kernel<5, 4, 1, 6>), grid, dim3(256), 0, w->stream, a);
+      hipLaunchKernelGGL(layernorm_kernel, dim3((n_max + 63) / 64, B), dim3(256), 0, s, x, res, g, b, y, C, bs, ld, d_len, 0, post_relu,
+                         1e-4f);
   }
-  kn_hit(ctx, KN_WN_F16);
-  return 0;
-}
-
-// LayerNorm -> [ReLU] -> conv with the norm inside the conv launch (lin16_kernel's LN prologue) when the shape has one;
-// otherwise the LayerNorm launch (raw -> normed) and the conv on its output.  `normed` may be nullptr when nothing else
-// reads the normalised tensor AND the fused form is taken; the fallback needs a buffer: `scratch`.
-static int launch_ln_conv(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const DevConv& c, ConvArgs a, const float* raw, float* normed,
-                          float* scratch, const float* gamma, const float* beta, int relu, int C, long long bs, int ld, const int* d_len,
-                          int B, int Pmax, int glow_tiles, int host_len, bool solo_tiles);
-
-// an encoder conv: the 16-row tile with the input staged once when the shape has one (lin16_kernel), else the generic tile
-static int launch_enc_conv(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const DevConv& c, const ConvArgs& a, int B, int Pmax,
-                           int glow_tiles, int host_len, bool solo_tiles = false) {
-  if (run_lin16(ctx, w, c, a, gm->arena, B, Pmax, KC_GLOW_ENC_CONV, host_len, solo_tiles) == 0) return 0;
-  return launch_conv(ctx, w, c, a, EPI_LINEAR, B, Pmax, KC_GLOW_ENC_CONV, nullptr, glow_tiles, host_len);
-}
-
-static int launch_ln_conv(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const DevConv& c, ConvArgs a, const float* raw, float* normed,
-                          float* scratch, const float* gamma, const float* beta, int relu, int C, long long bs, int ld, const int* d_len,
-                          int B, int Pmax, int glow_tiles, int host_len, bool solo_tiles) {
-  if (!w->opt.env.lin16_no_ln && glow_fuse_on(w)) {
-    Lin16Ln ln{gamma, beta, relu, normed};
-    a.x = raw;
-    if (run_lin16(ctx, w, c, a, gm->arena, B, Pmax, KC_GLOW_ENC_CONV, host_len, solo_tiles, &ln) == 0) return 0;
+  // an encoder conv: the 16-row tile with the input staged once when the shape has one (lin16_kernel), else the generic tile
+  int enc_conv(const DevConv& c, const ConvArgs& a) const {
+    if (lin16(c, a) == 0) return 0;
+    return conv(c, a);
   }
-  float* dst = normed ? normed : scratch;
-  {
-    ProfScope ps(ctx, w, KC_SMALL, 0);
-    run_layernorm(w, raw, nullptr, gamma, beta, dst, C, bs, ld, d_len, B, Pmax, relu);
+  // LayerNorm -> [ReLU] -> conv with the norm inside the conv launch (lin16_kernel's LN prologue) when the shape has one;
+  // otherwise the LayerNorm launch (raw -> normed) and the conv on its output.  a.x is the raw tensor; ln.out (where the
+  // normalised tensor is also stored) may be nullptr when nothing else reads it AND the fused form is taken; the fallback needs
+  // a buffer: `scratch`.
+  int ln_conv(const DevConv& c, ConvArgs a, const Lin16Ln& ln, float* scratch) const {
+    if (!w->opt.env.lin16_no_ln && glow_fuse_on(w) && lin16(c, a, &ln) == 0) return 0;
+    float* dst = ln.out ? ln.out : scratch;
+    layernorm(a.x, ln.gamma, ln.beta, dst, c.Cin, a.x_bs, ln.relu);
+    a.x = dst;
+    return enc_conv(c, a);
   }
-  a.x = dst;
-  return launch_enc_conv(ctx, w, gm, c, a, B, Pmax, glow_tiles, host_len, solo_tiles);
-}
+};
 
 struct GlowCall {
   const int64_t* ids = nullptr;
@@ -141,7 +80,8 @@ struct GlowCall {
   // ids + b * ids_ld — the rows of a coalesced pass come from different callers (host_join.h)
   const int64_t* const* row_ids = nullptr;
   // every launch on the smallest tile whatever the batch size: what a batch-1 call uses up to ~5000 decoder columns, so
-  // a row of a coalesced pass is computed by exactly the launches (and summation orders) of its own batch-1 call
+  // a row of a coalesced pass would be computed by exactly the launches (and summation orders) of its own batch-1 call
+  // (GlowPass::solo_tiles; no caller sets it)
   bool solo_tiles = false;
   const mi355tts_audio_settings* audio = nullptr;
   uint32_t flags = 0;
@@ -221,6 +161,9 @@ static int glow_precheck(const GlowModel* gm, const GlowCall& c, int* Pmax_out) 
 // Encoder workspace of one call: ONE definition for the forward pass and mi355tts_reserve.
 struct GlowEncLayout {
   size_t o_len, o_seed, o_ids, o_x, o_t1, o_t2, o_qkv, o_ffn, o_xm, o_logw, o_cum, o_sc, o_spk, o_cond, o_dps, total;
+  // a call's id_scales or durations_in (one of them, 4-byte entries, row stride P) sit right behind the region, where the decoder's
+  // workspace is appended later: duration_kernel has consumed them by then.  Not part of `total`: no other call's layout changes.
+  size_t o_pros, pros_end;
   int P, att_rows;
 };
 static GlowEncLayout glow_enc_layout(const mi355tts_glow_hparams& h, int B, int ids_ld, int Pmax) {
@@ -250,6 +193,8 @@ static GlowEncLayout glow_enc_layout(const mi355tts_glow_hparams& h, int B, int 
   L.o_cond = cv.take(spk ? sizeof(float) * (size_t)B * h.n_blocks_dec * 2 * H * h.n_block_layers : 0);
   L.o_dps = cv.take(spk ? sizeof(float) * (size_t)B * Fd * h.kernel_size : 0);
   L.total = cv.pos;
+  L.o_pros = cv.take(0);
+  L.pros_end = L.o_pros + sizeof(float) * (size_t)B * P;
   return L;
 }
 struct GlowDecLayout {
@@ -270,264 +215,350 @@ static GlowDecLayout glow_dec_layout(const mi355tts_glow_hparams& h, size_t enc_
   return L;
 }
 
-// The forward pass on worker `w`.  With `final_sync` false the mel object is returned while
-// its last kernels are still queued on w->stream (the fused synthesize path launches the
-// vocoder behind them on the same stream).
-static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const GlowCall& call, int Pmax, bool final_sync,
-                    mi355tts_mel** out) {
-  const mi355tts_glow_hparams& h = gm->hp;
-  const int64_t* ids = call.ids;
-  const int32_t* id_lens = call.id_lens;
+// The layouts bound to an arena: EVERY buffer, so that a pass which re-binds after the arena moved cannot miss one.
+struct GlowEncView {
+  int* len;
+  unsigned long long* seeds;
+  long long* ids;
+  float *x, *t1, *t2, *qkv, *ffn, *xm, *logw;
+  int* cum;
+  float* sc;
+  int* spk;
+  float *cond, *dps;
+  void* pros;
+};
+static GlowEncView glow_enc_view(const GlowEncLayout& L, char* base) {
+  auto f = [&](size_t off) { return (float*)(base + off); };
+  auto i = [&](size_t off) { return (int*)(base + off); };
+  return {i(L.o_len), (unsigned long long*)(base + L.o_seed), (long long*)(base + L.o_ids), f(L.o_x), f(L.o_t1), f(L.o_t2), f(L.o_qkv), f(L.o_ffn),
+          f(L.o_xm), f(L.o_logw), i(L.o_cum), f(L.o_sc), i(L.o_spk), f(L.o_cond), f(L.o_dps), base + L.o_pros};
+}
+struct GlowDecView {
+  float *z, *h, *acts, *skip, *nz;
+};
+static GlowDecView glow_dec_view(const GlowDecLayout& L, char* base) {
+  auto f = [&](size_t off) { return (float*)(base + off); };
+  return {f(L.o_z), f(L.o_h), f(L.o_ac), f(L.o_sk), f(L.o_nz)};
+}
+
+// drops a mel on an error exit: its blocks go back to the pool, so nothing queued on the stream may still read or write them
+struct MelDrop {
+  hipStream_t st;
+  mi355tts_mel* m;
+  ~MelDrop() {
+    if (!m) return;
+    mi355_sync(st);
+    mel_destroy(m);
+  }
+};
+
+// One forward pass on worker `w`: what its stages share.
+struct GlowRun {
+  mi355tts_ctx* ctx;
+  Worker* w;
+  const GlowModel* gm;
+  const GlowCall& call;
+  int Pmax;
+  int glow_tiles;
+  GlowEncLayout el;
+  GlowEncView ev;
+  mi355tts_mel* mel;
+  GlowPass pass(int n_max, int ld, const int* d_len, int host_len, int cls) const {
+    return {ctx, w, gm, gm->arena, w->stream, call.B, n_max, ld, d_len, host_len, glow_tiles, call.solo_tiles, cls};
+  }
+};
+
+// ---- column-owner launches (coltile.h).  Each returns 1 when the shape is not one the kernel takes (the caller then runs
+// the separate launches), 0 when launched.
+// conv_o + residual + LayerNorm of encoder layer `L`: x = LayerNorm(x + conv_o(att))
+static int run_oproj_ln(const GlowPass& p, const GlowLayer& L, const float* att, float* x) {
+  const int H = p.gm->hp.hidden_channels;
+  if (!glow_fuse_on(p.w) || !L.o16.ok || H > COL_MAXROWS || p.ld % 4 || p.n_max <= 0) return 1;
+  OprojLnArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.x = att; a.res = x; a.y = x; a.bs = (long long)H * p.ld; a.ld = p.ld;
+  p.rows().into(a);
+  a.len_mul = 1;
+  a.w = p.A + L.o16.w_off; a.b = p.A + L.o16.b_off; a.gamma = p.A + L.g1; a.beta = p.A + L.b1;
+  a.H = H; a.eps = 1e-4f;
+  ProfScope ps(p.ctx, p.w, p.cls, 2.0 * (double)H * H * (double)p.n_max * p.B);
+  kn_hit(p.ctx, KN_OPROJ_LN);
+  hipLaunchKernelGGL(oproj_ln_kernel, dim3((p.n_max + COL_T - 1) / COL_T, p.B), dim3(512), 0, p.s, a);
+  return 0;
+}
+// the tail of block `Bk` and the start of `next` (nullptr after the last block in reverse order)
+static int run_glow_tail(const GlowPass& p, const GlowDecView& dv, const GlowBlock& Bk, const GlowBlock* next) {
+  const mi355tts_glow_hparams& h = p.gm->hp;
+  const int H = h.hidden_channels, half = h.mel_channels * h.n_sqz / 2, F2 = p.ld;
+  if (!glow_fuse_on(p.w) || !Bk.t_rs.ok || !Bk.t_end.ok || !Bk.t_st.ok || (next && !next->t_st.ok) || h.n_split != 4 || (half % 2) || F2 % 4 ||
+      p.n_max <= 0)
+    return 1;
+  const float* A = p.A;
+  GlowTailArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.acts = dv.acts; a.skip = h.n_block_layers > 1 ? dv.skip : nullptr; a.hnext = next ? dv.h : nullptr; a.h_bs = (long long)H * F2; a.h_ld = F2;
+  a.z = dv.z; a.z_bs = (long long)h.mel_channels * h.n_sqz * F2; a.z_ld = F2;
+  p.rows().into(a);
+  a.len_mul = 1;
+  a.w_rs = A + Bk.t_rs.w_off; a.b_rs = A + Bk.t_rs.b_off;
+  a.w_end = A + Bk.t_end.w_off; a.b_end = A + Bk.t_end.b_off;
+  const GlowBlock& stb = next ? *next : Bk;  // the last block has no successor: its own start stands in (loaded, never used)
+  a.w_st = A + stb.t_st.w_off; a.b_st = A + stb.t_st.b_off;
+  a.mix_w = A + Bk.winv; a.mix_bias = A + Bk.an_bias; a.mix_scale = A + Bk.an_scale;
+  a.H = H; a.half = half;
+  const double mac = (double)H * H + 2.0 * half * H + (next ? (double)H * half : 0.0);
+  ProfScope ps(p.ctx, p.w, p.cls, 2.0 * mac * (double)p.n_max * p.B);
+  kn_hit(p.ctx, KN_GLOW_TAIL);
+  hipLaunchKernelGGL(glow_tail_kernel, dim3((p.n_max + COL_T - 1) / COL_T, p.B), dim3(512), 0, p.s, a);
+  return 0;
+}
+
+// the fp16 mode's WaveNet of block `Bk` (wn_f16.h): every layer's gate conv and res_skip but the last res_skip in ONE launch;
+// leaves `acts` (last layer's gated activations) and `skip` (layers 0 .. n - 2) as the f32 chain would.  1 = not taken.
+static int run_wn_f16(const GlowPass& p, const GlowDecView& dv, const GlowBlock& Bk) {
+  const mi355tts_glow_hparams& h = p.gm->hp;
+  const int H = h.hidden_channels, n = h.n_block_layers;
+  if (!p.gm->f16_ok || (int)Bk.h_in.size() != n || (int)Bk.h_rs.size() != n - 1 || p.n_max <= 0 || (H != 192 && H != 32)) return 1;
+  WnF16Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.h = dv.h; a.bs = (long long)H * p.ld; a.ld = p.ld;
+  p.rows().into(a);
+  for (int j = 0; j < n; ++j) {
+    a.w_in[j] = Bk.h_in[j].w; a.b_in[j] = Bk.h_in[j].bias;
+    if (j < n - 1) { a.w_rs[j] = Bk.h_rs[j].w; a.b_rs[j] = Bk.h_rs[j].bias; }
+  }
+  a.n_layers = n;
+  a.margin = (h.kernel_size_dec - 1) / 2 * n;
+  a.acts = dv.acts; a.skip = dv.skip;
+  const int to = WN_W - 2 * a.margin;
+  const dim3 grid((p.n_max + to - 1) / to, p.B);
+  const double mac = (double)n * 2.0 * H * H * h.kernel_size_dec + (double)(n - 1) * 2.0 * H * H;
+  ProfScope ps(p.ctx, p.w, p.cls, 2.0 * mac * (double)p.n_max * p.B);
+  // MI355TTS_WN_REPEAT (probe): the launch N times — it is idempotent; run 2 .. N find the block's weights in L2
+  const int repeat = std::max(1, p.w->opt.env.wn_repeat);
+  for (int r = 0; r < repeat; ++r) {
+    if (H == 192)
+      hipLaunchKernelGGL((wn_f16_kernel<5, 24, 3, 10>), grid, dim3(256), 0, p.s, a);
+    else
+      hipLaunchKernelGGL((wn_f16_kernel<5, 4, 1, 6>), grid, dim3(256), 0, p.s, a);
+  }
+  kn_hit(p.ctx, KN_WN_F16);
+  return 0;
+}
+
+// relative-position attention of layer `L`: qkv -> t2.  The MFMA kernel by head width (NK k-steps, EXACT when they cover it
+// without padding) and by row length (the 256-id LDS layout, or the ATTM_MAXP one); past ATTM_MAXP ids the VALU kernel.
+static void launch_attention(const GlowPass& p, const GlowLayer& L, const GlowEncView& v, int att_rows) {
+  const mi355tts_glow_hparams& h = p.gm->hp;
+  const int H = h.hidden_channels, nh = h.n_heads, P = p.ld, Pmax = p.n_max;
+  const long long bsH = (long long)H * P;
+  ProfScope ps = p.small();
+  kn_hit(p.ctx, KN_ATTENTION);
+  if (Pmax > ATTM_MAXP) {
+    hipLaunchKernelGGL(attention_kernel, dim3(att_rows / ATT_ROWS, nh, p.B), dim3(256), 0, p.s, v.qkv, 3 * bsH, P, p.d_len, H, nh,
+                       h.window_size, p.A + L.ek, p.A + L.ev, v.t2, bsH, P, v.sc, P);
+    return;
+  }
+  const dim3 ag((Pmax + 31) / 32, nh, p.B);
+  const int dkh = H / nh;
+  const int nk = dkh <= 32 ? 16 : dkh <= 64 ? 32 : dkh <= 96 ? 48 : 64;
+  const bool small_lds = Pmax <= 256 && !p.w->opt.env.att_big_lds;  // (A/B runs)
+  auto launch = [&](auto k, auto exact, auto pm) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(attention_mfma_kernel<decltype(k)::value, decltype(exact)::value != 0, decltype(pm)::value>), ag,
+                       dim3(512), 0, p.s, v.qkv, 3 * bsH, P, p.d_len, H, nh, h.window_size, p.A + L.ek, p.A + L.ev, v.t2, bsH, P);
+  };
+  switch_const<16, 32, 48, 64>(nk, [&](auto k) {
+    switch_const<0, 1>(dkh == 2 * nk ? 1 : 0, [&](auto exact) {
+      if (small_lds) launch(k, exact, int_c<256>{});
+      else launch(k, exact, int_c<ATTM_MAXP>{});
+    });
+  });
+}
+
+// ---- stage 1, the encoder (models.py:118-140): uploads, speaker conditioning, embed, prenet, attention layers, proj_m and the
+// duration predictor.  Leaves x_m, logw and everything a later stage reads in r.ev.
+static int glow_enc_upload(GlowRun& r) {
+  const GlowCall& call = r.call;
+  const mi355tts_glow_hparams& h = r.gm->hp;
   const int B = call.B, ids_ld = call.ids_ld;
-  const float noise_scale = call.noise_scale, length_scale = call.length_scale;
-  const float* noise = call.noise;
-  const int noise_ld = call.noise_ld;
-  const uint64_t seed = call.seed;
-  const mi355tts_audio_settings* audio = call.audio;
-  const uint32_t flags = call.flags;
-  hipStream_t s = w->stream;
-  // the `half` switch as this call saw it at its start: the decoder's WaveNets in fp16 (wn_f16.h)
-  const bool glow_f16 = gm->f16_ok && gm->precision.load() == MI355TTS_PRECISION_F16;
-  const float* A = gm->arena;
-  const int H = h.hidden_channels, Fc = h.filter_channels, Fd = h.filter_channels_dp, M = h.mel_channels;
-  const int k = h.kernel_size, nh = h.n_heads;
-  const bool in_dev = (flags & MI355TTS_IN_DEVICE) != 0;
-  const int enc_host_len = B == 1 ? id_lens[0] : -1;
-  // workgroup target per GlowTTS conv launch (tile-shape choice; tuning knob MI355TTS_GLOW_TILES)
-  const int glow_tiles = call.solo_tiles ? (1 << 30) : w->opt.env.glow_tiles > 0 ? w->opt.env.glow_tiles : 1024;
-  {
-    long long sum = 0;
-    for (int b = 0; b < B; ++b) sum += id_lens[b];
-    w->flop_scale = Pmax > 0 ? (double)sum / ((double)B * Pmax) : 1.0;  // ragged batch: count the rows' real ids
-  }
-
-  // ---- encoder workspace
-  const GlowEncLayout el = glow_enc_layout(h, B, ids_ld, Pmax);
-  const int P = el.P;  // row stride
-  const int att_rows = el.att_rows;
-  const size_t enc_bytes = el.total;
-  const size_t o_len = el.o_len, o_xm = el.o_xm, o_cum = el.o_cum;
-  // a call's id_scales or durations_in (one of them, 4-byte entries, row stride P) sit right behind the encoder's region, where
-  // the decoder's workspace is appended later: duration_kernel has consumed them by then.  No other call's layout changes.
+  hipStream_t s = r.w->stream;
+  const bool in_dev = (call.flags & MI355TTS_IN_DEVICE) != 0;
+  // a call's id_scales or durations_in (one of them) sit right behind the encoder's region (GlowEncLayout::o_pros)
   const void* pros_src = call.id_scales ? (const void*)call.id_scales : (const void*)call.durations_in;
-  const size_t o_pros = (enc_bytes + 255) & ~(size_t)255;
-  CHECK(reserve(w, pros_src ? o_pros + sizeof(float) * (size_t)B * P : enc_bytes));
-  char* base = w->arena;
-  int* d_len = (int*)(base + el.o_len);
-  long long* d_ids = (long long*)(base + el.o_ids);
-  float* x = (float*)(base + el.o_x);
-  float* t1 = (float*)(base + el.o_t1);
-  float* t2 = (float*)(base + el.o_t2);
-  float* qkv = (float*)(base + el.o_qkv);
-  float* ffn = (float*)(base + el.o_ffn);
-  float* xm = (float*)(base + el.o_xm);
-  float* logw = (float*)(base + el.o_logw);
-  int* cum = (int*)(base + el.o_cum);
-  float* sc = (float*)(base + el.o_sc);
-
-  HIPCHECK(hipMemcpyAsync(d_len, id_lens, sizeof(int) * B, hipMemcpyHostToDevice, s));
-  unsigned long long* d_seeds = nullptr;
-  if (call.row_seeds) {
-    d_seeds = (unsigned long long*)(base + el.o_seed);
-    HIPCHECK(hipMemcpyAsync(d_seeds, call.row_seeds, sizeof(unsigned long long) * B, hipMemcpyHostToDevice, s));
-  }
+  CHECK(reserve(r.w, pros_src ? r.el.pros_end : r.el.total));
+  r.ev = glow_enc_view(r.el, r.w->arena);
+  const GlowEncView& v = r.ev;
+  HIPCHECK(hipMemcpyAsync(v.len, call.id_lens, sizeof(int) * B, hipMemcpyHostToDevice, s));
+  if (call.row_seeds) HIPCHECK(hipMemcpyAsync(v.seeds, call.row_seeds, sizeof(unsigned long long) * B, hipMemcpyHostToDevice, s));
   if (call.row_ids) {
-    HIPCHECK(hipMemsetAsync(d_ids, 0, sizeof(long long) * (size_t)B * ids_ld, s));
+    HIPCHECK(hipMemsetAsync(v.ids, 0, sizeof(long long) * (size_t)B * ids_ld, s));
     for (int b = 0; b < B; ++b)
-      HIPCHECK(hipMemcpyAsync(d_ids + (size_t)b * ids_ld, call.row_ids[b], sizeof(long long) * (size_t)id_lens[b],
+      HIPCHECK(hipMemcpyAsync(v.ids + (size_t)b * ids_ld, call.row_ids[b], sizeof(long long) * (size_t)call.id_lens[b],
                               in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   } else {
-    HIPCHECK(hipMemcpyAsync(d_ids, ids, sizeof(long long) * (size_t)B * ids_ld, in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(v.ids, call.ids, sizeof(long long) * (size_t)B * ids_ld, in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   }
-
   // prosody inputs go up with the ids
-  void* d_pros = pros_src ? (void*)(base + o_pros) : nullptr;
   if (pros_src)
-    HIPCHECK(hipMemcpy2DAsync(d_pros, sizeof(float) * P, pros_src, sizeof(float) * call.pros_ld, sizeof(float) * Pmax, (size_t)B,
+    HIPCHECK(hipMemcpy2DAsync(v.pros, sizeof(float) * r.el.P, pros_src, sizeof(float) * call.pros_ld, sizeof(float) * r.Pmax, (size_t)B,
                               hipMemcpyHostToDevice, s));
-
   // multi-speaker voices: everything the speaker vector feeds, once per call (small_kernels.h: speaker_cond_kernel)
-  const int gin = gm->gin();
-  const int n2 = 2 * H * h.n_block_layers;  // gate offsets per flow block
-  float* spk_cond = gin ? (float*)(base + el.o_cond) : nullptr;
-  float* spk_dps = gin ? (float*)(base + el.o_dps) : nullptr;
-  if (gin) {
-    int* d_spk = (int*)(base + el.o_spk);
-    HIPCHECK(hipMemcpyAsync(d_spk, call.speaker_ids, sizeof(int) * B, hipMemcpyHostToDevice, s));
-    ProfScope ps(ctx, w, KC_SMALL, 0);
-    hipLaunchKernelGGL(speaker_cond_kernel, dim3(h.n_blocks_dec + 1, B), dim3(256), 0, s, A + gm->emb_g, h.n_speakers, gin, d_spk,
-                       A + gm->cond_w, A + gm->cond_b, h.n_blocks_dec, n2, spk_cond, A + gm->dp_wg, Fd * k, k, spk_dps);
+  if (const int gin = r.gm->gin()) {
+    const float* A = r.gm->arena;
+    const int k = h.kernel_size, n2 = 2 * h.hidden_channels * h.n_block_layers;  // n2: gate offsets per flow block
+    HIPCHECK(hipMemcpyAsync(v.spk, call.speaker_ids, sizeof(int) * B, hipMemcpyHostToDevice, s));
+    ProfScope ps(r.ctx, r.w, KC_SMALL, 0);
+    hipLaunchKernelGGL(speaker_cond_kernel, dim3(h.n_blocks_dec + 1, B), dim3(256), 0, s, A + r.gm->emb_g, h.n_speakers, gin, v.spk,
+                       A + r.gm->cond_w, A + r.gm->cond_b, h.n_blocks_dec, n2, v.cond, A + r.gm->dp_wg, h.filter_channels_dp * k, k, v.dps);
   }
-  const long long bsH = (long long)H * P;
-  {
-    ProfScope ps(ctx, w, KC_SMALL, 0);
-    hipLaunchKernelGGL(embed_kernel, dim3((Pmax + 63) / 64, 8, B), dim3(256), 0, s, d_ids, ids_ld, d_len, A + gm->emb,
-                       h.num_symbols, H, std::sqrt((float)H), x, bsH, P);
-  }
-  if (h.prenet) {
-    // ConvReluNorm: conv -> LayerNorm -> ReLU (x3), then x + proj(.)  (layers.py:73-80)
-    // Each LayerNorm -> ReLU runs inside the conv that consumes it (launch_ln_conv): conv_0 writes its raw output, conv_i
-    // normalises conv_{i-1}'s, proj the last one's.  Raw outputs alternate between t1 and t2; qkv is the fallback's scratch.
-    float* raw = t1;
-    {
-      ConvArgs a = base_args(x, bsH, P, d_len, 1, raw, bsH, P, d_len, 1, 1, h.prenet_kernel_size / 2);
-      CHECK(launch_enc_conv(ctx, w, gm, gm->pre_conv[0], a, B, Pmax, glow_tiles, enc_host_len, call.solo_tiles));
-    }
-    for (int i = 1; i < h.prenet_layers; ++i) {
-      float* out = raw == t1 ? t2 : t1;
-      ConvArgs a = base_args(raw, bsH, P, d_len, 1, out, bsH, P, d_len, 1, 1, h.prenet_kernel_size / 2);
-      CHECK(launch_ln_conv(ctx, w, gm, gm->pre_conv[i], a, raw, nullptr, qkv, A + gm->pre_g[i - 1], A + gm->pre_b[i - 1], 1, H, bsH, P, d_len,
-                           B, Pmax, glow_tiles, enc_host_len, call.solo_tiles));
-      raw = out;
-    }
-    ConvArgs a = base_args(raw, bsH, P, d_len, 1, x, bsH, P, d_len, 1, 1, 0);
-    a.res = x;
-    const int last = h.prenet_layers - 1;
-    CHECK(launch_ln_conv(ctx, w, gm, gm->pre_proj, a, raw, nullptr, qkv, A + gm->pre_g[last], A + gm->pre_b[last], 1, H, bsH, P, d_len, B, Pmax,
-                         glow_tiles, enc_host_len, call.solo_tiles));
-  }
-  bool ln2_pending = false;  // the previous layer's norm_layers_2 is still to be applied to t1 (the next qkv conv does it)
-  for (int l = 0; l < h.n_layers_enc; ++l) {  // Encoder.forward, attentions.py:62-74
-    const GlowLayer& L = gm->layers[l];
-    {
-      ConvArgs a = base_args(x, bsH, P, d_len, 1, qkv, 3 * bsH, P, d_len, 1, 1, 0);
-      if (ln2_pending) {  // x = LayerNorm(t1) on the way in; stored too: it is the residual of this layer's conv_o and FFN
-        const GlowLayer& Lp = gm->layers[l - 1];
-        CHECK(launch_ln_conv(ctx, w, gm, L.qkv, a, t1, x, nullptr, A + Lp.g2, A + Lp.b2, 0, H, bsH, P, d_len, B, Pmax, glow_tiles,
-                             enc_host_len, call.solo_tiles));
-        ln2_pending = false;
-      } else {
-        CHECK(launch_enc_conv(ctx, w, gm, L.qkv, a, B, Pmax, glow_tiles, enc_host_len, call.solo_tiles));
-      }
-    }
-    {
-      ProfScope ps(ctx, w, KC_SMALL, 0);
-      kn_hit(ctx, KN_ATTENTION);
-      const dim3 ag((Pmax + 31) / 32, nh, B);
-      const int dkh = H / nh;
-      const bool att_big = w->opt.env.att_big_lds;  // (A/B runs)
-#define ATT_LAUNCH_P(NK, X, PM)                                                                                             \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(attention_mfma_kernel<NK, X, PM>), ag, dim3(512), 0, s, qkv, 3 * bsH, P, d_len, H, nh, \
-                     h.window_size, A + L.ek, A + L.ev, t2, bsH, P)
-#define ATT_LAUNCH_X(NK, X)                        \
-  do {                                             \
-    if (Pmax <= 256 && !att_big) ATT_LAUNCH_P(NK, X, 256); \
-    else ATT_LAUNCH_P(NK, X, ATTM_MAXP);           \
-  } while (0)
-#define ATT_LAUNCH(NK)                                                                                                   \
-  do {                                                                                                                   \
-    if (dkh == 2 * NK) ATT_LAUNCH_X(NK, true);                                                                           \
-    else ATT_LAUNCH_X(NK, false);                                                                                        \
-  } while (0)
-      if (Pmax <= ATTM_MAXP && dkh <= 32) ATT_LAUNCH(16);
-      else if (Pmax <= ATTM_MAXP && dkh <= 64) ATT_LAUNCH(32);
-      else if (Pmax <= ATTM_MAXP && dkh <= 96) ATT_LAUNCH(48);
-      else if (Pmax <= ATTM_MAXP) ATT_LAUNCH(64);
-#undef ATT_LAUNCH
-#undef ATT_LAUNCH_X
-#undef ATT_LAUNCH_P
-      else
-        hipLaunchKernelGGL(attention_kernel, dim3(att_rows / ATT_ROWS, nh, B), dim3(256), 0, s, qkv, 3 * bsH, P, d_len, H, nh,
-                           h.window_size, A + L.ek, A + L.ev, t2, bsH, P, sc, P);
-    }
-    if (run_oproj_ln(ctx, w, gm, L, t2, x, H, bsH, P, d_len, enc_host_len, B, Pmax)) {
-      ConvArgs a = base_args(t2, bsH, P, d_len, 1, t1, bsH, P, d_len, 1, 1, 0);
-      a.res = x;
-      CHECK(launch_conv(ctx, w, L.o, a, EPI_LINEAR, B, Pmax, KC_GLOW_ENC_CONV, nullptr, glow_tiles, enc_host_len));
-      ProfScope ps(ctx, w, KC_SMALL, 0);
-      run_layernorm(w, t1, nullptr, A + L.g1, A + L.b1, x, H, bsH, P, d_len, B, Pmax, 0);
-    }
-    {  // FFN, attentions.py:375-383
-      ConvArgs a = base_args(x, bsH, P, d_len, 1, ffn, (long long)Fc * P, P, d_len, 1, 1, k / 2);
-      a.out_act = ACT_RELU;
-      CHECK(launch_enc_conv(ctx, w, gm, L.ffn1, a, B, Pmax, glow_tiles, enc_host_len, call.solo_tiles));
-      ConvArgs c = base_args(ffn, (long long)Fc * P, P, d_len, 1, t1, bsH, P, d_len, 1, 1, k / 2);
-      c.res = x;
-      CHECK(launch_enc_conv(ctx, w, gm, L.ffn2, c, B, Pmax, glow_tiles, enc_host_len, call.solo_tiles));
-      if (l + 1 < h.n_layers_enc) {
-        ln2_pending = true;  // norm_layers_2 rides in the next layer's qkv conv
-      } else {
-        ProfScope ps(ctx, w, KC_SMALL, 0);
-        run_layernorm(w, t1, nullptr, A + L.g2, A + L.b2, x, H, bsH, P, d_len, B, Pmax, 0);
-      }
-    }
-  }
-  {  // proj_m and the duration predictor (models.py:133-139, 39-49)
-    ConvArgs a = base_args(x, bsH, P, d_len, 1, xm, (long long)M * P, P, d_len, 1, 1, 0);
-    CHECK(launch_enc_conv(ctx, w, gm, gm->proj_m, a, B, Pmax, glow_tiles, enc_host_len, call.solo_tiles));
-    float* d1 = ffn;
-    float* d2 = ffn + (size_t)B * Fd * P;
-    float* d3 = ffn + (size_t)2 * B * Fd * P;
-    const long long bsD = (long long)Fd * P;
-    ConvArgs c1 = base_args(x, bsH, P, d_len, 1, d1, bsD, P, d_len, 1, 1, k / 2);
-    c1.out_act = ACT_RELU;
-    if (gin) {
-      // conv_1 over [x ; g repeated along time] (models.py:128-132) = conv_1's encoder half over x + a plane that depends only
-      // on the speaker and on where the row's zero padding starts: d3 is free until conv_2's fallback may use it
-      ProfScope ps(ctx, w, KC_SMALL, 0);
-      hipLaunchKernelGGL(speaker_dp_plane_kernel, dim3((P + 255) / 256, Fd, B), dim3(256), 0, s, spk_dps, Fd, k, k / 2, d_len, d3, bsD, P);
-      c1.res = d3;
-    }
-    CHECK(launch_enc_conv(ctx, w, gm, gm->dp1, c1, B, Pmax, glow_tiles, enc_host_len, call.solo_tiles));
-    // norm_1 inside conv_2 (launch_ln_conv): d1 -> d2; d3 is the fallback's scratch
-    ConvArgs c2 = base_args(d1, bsD, P, d_len, 1, d2, bsD, P, d_len, 1, 1, k / 2);
-    c2.out_act = ACT_RELU;
-    CHECK(launch_ln_conv(ctx, w, gm, gm->dp2, c2, d1, nullptr, d3, A + gm->dg1, A + gm->db1, 0, Fd, bsD, P, d_len, B, Pmax, glow_tiles,
-                         enc_host_len, call.solo_tiles));
-    if (glow_fuse_on(w) && Fd <= 256) {  // norm_2 and proj (1 x 1, Fd -> 1) in one launch
-      ProfScope ps(ctx, w, KC_SMALL, 0);
-      hipLaunchKernelGGL(layernorm16_kernel, dim3((Pmax + 15) / 16, B), dim3(256), 0, w->stream, d2, (const float*)nullptr,
-                         A + gm->dg2, A + gm->db2, d1, Fd, bsD, P, d_len, 0, 0, 1e-4f, A + gm->dpp_w, A + gm->dpp_b, logw, (long long)P);
-    } else {
-      {
-        ProfScope ps(ctx, w, KC_SMALL, 0);
-        run_layernorm(w, d2, nullptr, A + gm->dg2, A + gm->db2, d1, Fd, bsD, P, d_len, B, Pmax, 0);
-      }
-      ConvArgs c3 = base_args(d1, bsD, P, d_len, 1, logw, P, P, d_len, 1, 1, 0);
-      CHECK(launch_conv(ctx, w, gm->dpp, c3, EPI_LINEAR, B, Pmax, KC_GLOW_ENC_CONV, nullptr, glow_tiles, enc_host_len));
-    }
-  }
+  return 0;
+}
 
-  // ---- durations -> frame counts (the one host sync of the path)
-  mi355tts_mel* mel = nullptr;
-  {
-    // frames live with the result object
-    auto* m = new mi355tts_mel();
-    m->ctx = ctx;
-    m->B = B;
-    m->M = M;
-    m->ld = 0;
-    m->frames.assign(B, 0);
-    m->frames_dev = (int*)pool_alloc(ctx, sizeof(int) * B);
-    if (!m->frames_dev) {
-      delete m;
-      return fail(MI355TTS_ERR_NOMEM, "hipMalloc frames");
-    }
-    if (call.want_durations) {  // only a call that asks pays for the block, the copy behind the frame counts and the host vector
-      m->dur_ld = call.pros_ld;
-      m->dur_dev = (int*)pool_alloc(ctx, sizeof(int) * (size_t)B * m->dur_ld);
-      if (!m->dur_dev) {
-        mel_destroy(m);
-        return fail(MI355TTS_ERR_NOMEM, "hipMalloc durations");
-      }
-      m->durations.assign((size_t)B * m->dur_ld, 0);
-    }
-    mel = m;
+// ConvReluNorm: conv -> LayerNorm -> ReLU (x3), then x + proj(.)  (layers.py:73-80)
+// Each LayerNorm -> ReLU runs inside the conv that consumes it (ln_conv): conv_0 writes its raw output, conv_i normalises
+// conv_{i-1}'s, proj the last one's.  Raw outputs alternate between t1 and t2; qkv is the fallback's scratch.
+static int glow_prenet(const GlowPass& p, const GlowEncView& v) {
+  const GlowModel* gm = p.gm;
+  const mi355tts_glow_hparams& h = gm->hp;
+  const long long bsH = (long long)h.hidden_channels * p.ld;
+  const int pad = h.prenet_kernel_size / 2;
+  float* raw = v.t1;
+  CHECK(p.enc_conv(gm->pre_conv[0], p.args(v.x, bsH, raw, bsH, 1, pad)));
+  for (int i = 1; i < h.prenet_layers; ++i) {
+    float* out = raw == v.t1 ? v.t2 : v.t1;
+    CHECK(p.ln_conv(gm->pre_conv[i], p.args(raw, bsH, out, bsH, 1, pad), {p.A + gm->pre_g[i - 1], p.A + gm->pre_b[i - 1], 1, nullptr}, v.qkv));
+    raw = out;
   }
-  struct MelGuard {  // error exits: nothing queued on the stream may still write the blocks that go back to the pool
-    mi355tts_mel* m;
-    hipStream_t st;
-    ~MelGuard() {
-      if (!m) return;
-      mi355_sync(st);
-      mel_destroy(m);
-    }
-  } mguard{mel, s};
+  ConvArgs a = p.args(raw, bsH, v.x, bsH);
+  a.res = v.x;
+  const int last = h.prenet_layers - 1;
+  return p.ln_conv(gm->pre_proj, a, {p.A + gm->pre_g[last], p.A + gm->pre_b[last], 1, nullptr}, v.qkv);
+}
+
+// Encoder layer l (Encoder.forward, attentions.py:62-74).  Its norm_layers_2 rides in the next layer's qkv conv: `prev` is the
+// layer whose norm is still to be applied to t1 (nullptr for the first), and the last layer applies its own.
+static int glow_enc_layer(const GlowPass& p, const GlowEncView& v, int att_rows, int l) {
+  const mi355tts_glow_hparams& h = p.gm->hp;
+  const GlowLayer& L = p.gm->layers[l];
+  const GlowLayer* prev = l > 0 ? &p.gm->layers[l - 1] : nullptr;
+  const int H = h.hidden_channels, Fc = h.filter_channels, k = h.kernel_size;
+  const long long bsH = (long long)H * p.ld, bsF = (long long)Fc * p.ld;
+  if (prev)  // x = LayerNorm(t1) on the way in; stored too: it is the residual of this layer's conv_o and FFN
+    CHECK(p.ln_conv(L.qkv, p.args(v.t1, bsH, v.qkv, 3 * bsH), {p.A + prev->g2, p.A + prev->b2, 0, v.x}, nullptr));
+  else
+    CHECK(p.enc_conv(L.qkv, p.args(v.x, bsH, v.qkv, 3 * bsH)));
+  launch_attention(p, L, v, att_rows);
+  if (run_oproj_ln(p, L, v.t2, v.x)) {
+    ConvArgs a = p.args(v.t2, bsH, v.t1, bsH);
+    a.res = v.x;
+    CHECK(p.conv(L.o, a));
+    p.layernorm(v.t1, p.A + L.g1, p.A + L.b1, v.x, H, bsH, 0);
+  }
+  // FFN, attentions.py:375-383
+  ConvArgs a = p.args(v.x, bsH, v.ffn, bsF, 1, k / 2);
+  a.out_act = ACT_RELU;
+  CHECK(p.enc_conv(L.ffn1, a));
+  ConvArgs c = p.args(v.ffn, bsF, v.t1, bsH, 1, k / 2);
+  c.res = v.x;
+  CHECK(p.enc_conv(L.ffn2, c));
+  if (l + 1 == h.n_layers_enc) p.layernorm(v.t1, p.A + L.g2, p.A + L.b2, v.x, H, bsH, 0);
+  return 0;
+}
+
+// proj_m and the duration predictor (models.py:133-139, 39-49): x -> x_m, logw
+static int glow_proj_durations(const GlowPass& p, const GlowEncView& v) {
+  const GlowModel* gm = p.gm;
+  const mi355tts_glow_hparams& h = gm->hp;
+  const float* A = p.A;
+  const int H = h.hidden_channels, Fd = h.filter_channels_dp, M = h.mel_channels, k = h.kernel_size, P = p.ld, B = p.B;
+  const long long bsH = (long long)H * P, bsD = (long long)Fd * P;
+  CHECK(p.enc_conv(gm->proj_m, p.args(v.x, bsH, v.xm, (long long)M * P)));
+  float* d1 = v.ffn;
+  float* d2 = v.ffn + (size_t)B * Fd * P;
+  float* d3 = v.ffn + (size_t)2 * B * Fd * P;
+  ConvArgs c1 = p.args(v.x, bsH, d1, bsD, 1, k / 2);
+  c1.out_act = ACT_RELU;
+  if (gm->gin()) {
+    // conv_1 over [x ; g repeated along time] (models.py:128-132) = conv_1's encoder half over x + a plane that depends only
+    // on the speaker and on where the row's zero padding starts: d3 is free until conv_2's fallback may use it
+    ProfScope ps = p.small();
+    hipLaunchKernelGGL(speaker_dp_plane_kernel, dim3((P + 255) / 256, Fd, B), dim3(256), 0, p.s, v.dps, Fd, k, k / 2, p.d_len, d3, bsD, P);
+    c1.res = d3;
+  }
+  CHECK(p.enc_conv(gm->dp1, c1));
+  // norm_1 inside conv_2 (ln_conv): d1 -> d2; d3 is the fallback's scratch
+  ConvArgs c2 = p.args(d1, bsD, d2, bsD, 1, k / 2);
+  c2.out_act = ACT_RELU;
+  CHECK(p.ln_conv(gm->dp2, c2, {A + gm->dg1, A + gm->db1, 0, nullptr}, d3));
+  if (glow_fuse_on(p.w) && Fd <= 256) {  // norm_2 and proj (1 x 1, Fd -> 1) in one launch
+    ProfScope ps = p.small();
+    hipLaunchKernelGGL(layernorm16_kernel, dim3((p.n_max + 15) / 16, B), dim3(256), 0, p.s, d2, (const float*)nullptr, A + gm->dg2,
+                       A + gm->db2, d1, Fd, bsD, P, p.d_len, 0, 0, 1e-4f, A + gm->dpp_w, A + gm->dpp_b, v.logw, (long long)P);
+    return 0;
+  }
+  p.layernorm(d2, A + gm->dg2, A + gm->db2, d1, Fd, bsD, 0);
+  return p.conv(gm->dpp, p.args(d1, bsD, v.logw, P));
+}
+
+static int glow_encoder(GlowRun& r) {
+  const GlowCall& call = r.call;
+  const mi355tts_glow_hparams& h = r.gm->hp;
+  const int B = call.B, H = h.hidden_channels, P = r.el.P, Pmax = r.Pmax;
+  long long sum = 0;
+  for (int b = 0; b < B; ++b) sum += call.id_lens[b];
+  r.w->flop_scale = Pmax > 0 ? (double)sum / ((double)B * Pmax) : 1.0;  // ragged batch: count the rows' real ids
+  CHECK(glow_enc_upload(r));
+  const GlowEncView& v = r.ev;
+  const GlowPass p = r.pass(Pmax, P, v.len, B == 1 ? call.id_lens[0] : -1, KC_GLOW_ENC_CONV);
   {
-    ProfScope ps(ctx, w, KC_SMALL, 0);
-    hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(64), 0, s, logw, (long long)P, d_len, length_scale, h.n_sqz, cum, P,
-                       mel->frames_dev, 1 << 28, call.id_scales ? (const float*)d_pros : nullptr,
-                       call.durations_in ? (const int*)d_pros : nullptr, P, mel->dur_dev, mel->dur_ld);
+    ProfScope ps = p.small();
+    hipLaunchKernelGGL(embed_kernel, dim3((Pmax + 63) / 64, 8, B), dim3(256), 0, p.s, v.ids, call.ids_ld, v.len, p.A + r.gm->emb,
+                       h.num_symbols, H, std::sqrt((float)H), v.x, (long long)H * P, P);
+  }
+  if (h.prenet) CHECK(glow_prenet(p, v));
+  for (int l = 0; l < h.n_layers_enc; ++l) CHECK(glow_enc_layer(p, v, r.el.att_rows, l));
+  return glow_proj_durations(p, v);
+}
+
+// ---- stage 2, durations -> frame counts (the one host sync of the path): the mel object (handed to `drop` as soon as it
+// exists), duration_kernel, the read-back, the result blocks.  mel->max_frames == 0: nothing to decode.
+static int glow_mel_new(mi355tts_ctx* ctx, const GlowCall& call, int M, mi355tts_mel** out) {
+  const int B = call.B;
+  // frames live with the result object
+  auto* m = new mi355tts_mel();
+  m->ctx = ctx; m->B = B; m->M = M; m->ld = 0;
+  m->frames.assign(B, 0);
+  m->frames_dev = (int*)pool_alloc(ctx, sizeof(int) * B);
+  if (!m->frames_dev) {
+    delete m;
+    return fail(MI355TTS_ERR_NOMEM, "hipMalloc frames");
+  }
+  if (call.want_durations) {  // only a call that asks pays for the block, the copy behind the frame counts and the host vector
+    m->dur_ld = call.pros_ld;
+    m->dur_dev = (int*)pool_alloc(ctx, sizeof(int) * (size_t)B * m->dur_ld);
+    if (!m->dur_dev) {
+      mel_destroy(m);
+      return fail(MI355TTS_ERR_NOMEM, "hipMalloc durations");
+    }
+    m->durations.assign((size_t)B * m->dur_ld, 0);
+  }
+  *out = m;
+  return 0;
+}
+static int glow_durations(GlowRun& r, MelDrop& drop) {
+  const GlowCall& call = r.call;
+  const mi355tts_glow_hparams& h = r.gm->hp;
+  Worker* w = r.w;
+  hipStream_t s = w->stream;
+  const GlowEncView& v = r.ev;
+  const int B = call.B, M = h.mel_channels, P = r.el.P;
+  CHECK(glow_mel_new(r.ctx, call, M, &r.mel));
+  mi355tts_mel* mel = drop.m = r.mel;
+  {
+    ProfScope ps(r.ctx, w, KC_SMALL, 0);
+    hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(64), 0, s, v.logw, (long long)P, v.len, call.length_scale, h.n_sqz, v.cum, P,
+                       mel->frames_dev, 1 << 28, call.id_scales ? (const float*)v.pros : nullptr,
+                       call.durations_in ? (const int*)v.pros : nullptr, P, mel->dur_dev, mel->dur_ld);
   }
   if ((size_t)B > w->pinned_ints) return fail(MI355TTS_ERR_INVALID, "batch too large");
   HIPCHECK(hipMemcpyAsync(w->pinned, mel->frames_dev, sizeof(int) * B, hipMemcpyDeviceToHost, s));
@@ -536,192 +567,187 @@ static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const Glo
   HIPCHECK(mi355_sync(s));
   if (call.durations_out) std::memcpy(call.durations_out, mel->durations.data(), sizeof(int32_t) * mel->durations.size());
   int Fmax = 0;
+  long long sum = 0;
   for (int b = 0; b < B; ++b) {
     mel->frames[b] = w->pinned[b];
     Fmax = std::max(Fmax, w->pinned[b]);
+    sum += w->pinned[b];
   }
-  if (noise && noise_scale != 0.f && noise_ld < Fmax)
-    return fail(MI355TTS_ERR_TOO_SMALL, "noise has %d columns but the utterance needs %d frames", noise_ld, Fmax);
+  if (call.noise && call.noise_scale != 0.f && call.noise_ld < Fmax)
+    return fail(MI355TTS_ERR_TOO_SMALL, "noise has %d columns but the utterance needs %d frames", call.noise_ld, Fmax);
   mel->max_frames = Fmax;
-  {
-    long long sum = 0;
-    for (int b = 0; b < B; ++b) sum += mel->frames[b];
-    w->flop_scale = Fmax > 0 ? (double)sum / ((double)B * Fmax) : 1.0;
-  }
-  const int Fld = (Fmax + 3) & ~3;
-  mel->ld = Fld;
-  if (Fmax == 0) {
-    mguard.m = nullptr;
-    *out = mel;
-    return 0;
-  }
-  {
-    const size_t n = (size_t)B * M * Fld * sizeof(float);
-    mel->raw_bytes = n;
-    mel->raw = (float*)pool_alloc(ctx, n);
-    mel->voc = (float*)pool_alloc(ctx, n);
-    if (!mel->raw || !mel->voc) return fail(MI355TTS_ERR_NOMEM, "hipMalloc mel");
-  }
-
-  // ---- decoder workspace (appended after the encoder's, which stays live)
-  const int nsq = h.n_sqz;
-  const int C = M * nsq, half = C / 2;
-  const int F2max = Fmax / nsq;
-  const int F2 = (F2max + 3) & ~3;
-  const GlowDecLayout dl = glow_dec_layout(h, enc_bytes, B, Fmax, (noise && !in_dev) ? (size_t)B * M * noise_ld : 0);
-  const size_t o_z = dl.o_z, o_h = dl.o_h, o_ac = dl.o_ac, o_sk = dl.o_sk, o_nz = dl.o_nz;
-  if (dl.total > w->arena_bytes) {
-    // growing would move the encoder buffers: stage the three still-live encoder
-    // outputs (x_m, cum, len) through a fresh arena instead
-    std::vector<char> keep(enc_bytes);
-    HIPCHECK(hipMemcpy(keep.data(), w->arena, enc_bytes, hipMemcpyDeviceToHost));
-    CHECK(reserve(w, dl.total));
-    HIPCHECK(hipMemcpy(w->arena, keep.data(), enc_bytes, hipMemcpyHostToDevice));
-    base = w->arena;
-    d_len = (int*)(base + o_len);
-    if (d_seeds) d_seeds = (unsigned long long*)(base + el.o_seed);
-    xm = (float*)(base + o_xm);
-    cum = (int*)(base + o_cum);
-    if (gin) spk_cond = (float*)(base + el.o_cond);
-  }
-  float* z = (float*)(base + o_z);
-  float* hbuf = (float*)(base + o_h);
-  float* acts = (float*)(base + o_ac);
-  float* skip = (float*)(base + o_sk);
-  const float* d_noise = noise;
-  if (noise && !in_dev) {
-    float* nz = (float*)(base + o_nz);
-    HIPCHECK(hipMemcpyAsync(nz, noise, sizeof(float) * (size_t)B * M * noise_ld, hipMemcpyHostToDevice, s));
-    d_noise = nz;
-  }
-  const int* d_frames = mel->frames_dev;
-  const long long bsZ = (long long)C * F2, bsD = (long long)H * F2;
-  {
-    ProfScope ps(ctx, w, KC_SMALL, 0);
-    hipLaunchKernelGGL(expand_noise_squeeze_kernel, dim3((Fmax + 255) / 256, 8, B), dim3(256), 0, s, xm, (long long)M * P, P,
-                       d_len, cum, P, d_frames, d_noise, (long long)M * noise_ld, noise_ld, noise_scale, seed, d_seeds, M, nsq,
-                       z, bsZ, F2);
-  }
-  // frames/n_sqz is the decoder's time axis: len = frames[b] / nsq  -> use out_mul trick via a scaled length array
-  // (frames are multiples of n_sqz; kernels take frames with a divisor where needed)
-  const int dec_host_len = B == 1 ? mel->frames[0] / nsq : -1;
-  int* d_f2 = (int*)(base + o_len);  // reuse: id lengths are no longer needed after expansion
-  {
-    // d_f2[b] = frames[b] / nsq, computed on the host side of the sync above
-    for (int b = 0; b < B; ++b) w->pinned[b] = mel->frames[b] / nsq;
-    HIPCHECK(hipMemcpyAsync(d_f2, w->pinned, sizeof(int) * B, hipMemcpyHostToDevice, s));
-  }
-  float* const hcur = hbuf;  // the WaveNet's hidden state
-  bool start_done = false;  // the previous block's tail launch already ran this block's start conv
-  for (int blk = h.n_blocks_dec - 1; blk >= 0; --blk) {  // models.py:195-206, reversed flows
-    const GlowBlock& Bk = gm->blocks[blk];
-    if (!start_done) {  // CouplingBlock reverse (attentions.py:119-142): h = start(x0)
-      ConvArgs a = base_args(z, bsZ, F2, d_f2, 1, hcur, bsD, F2, d_f2, 1, 1, 0);
-      CHECK(launch_conv(ctx, w, Bk.start, a, EPI_LINEAR, B, F2max, KC_GLOW_DEC_CONV, nullptr, glow_tiles, dec_host_len));
-    }
-    int dil = 1;
-    bool tail_done = false;
-    // the fp16 mode: layers 0 .. n - 1 up to the last gated tile in ONE launch (wn_f16.h); the loop then runs the last layer's tail
-    const bool wn16 = glow_f16 && run_wn_f16(ctx, w, gm, Bk, hcur, acts, skip, bsD, F2, d_f2, dec_host_len, B, F2max) == 0;
-    for (int j = wn16 ? h.n_block_layers - 1 : 0; j < h.n_block_layers; ++j) {  // WN.forward, layers.py:138-162
-      const int kd = h.kernel_size_dec;
-      const bool last = j == h.n_block_layers - 1;
-      ConvArgs a = base_args(hcur, bsD, F2, d_f2, 1, acts, bsD, F2, d_f2, 1, dil, (kd * dil - dil) / 2);
-      a.half = H;
-      if (gin) {  // x_in + g_l (layers.py:144-154): this block's, this layer's [2H] slice of cond_layer(g), per batch row
-        a.cond = spk_cond + (size_t)blk * n2 + (size_t)j * 2 * H;
-        a.cond_bs = (long long)h.n_blocks_dec * n2;
-      }
-      if (B == 1 && dec_host_len >= 0) {  // the length is known on the host: no device length array to chase
-        a.in_len = a.out_len = nullptr;
-        a.in_const = a.out_const = dec_host_len;
-      }
-      if (!wn16) {
-        const int g16 = run_gate16(ctx, w, Bk.in[j], a, B, F2max, KC_GLOW_DEC_CONV, s);
-        if (g16 < 0) return g16;
-        if (g16 == 1) CHECK(launch_conv(ctx, w, Bk.in[j], a, EPI_GATE, B, F2max, KC_GLOW_DEC_CONV, nullptr, glow_tiles, dec_host_len));
-      }
-      if (last) {
-        // last layer: res_skip (all skip) + end + coupling + InvConvNear/ActNorm + the next block's start in ONE launch
-        const GlowBlock* next = blk > 0 ? &gm->blocks[blk - 1] : nullptr;
-        tail_done = run_glow_tail(ctx, w, gm, Bk, next, acts, skip, hcur, bsD, z, bsZ, F2, d_f2, dec_host_len, B, F2max) == 0;
-        if (tail_done) break;
-      }
-      ConvArgs r = base_args(acts, bsD, F2, d_f2, 1, hcur, bsD, F2, d_f2, 1, 1, 0);
-      if (j < h.n_block_layers - 1) {
-        r.res = hcur;  // x = x + res_skip[:H]
-        r.split = H;
-      } else {
-        r.split = 0;  // last layer: everything is skip
-      }
-      r.y2 = skip;
-      r.y2_bs = bsD;
-      r.y2_ld = F2;
-      r.accum2 = j > 0;
-      if (run_lin16(ctx, w, Bk.rs[j], r, A, B, F2max, KC_GLOW_DEC_CONV, dec_host_len, call.solo_tiles) != 0)
-        CHECK(launch_conv(ctx, w, Bk.rs[j], r, EPI_LINEAR, B, F2max, KC_GLOW_DEC_CONV, nullptr, glow_tiles, dec_host_len));
-      dil *= h.dilation_rate;
-    }
-    start_done = tail_done;
-    if (tail_done) continue;
-    {  // m, logs = end(wn_out);  z1 = (x1 - m) * exp(-logs)
-      ConvArgs a = base_args(skip, bsD, F2, d_f2, 1, z + (size_t)half * F2, bsZ, F2, d_f2, 1, 1, 0);
-      a.res = z + (size_t)half * F2;
-      a.half = half;
-      const bool fuse_mix = h.n_split == 4 && (half % 2) == 0;
-      if (fuse_mix) {  // InvConvNear + ActNorm ride in the coupling conv's epilogue
-        a.mix_x0 = z;
-        a.mix_w = A + Bk.winv;
-        a.mix_bias = A + Bk.an_bias;
-        a.mix_scale = A + Bk.an_scale;
-      }
-      CHECK(launch_conv(ctx, w, Bk.end, a, EPI_COUPLING, B, F2max, KC_GLOW_DEC_CONV, nullptr, glow_tiles, dec_host_len));
-      if (fuse_mix) continue;
-    }
-    {
-      ProfScope ps(ctx, w, KC_SMALL, 0);
-      hipLaunchKernelGGL(invconv_actnorm_kernel, dim3((F2max + 255) / 256, std::min(C / h.n_split, 16), B), dim3(256), 0, s, z,
-                         bsZ, F2, d_f2, 1, C, h.n_split, A + Bk.winv, A + Bk.an_bias, A + Bk.an_scale);
-    }
-  }
-  {
-    ProfScope ps(ctx, w, KC_SMALL, 0);
-    hipLaunchKernelGGL(mel_finalize_kernel, dim3((Fld + 255) / 256, std::min(M, 16), B), dim3(256), 0, s, z, bsZ, F2, d_frames, M,
-                       nsq, mel->raw, mel->voc, (long long)M * Fld, Fld, to_mt(audio), audio ? 1 : 0);
-  }
-  if (final_sync) {
-    HIPCHECK(mi355_sync(s));
-    HIPCHECK(hipGetLastError());
-  }
-  mguard.m = nullptr;
-  w->flop_scale = 1.0;
-  *out = mel;
+  w->flop_scale = Fmax > 0 ? (double)sum / ((double)B * Fmax) : 1.0;
+  mel->ld = (Fmax + 3) & ~3;
+  if (Fmax == 0) return 0;
+  const size_t n = (size_t)B * M * mel->ld * sizeof(float);
+  mel->raw_bytes = n;
+  mel->raw = (float*)pool_alloc(r.ctx, n);
+  mel->voc = (float*)pool_alloc(r.ctx, n);
+  if (!mel->raw || !mel->voc) return fail(MI355TTS_ERR_NOMEM, "hipMalloc mel");
   return 0;
 }
 
-static int glow_infer_impl(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
-                           float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
-                           const uint64_t* row_seeds, const mi355tts_audio_settings* audio, uint32_t flags, mi355tts_mel** out,
-                           const int32_t* speaker_ids = nullptr, const mi355tts_prosody* prosody = nullptr) {
+// ---- stage 3, the decoder (models.py:195-206, the flows in reverse)
+// The decoder's workspace is appended to the encoder's, which stays live.  When that outgrows the arena, growing moves it: the
+// encoder's region goes through the host into the fresh arena and EVERY view is bound again.
+static int glow_dec_workspace(GlowRun& r, const GlowDecLayout& dl, GlowDecView* dv) {
+  Worker* w = r.w;
+  if (dl.total > w->arena_bytes) {
+    std::vector<char> keep(r.el.total);
+    HIPCHECK(hipMemcpy(keep.data(), w->arena, keep.size(), hipMemcpyDeviceToHost));
+    CHECK(reserve(w, dl.total));
+    HIPCHECK(hipMemcpy(w->arena, keep.data(), keep.size(), hipMemcpyHostToDevice));
+    r.ev = glow_enc_view(r.el, w->arena);
+  }
+  *dv = glow_dec_view(dl, w->arena);
+  return 0;
+}
+
+// Flow block `blk` in reverse (CouplingBlock, attentions.py:119-142; WN.forward, layers.py:138-162).  Three forms of the same
+// arithmetic, fastest first:
+//   * the WaveNet: the fp16 mode's one launch for every layer but the last tail (wn16), else per layer the 16-row gate tile or
+//     the generic tile, and res_skip on the 16-row tile or the generic one;
+//   * the tail: last res_skip + end + coupling + InvConvNear / ActNorm + the NEXT block's start conv in one launch (tail_done),
+//     else res_skip, then the coupling conv with the mix in its epilogue, else the mix as a launch of its own.
+// *start_done: in, the previous block's tail already ran this block's start conv; out, this block's tail ran the next one's.
+static int glow_flow_block(const GlowPass& p, const GlowDecView& dv, const float* spk_cond, bool glow_f16, int blk, bool* start_done) {
+  const mi355tts_glow_hparams& h = p.gm->hp;
+  const GlowBlock& Bk = p.gm->blocks[blk];
+  const int H = h.hidden_channels, C = h.mel_channels * h.n_sqz, half = C / 2, F2 = p.ld, n = h.n_block_layers;
+  const int n2 = 2 * H * n;  // gate offsets per flow block
+  const long long bsZ = (long long)C * F2, bsD = (long long)H * F2;
+  float* const hcur = dv.h;  // the WaveNet's hidden state
+  if (!*start_done) CHECK(p.conv(Bk.start, p.args(dv.z, bsZ, hcur, bsD)));  // h = start(x0)
+  *start_done = false;
+  int dil = 1;
+  // the fp16 mode: layers 0 .. n - 1 up to the last gated tile in ONE launch (wn_f16.h); the loop then runs the last layer's tail
+  const bool wn16 = glow_f16 && run_wn_f16(p, dv, Bk) == 0;
+  for (int j = wn16 ? n - 1 : 0; j < n; ++j) {
+    const int kd = h.kernel_size_dec;
+    const bool last = j == n - 1;
+    if (!wn16) {
+      ConvArgs a = p.args(hcur, bsD, dv.acts, bsD, dil, (kd * dil - dil) / 2);
+      a.half = H;
+      if (spk_cond) {  // x_in + g_l (layers.py:144-154): this block's, this layer's [2H] slice of cond_layer(g), per batch row
+        a.cond = spk_cond + (size_t)blk * n2 + (size_t)j * 2 * H;
+        a.cond_bs = (long long)h.n_blocks_dec * n2;
+      }
+      // one row: the length is known on the host, no device length array to chase
+      a.in_len = a.out_len = p.rows().len;
+      a.in_const = a.out_const = p.rows().len_const;
+      const int g16 = p.gate16(Bk.in[j], a);
+      if (g16 < 0) return g16;
+      if (g16 == 1) CHECK(p.conv(Bk.in[j], a, EPI_GATE));
+    }
+    if (last) {
+      const GlowBlock* next = blk > 0 ? &p.gm->blocks[blk - 1] : nullptr;
+      *start_done = run_glow_tail(p, dv, Bk, next) == 0;
+      if (*start_done) return 0;
+    }
+    ConvArgs r = p.args(dv.acts, bsD, hcur, bsD);
+    r.split = last ? 0 : H;    // last layer: everything is skip
+    if (!last) r.res = hcur;  // x = x + res_skip[:H]
+    r.y2 = dv.skip; r.y2_bs = bsD; r.y2_ld = F2; r.accum2 = j > 0;
+    if (p.lin16(Bk.rs[j], r) != 0) CHECK(p.conv(Bk.rs[j], r));
+    dil *= h.dilation_rate;
+  }
+  // m, logs = end(wn_out);  z1 = (x1 - m) * exp(-logs)
+  float* z1 = dv.z + (size_t)half * F2;
+  ConvArgs a = p.args(dv.skip, bsD, z1, bsZ);
+  a.res = z1;
+  a.half = half;
+  const bool fuse_mix = h.n_split == 4 && (half % 2) == 0;
+  if (fuse_mix) {  // InvConvNear + ActNorm ride in the coupling conv's epilogue
+    a.mix_x0 = dv.z; a.mix_w = p.A + Bk.winv; a.mix_bias = p.A + Bk.an_bias; a.mix_scale = p.A + Bk.an_scale;
+  }
+  CHECK(p.conv(Bk.end, a, EPI_COUPLING));
+  if (fuse_mix) return 0;
+  ProfScope ps = p.small();
+  hipLaunchKernelGGL(invconv_actnorm_kernel, dim3((p.n_max + 255) / 256, std::min(C / h.n_split, 16), p.B), dim3(256), 0, p.s, dv.z, bsZ, F2,
+                     p.d_len, 1, C, h.n_split, p.A + Bk.winv, p.A + Bk.an_bias, p.A + Bk.an_scale);
+  return 0;
+}
+
+static int glow_decoder(GlowRun& r) {
+  const GlowCall& call = r.call;
+  const mi355tts_glow_hparams& h = r.gm->hp;
+  Worker* w = r.w;
+  hipStream_t s = w->stream;
+  mi355tts_mel* mel = r.mel;
+  const int B = call.B, M = h.mel_channels, nsq = h.n_sqz, P = r.el.P;
+  const int Fmax = mel->max_frames, Fld = mel->ld, F2max = Fmax / nsq, F2 = (F2max + 3) & ~3;
+  const long long bsZ = (long long)M * nsq * F2;
+  const bool host_noise = call.noise && !(call.flags & MI355TTS_IN_DEVICE);
+  GlowDecView dv;
+  CHECK(glow_dec_workspace(r, glow_dec_layout(h, r.el.total, B, Fmax, host_noise ? (size_t)B * M * call.noise_ld : 0), &dv));
+  const GlowEncView& v = r.ev;
+  const float* d_noise = call.noise;
+  if (host_noise) {
+    HIPCHECK(hipMemcpyAsync(dv.nz, call.noise, sizeof(float) * (size_t)B * M * call.noise_ld, hipMemcpyHostToDevice, s));
+    d_noise = dv.nz;
+  }
+  {
+    ProfScope ps(r.ctx, w, KC_SMALL, 0);
+    hipLaunchKernelGGL(expand_noise_squeeze_kernel, dim3((Fmax + 255) / 256, 8, B), dim3(256), 0, s, v.xm, (long long)M * P, P, v.len,
+                       v.cum, P, mel->frames_dev, d_noise, (long long)M * call.noise_ld, call.noise_ld, call.noise_scale, call.seed,
+                       call.row_seeds ? v.seeds : nullptr, M, nsq, dv.z, bsZ, F2);
+  }
+  // the decoder's time axis: row b is frames[b] / n_sqz columns long (frames are multiples of n_sqz), computed on the host side
+  // of the sync.  The array reuses the id lengths' slot: they are no longer needed after expansion.
+  int* d_f2 = v.len;
+  for (int b = 0; b < B; ++b) w->pinned[b] = mel->frames[b] / nsq;
+  HIPCHECK(hipMemcpyAsync(d_f2, w->pinned, sizeof(int) * B, hipMemcpyHostToDevice, s));
+  const GlowPass p = r.pass(F2max, F2, d_f2, B == 1 ? mel->frames[0] / nsq : -1, KC_GLOW_DEC_CONV);
+  // the `half` switch as this call saw it: the decoder's WaveNets in fp16 (wn_f16.h)
+  const bool glow_f16 = r.gm->f16_ok && r.gm->precision.load() == MI355TTS_PRECISION_F16;
+  bool start_done = false;
+  for (int blk = h.n_blocks_dec - 1; blk >= 0; --blk)
+    CHECK(glow_flow_block(p, dv, r.gm->gin() ? v.cond : nullptr, glow_f16, blk, &start_done));
+  ProfScope ps(r.ctx, w, KC_SMALL, 0);
+  hipLaunchKernelGGL(mel_finalize_kernel, dim3((Fld + 255) / 256, std::min(M, 16), B), dim3(256), 0, s, dv.z, bsZ, F2, mel->frames_dev, M,
+                     nsq, mel->raw, mel->voc, (long long)M * Fld, Fld, to_mt(call.audio), call.audio ? 1 : 0);
+  return 0;
+}
+
+// The forward pass on worker `w`.  With `final_sync` false the mel object is returned while
+// its last kernels are still queued on w->stream (the fused synthesize path launches the
+// vocoder behind them on the same stream).
+static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const GlowCall& call, int Pmax, bool final_sync,
+                    mi355tts_mel** out) {
+  const int glow_tiles = call.solo_tiles ? (1 << 30) : w->opt.env.glow_tiles > 0 ? w->opt.env.glow_tiles : 1024;
+  GlowRun r{ctx, w, gm, call, Pmax, glow_tiles, glow_enc_layout(gm->hp, call.B, call.ids_ld, Pmax), {}, nullptr};
+  CHECK(glow_encoder(r));
+  MelDrop drop{w->stream, nullptr};
+  CHECK(glow_durations(r, drop));
+  if (r.mel->max_frames > 0) {
+    CHECK(glow_decoder(r));
+    if (final_sync) {
+      HIPCHECK(mi355_sync(w->stream));
+      HIPCHECK(hipGetLastError());
+    }
+    w->flop_scale = 1.0;
+  }
+  drop.m = nullptr;
+  *out = r.mel;
+  return 0;
+}
+
+// the arguments the entry points share, in their order (the rest of a GlowCall is filled by the entry that has it)
+static GlowCall glow_call(const int64_t* ids, const int32_t* id_lens, int B, int ids_ld, float noise_scale, float length_scale,
+                          const float* noise, int noise_ld, uint64_t seed, const mi355tts_audio_settings* audio, uint32_t flags) {
+  GlowCall c;
+  c.ids = ids; c.id_lens = id_lens; c.B = B; c.ids_ld = ids_ld;
+  c.noise_scale = noise_scale; c.length_scale = length_scale;
+  c.noise = noise; c.noise_ld = noise_ld; c.seed = seed;
+  c.audio = audio; c.flags = flags;
+  return c;
+}
+
+static int glow_infer_impl(mi355tts_ctx* ctx, int glow, const GlowCall& c, mi355tts_mel** out) {
   if (!ctx || !out) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GlowModel> gpin;
   CHECK(find_glow(ctx, glow, &gpin));
   const GlowModel* gm = gpin.get();
-  GlowCall c;
-  c.ids = ids;
-  c.id_lens = id_lens;
-  c.B = B;
-  c.ids_ld = ids_ld;
-  c.noise_scale = noise_scale;
-  c.length_scale = length_scale;
-  c.noise = noise;
-  c.noise_ld = noise_ld;
-  c.seed = seed;
-  c.row_seeds = row_seeds;
-  c.speaker_ids = speaker_ids;
-  c.audio = audio;
-  c.flags = flags;
-  c.set_prosody(prosody, true);  // the two-call form: the mel always keeps the durations
   int Pmax = 0;
   CHECK(glow_precheck(gm, c, &Pmax));
   HIPCHECK(hipSetDevice(ctx->device));
@@ -734,26 +760,33 @@ static int glow_infer_impl(mi355tts_ctx* ctx, int glow, const int64_t* ids, cons
 extern "C" int mi355tts_glow_infer(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
                                    float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
                                    const mi355tts_audio_settings* audio, uint32_t flags, mi355tts_mel** out) {
-  return glow_infer_impl(ctx, glow, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, nullptr, audio, flags, out);
+  return glow_infer_impl(ctx, glow, glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, audio, flags), out);
 }
 extern "C" int mi355tts_glow_infer_speakers(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
                                             float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
                                             const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
                                             uint32_t flags, mi355tts_mel** out) {
   if (!speaker_ids) return fail(MI355TTS_ERR_INVALID, "speaker_ids null");
-  return glow_infer_impl(ctx, glow, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, row_seeds, audio, flags, out,
-                         speaker_ids);
+  GlowCall c = glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, audio, flags);
+  c.row_seeds = row_seeds;
+  c.speaker_ids = speaker_ids;
+  return glow_infer_impl(ctx, glow, c, out);
 }
 extern "C" int mi355tts_glow_infer_rows(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
                                         float noise_scale, float length_scale, const uint64_t* row_seeds,
                                         const mi355tts_audio_settings* audio, uint32_t flags, mi355tts_mel** out) {
   if (!row_seeds) return fail(MI355TTS_ERR_INVALID, "row_seeds null");
-  return glow_infer_impl(ctx, glow, ids, id_lens, B, ids_ld, noise_scale, length_scale, nullptr, 0, 0, row_seeds, audio, flags, out);
+  GlowCall c = glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, nullptr, 0, 0, audio, flags);
+  c.row_seeds = row_seeds;
+  return glow_infer_impl(ctx, glow, c, out);
 }
 extern "C" int mi355tts_glow_infer_prosody(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
                                            float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
                                            const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
                                            uint32_t flags, const mi355tts_prosody* prosody, mi355tts_mel** out) {
-  return glow_infer_impl(ctx, glow, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, row_seeds, audio, flags, out,
-                         speaker_ids, prosody);
+  GlowCall c = glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, audio, flags);
+  c.row_seeds = row_seeds;
+  c.speaker_ids = speaker_ids;
+  c.set_prosody(prosody, true);  // the two-call form: the mel always keeps the durations
+  return glow_infer_impl(ctx, glow, c, out);
 }

@@ -235,16 +235,10 @@ static int run_pair_group_f16(mi355tts_ctx* ctx, Worker* w, const HPairPlan* p, 
 }
 
 // lengths: one row with a host-known length takes it as a launch constant (no dependent load in every workgroup's prologue)
-static void h_set_lengths(HConvArgs& a, const int* d_frames, int host_len, int in_mul, int out_mul) {
-  if (host_len >= 0) {
-    a.in_len = nullptr;
-    a.out_len = nullptr;
-    a.in_const = host_len * in_mul;
-    a.out_const = host_len * out_mul;
-  } else {
-    a.in_len = d_frames;
-    a.out_len = d_frames;
-  }
+static void h_set_lengths(HConvArgs& a, int B, const int* d_frames, int host_len, int in_mul, int out_mul) {
+  const RowLen in = row_len(B, host_len, d_frames, in_mul), out = row_len(B, host_len, d_frames, out_mul);
+  a.in_len = in.len; a.in_const = in.len_const;
+  a.out_len = out.len; a.out_const = out.len_const;
   a.in_mul = in_mul;
   a.out_mul = out_mul;
 }
@@ -307,7 +301,7 @@ static int hifigan_body_f16(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const m
     a.y_bs = (long long)(C0 / 8) * F;
     a.y_ld = F;
     a.cout = C0;
-    h_set_lengths(a, d_frames, voc_host_len, 1, 1);
+    h_set_lengths(a, B, d_frames, voc_host_len, 1, 1);
     const HPlan p = plan_f16(hm->h_pre, a, EPI_LINEAR, B, F, 2.0 * C0 * M * 7 * (double)F * B);
     CHECK(run_plan_f16(ctx, w, p, KC_VOC_IO, s));
   }
@@ -336,7 +330,7 @@ static int hifigan_body_f16(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const m
       a.up = u;
       a.up_pad = u / 2;
       a.cout = cout;
-      h_set_lengths(a, d_frames, voc_host_len, mul, mul * u);
+      h_set_lengths(a, B, d_frames, voc_host_len, mul, mul * u);
       HPlan p = plan_f16(hm->h_ups[i], a, EPI_UPSAMPLE, B, Lin + 1, 2.0 * ch * cout * (2.0 * u) * (double)Lin * B);
       p.mrf = ncur > 1;
       CHECK(run_plan_f16(ctx, w, p, KC_UPSAMPLE, s));
@@ -370,7 +364,7 @@ static int hifigan_body_f16(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const m
       a.y_ld = ldo;
       a.res = res;
       a.cout = ch;
-      h_set_lengths(a, d_frames, voc_host_len, mul, mul);
+      h_set_lengths(a, B, d_frames, voc_host_len, mul, mul);
       return a;
     };
     // in this mode "mrf_group" and "rb_pair" select the grouped / fused launches (as the call saw them at its start)

@@ -360,7 +360,7 @@ static int hifigan_body_f32(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const m
     a.slope = 0.01f;
     a.x_bs = (long long)ch * ldin;
     a.x_ld = ldin;
-    if (B == 1 && voc_host_len >= 0) { a.len = nullptr; a.len_const = voc_host_len * mul; } else { a.len = d_frames; }
+    row_len(B, voc_host_len, d_frames, mul).into(a);
     a.len_mul = mul;
     a.w = hm->arena + hm->post_w_off;
     a.bias = hm->arena + hm->post_b_off;

@@ -25,6 +25,22 @@
 //     solitary call and reports what that returns.
 #pragma once
 
+// GlowTTS, then the vocoder behind it on the same stream, on a freshly acquired worker: the body of every fused call.  The
+// frame counts reach `frames_out` as soon as they are known — before the vocoder's checks can fail (TOO_SMALL reports them).
+// (Pmax: what glow_precheck returned for `g`)
+static int run_fused_call(mi355tts_ctx* ctx, const GlowModel* gm, HifiModel* hm, int vocoder, const GlowCall& g, int Pmax, VocCall& v,
+                          int32_t* frames_out) {
+  Worker* w = nullptr;
+  CHECK(acquire_worker(ctx, &w));
+  WorkerGuard guard{ctx, w};
+  MelDrop drop{w->stream, nullptr};
+  CHECK(glow_run(ctx, w, gm, g, Pmax, false, &drop.m));
+  const mi355tts_mel* mel = drop.m;
+  for (int b = 0; b < g.B; ++b) frames_out[b] = mel->frames[b];
+  CHECK(hifigan_precheck(ctx, hm, vocoder, mel->frames.data(), g.B, mel->M, mel->max_frames, v));
+  return hifigan_run(ctx, w, hm, mel, v);
+}
+
 struct CallReq {
   // request: the arguments of one batch-1 mi355tts_synthesize call
   const GlowModel* gm = nullptr;
@@ -74,15 +90,7 @@ static void call_join_run(mi355tts_ctx* ctx, std::vector<CallReq*>& rows) {
     ld = std::max(ld, (int)rows[b]->len);
   }
   const CallReq& lead = *rows[0];
-  GlowCall c;
-  c.ids = ptrs[0];
-  c.id_lens = lens.data();
-  c.B = n;
-  c.ids_ld = ld;
-  c.noise_scale = lead.noise_scale;
-  c.length_scale = lead.length_scale;
-  c.audio = lead.audio;
-  c.flags = lead.flags & MI355TTS_IN_DEVICE;
+  GlowCall c = glow_call(ptrs[0], lens.data(), n, ld, lead.noise_scale, lead.length_scale, nullptr, 0, 0, lead.audio, lead.flags & MI355TTS_IN_DEVICE);
   if (n > 1) {
     c.row_ids = ptrs.data();
     c.row_seeds = seeds.data();
@@ -93,31 +101,15 @@ static void call_join_run(mi355tts_ctx* ctx, std::vector<CallReq*>& rows) {
   v.denoiser_strength = lead.denoiser_strength;
   v.flags = lead.flags & MI355TTS_OUT_DEVICE;
   v.rows = outs.data();
-  int rc = 0;
+  std::vector<int32_t> frames(n, 0);
   auto run = [&]() -> int {
     int Pmax = 0;
     CHECK(glow_precheck(lead.gm, c, &Pmax));
     HIPCHECK(hipSetDevice(ctx->device));
-    Worker* w = nullptr;
-    CHECK(acquire_worker(ctx, &w));
-    WorkerGuard guard{ctx, w};
-    mi355tts_mel* mel = nullptr;
-    struct MelDrop {
-      Worker* w;
-      mi355tts_mel* m;
-      ~MelDrop() {
-        if (!m) return;
-        mi355_sync(w->stream);  // its blocks go back to the pool: nothing queued may still read them
-        mel_destroy(m);
-      }
-    } drop{w, nullptr};
-    CHECK(glow_run(ctx, w, lead.gm, c, Pmax, false, &mel));
-    drop.m = mel;
-    for (int b = 0; b < n; ++b) rows[b]->frames = mel->frames[b];  // (also on the error returns below: TOO_SMALL reports the real counts)
-    CHECK(hifigan_precheck(ctx, lead.hm, lead.vocoder, mel->frames.data(), n, mel->M, mel->max_frames, v));
-    return hifigan_run(ctx, w, lead.hm, mel, v);
+    return run_fused_call(ctx, lead.gm, lead.hm, lead.vocoder, c, Pmax, v, frames.data());
   };
-  rc = run();
+  const int rc = run();
+  for (int b = 0; b < n; ++b) rows[b]->frames = frames[b];  // (also after an error past the acoustic pass: TOO_SMALL reports the real counts)
   const std::string msg = rc ? g_err : std::string();
   for (int b = 0; b < n; ++b) {
     rows[b]->rc = rc;

@@ -37,6 +37,20 @@ struct ProfScope {
   }
 };
 
+// The row-length rule of every launch: one row whose length the host knows takes it as a launch constant (no dependent load of
+// len[b] in every workgroup's prologue); a batch reads the device array (the kernels ignore len_const when len is non-null).
+struct RowLen {
+  const int* len;
+  int len_const;
+  template <class Args>
+  void into(Args& a) const { a.len = len; a.len_const = len_const; }
+};
+// (dev_const: what a batch's launch carries in the constant's place)
+static inline RowLen row_len(int B, int host_len, const int* dev_len, int mul = 1, int dev_const = 0) {
+  if (B == 1 && host_len >= 0) return {nullptr, host_len * mul};
+  return {dev_len, dev_const};
+}
+
 template <int K, int CI_C, int MB, int NB, int WN, int KS, int HALO, int EPI>
 static void launch_conv_inst(hipStream_t s, dim3 grid, const ConvArgs& a) {
   kn_add(KN_CONV_MFMA);
@@ -161,18 +175,14 @@ static int plan_conv(const CallOptions& o, const DevConv& c, ConvArgs a, int epi
   out->empty = true;
   out->bf16 = 0;
   if (n_max <= 0 || B <= 0) return 0;
-  if (B == 1 && host_len >= 0) {
-    // single utterance: the host already knows the row length, so the kernel need not
-    // start with a dependent global load of len[b]
-    if (a.in_len) {
-      a.in_const = host_len * a.in_mul;
-      a.in_len = nullptr;
-    }
-    if (a.out_len) {
-      a.out_const = host_len * a.out_mul;
-      a.out_len = nullptr;
-    }
-  }
+  // the row-length rule, per side (one that arrives without a length array already carries its constant)
+  auto side = [&](const int*& len, int& len_const, int mul) {
+    if (!len) return;
+    const RowLen r = row_len(B, host_len, len, mul, len_const);
+    len = r.len; len_const = r.len_const;
+  };
+  side(a.in_len, a.in_const, a.in_mul);
+  side(a.out_len, a.out_const, a.out_mul);
   if (epi == EPI_LINEAR && a.split > 0 && a.split < c.rows && (a.split % 32))
     return fail(MI355TTS_ERR_INVALID, "row split %d must be a multiple of 32", a.split);
   a.w = c.w;
@@ -546,9 +556,8 @@ static void plan_pair(const CallOptions& o, const DevConv& c1, const DevConv& c2
   a.y = y;
   a.bs = bs;
   a.ld = ld;
-  a.len = (B == 1 && host_len >= 0) ? nullptr : len;
+  row_len(B, host_len, len, len_mul).into(a);
   a.len_mul = len_mul;
-  a.len_const = host_len * len_mul;
   a.w1 = c1.w;
   a.b1 = c1.bias;
   a.w2 = c2.w;
@@ -649,9 +658,8 @@ static int run_mrf_small(mi355tts_ctx* ctx, Worker* w, const MrfStage& ms, const
   a.y2 = y2;
   a.bs = bs;
   a.ld = ld;
-  a.len = (B == 1 && host_len >= 0) ? nullptr : len;
+  row_len(B, host_len, len, len_mul).into(a);
   a.len_mul = len_mul;
-  a.len_const = host_len * len_mul;
   a.w = arena + ms.w_off;
   a.bias = arena + ms.b_off;
   a.tab = reinterpret_cast<const int*>(arena + ms.t_off);
@@ -729,6 +737,20 @@ struct Lin16Ln {
   int relu;
   float* out;
 };
+// every lin16_kernel<K, J, NBLK, LN, RTW> that is built: J 32-channel groups in, NBLK 16-column blocks per workgroup, LN = the
+// LayerNorm prologue, RTW row tiles per workgroup (4: the wide 1 x 1 form)
+struct Lin16Shape {
+  int K, J, NBLK;
+  bool LN;
+  int RTW;
+};
+constexpr Lin16Shape LIN16_SHAPES[9] = {{1, 6, 2, false, 4}, {1, 6, 2, true, 1}, {5, 6, 2, true, 1}, {3, 8, 2, true, 1}, {3, 6, 2, false, 1},
+                                        {3, 8, 2, false, 1}, {3, 24, 1, false, 1}, {5, 6, 2, false, 1}, {1, 6, 2, false, 1}};
+static int lin16_shape(int K, int J, bool ln, int rtw) {
+  for (int i = 0; i < 9; ++i)
+    if (LIN16_SHAPES[i].K == K && LIN16_SHAPES[i].J == J && LIN16_SHAPES[i].LN == ln && LIN16_SHAPES[i].RTW == rtw) return i;
+  return -1;
+}
 static int run_lin16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const ConvArgs& a, const float* arena, int B, int n_max, int cls,
                      int host_len, bool solo_tiles = false, const Lin16Ln* ln = nullptr) {
   const CallOptions& o = w->opt;
@@ -755,29 +777,22 @@ static int run_lin16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const ConvA
   Lin16Args g;
   std::memset(&g, 0, sizeof(g));
   g.x = a.x; g.x_bs = a.x_bs; g.x_ld = a.x_ld;
-  if (B == 1 && host_len >= 0) { g.len = nullptr; g.len_const = host_len * a.in_mul; } else { g.len = a.in_len; g.len_const = a.in_const; }
+  row_len(B, host_len, a.in_len, a.in_mul, a.in_const).into(g);
   g.len_mul = a.in_mul;
   g.w = arena + c.l16_w_off; g.bias = arena + c.l16_b_off; g.Cin = c.Cin; g.rows = c.rows; g.dil = a.dil; g.pad = a.pad;
   g.y = a.y; g.y_bs = a.y_bs; g.y_ld = a.y_ld; g.res = a.res; g.relu = a.out_act == ACT_RELU;
   g.split = two ? a.split : (1 << 30); g.y2 = a.y2; g.y2_bs = a.y2_bs; g.y2_ld = a.y2_ld; g.accum2 = a.accum2;
+  const int shape = lin16_shape(c.K, c.l16_J, ln != nullptr, wide ? 4 : 1);
+  if (shape < 0) return 1;
   if (ln) {
-    const bool ln_shape = (c.K == 1 && c.l16_J == 6) || (c.K == 5 && c.l16_J == 6) || (c.K == 3 && c.l16_J == 8);
-    if (!ln_shape) return 1;
     g.ln_gamma = ln->gamma; g.ln_beta = ln->beta; g.ln_eps = 1e-4f; g.ln_relu = ln->relu; g.ln_out = ln->out;
   }
   ProfScope ps(ctx, w, cls, 2.0 * (double)c.Cout * c.Cin * c.K * (double)n_max * B);
   const dim3 grid(gx, wide ? gy / 4 : gy, B);
-  hipStream_t s = w->stream;
-  if (wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<1, 6, 2, false, 4>), grid, dim3(512), 0, s, g);
-  else if (ln && c.K == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<1, 6, 2, true>), grid, dim3(512), 0, s, g);
-  else if (ln && c.K == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<5, 6, 2, true>), grid, dim3(512), 0, s, g);
-  else if (ln && c.K == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<3, 8, 2, true>), grid, dim3(512), 0, s, g);
-  else if (c.K == 3 && c.l16_J == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<3, 6, 2>), grid, dim3(512), 0, s, g);
-  else if (c.K == 3 && c.l16_J == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<3, 8, 2>), grid, dim3(512), 0, s, g);
-  else if (c.K == 3 && c.l16_J == 24) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<3, 24, 1>), grid, dim3(512), 0, s, g);
-  else if (c.K == 5 && c.l16_J == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<5, 6, 2>), grid, dim3(512), 0, s, g);
-  else if (c.K == 1 && c.l16_J == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<1, 6, 2>), grid, dim3(512), 0, s, g);
-  else return 1;
+  switch_const<0, 1, 2, 3, 4, 5, 6, 7, 8>(shape, [&](auto i) {
+    constexpr Lin16Shape t = LIN16_SHAPES[decltype(i)::value];
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<t.K, t.J, t.NBLK, t.LN, t.RTW>), grid, dim3(512), 0, w->stream, g);
+  });
   kn_hit(ctx, wide ? KN_LIN16_WIDE : ln ? KN_LIN16_LN : KN_LIN16);
   return 0;
 }

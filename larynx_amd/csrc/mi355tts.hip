@@ -901,11 +901,7 @@ extern "C" int mi355tts_mel_from_buffer(mi355tts_ctx* ctx, const float* mel, con
 // read-back and the final one (the two-call form adds a sync, a worker hand-over and a mel
 // object round trip through the caller).  Replaces the body of `_sentence_task`
 // (larynx/__init__.py:229-283) between the two log lines, pause padding included.
-static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
-                           float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
-                           const int32_t* speaker_ids, const mi355tts_audio_settings* audio, float denoiser_strength,
-                           int32_t pad_before, int32_t pad_after, int32_t* frames_out, float* wav_f32, int16_t* wav_i16,
-                           int64_t wav_ld, uint32_t flags, const mi355tts_prosody* prosody = nullptr) {
+static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const GlowCall& g, VocCall& v, int32_t* frames_out) {
   if (!ctx || !frames_out) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GlowModel> gpin;
   std::shared_ptr<HifiModel> vpin;
@@ -913,53 +909,21 @@ static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const int64
   CHECK(find_hifi(ctx, vocoder, &vpin));
   const GlowModel* gm = gpin.get();
   HifiModel* hm = vpin.get();
-  GlowCall g;
-  g.ids = ids;
-  g.id_lens = id_lens;
-  g.B = B;
-  g.ids_ld = ids_ld;
-  g.noise_scale = noise_scale;
-  g.length_scale = length_scale;
-  g.noise = noise;
-  g.noise_ld = noise_ld;
-  g.seed = seed;
-  g.speaker_ids = speaker_ids;
-  g.audio = audio;
-  g.flags = flags & MI355TTS_IN_DEVICE;
-  g.set_prosody(prosody, false);
-  VocCall v;
-  v.denoiser_strength = denoiser_strength;
-  v.wav_f32 = wav_f32;
-  v.wav_i16 = wav_i16;
-  v.wav_ld = wav_ld;
-  v.flags = flags & MI355TTS_OUT_DEVICE;
-  v.pad_before = pad_before;
-  v.pad_after = pad_after;
   int Pmax = 0;
   CHECK(glow_precheck(gm, g, &Pmax));
-  CHECK(hifigan_precheck(ctx, hm, vocoder, nullptr, B, gm->hp.mel_channels, -1, v));  // incl. the one-time denoiser bias
+  CHECK(hifigan_precheck(ctx, hm, vocoder, nullptr, g.B, gm->hp.mel_channels, -1, v));  // incl. the one-time denoiser bias
   HIPCHECK(hipSetDevice(ctx->device));
   // (decided before a worker, and with it a CallOptions, exists: the one place that reads these options off the context)
   const int lanes = g_env.call_coalesce_off ? 0 : ctx->opts.call_coalesce.load();
-  if (lanes > 0 && B == 1 && !noise && !speaker_ids && !g.has_prosody() && id_lens[0] <= ATTM_MAXP && ctx->opts.voc_out.load() && !ctx->opts.serial_branches.load()) {
+  if (lanes > 0 && g.B == 1 && !g.noise && !g.speaker_ids && !g.has_prosody() && g.id_lens[0] <= ATTM_MAXP && ctx->opts.voc_out.load() && !ctx->opts.serial_branches.load()) {
     // a batch-1 call: it rides a fused padded call with whichever other batch-1 calls are waiting right now (host_join.h)
     CallReq req;
-    req.gm = gm;
-    req.hm = hm;
-    req.vocoder = vocoder;
-    req.ids = ids;
-    req.len = id_lens[0];
-    req.noise_scale = noise_scale;
-    req.length_scale = length_scale;
-    req.seed = seed;
-    req.audio = audio;
-    req.flags = flags & (MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE);
-    req.denoiser_strength = denoiser_strength;
-    req.out.wav_f32 = wav_f32;
-    req.out.wav_i16 = wav_i16;
-    req.out.wav_ld = wav_ld;
-    req.out.pad_before = pad_before;
-    req.out.pad_after = pad_after;
+    req.gm = gm; req.hm = hm; req.vocoder = vocoder;
+    req.ids = g.ids; req.len = g.id_lens[0]; req.seed = g.seed;
+    req.noise_scale = g.noise_scale; req.length_scale = g.length_scale; req.audio = g.audio;
+    req.flags = g.flags | v.flags;
+    req.denoiser_strength = v.denoiser_strength;
+    req.out = {v.wav_f32, v.wav_i16, v.wav_ld, v.pad_before, v.pad_after};
     const int jr = call_join(ctx, req, lanes);
     if (jr <= 0) {
       frames_out[0] = req.frames;
@@ -967,32 +931,26 @@ static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const int64
     }
     // jr == 1: the shared pass failed; this call runs alone below and reports its own result
   }
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  mi355tts_mel* mel = nullptr;
-  struct MelDrop {
-    Worker* w;
-    mi355tts_mel* m;
-    ~MelDrop() {
-      if (!m) return;
-      mi355_sync(w->stream);  // its blocks go back to the pool: nothing queued may still read them
-      mel_destroy(m);
-    }
-  } drop{w, nullptr};
-  CHECK(glow_run(ctx, w, gm, g, Pmax, false, &mel));
-  drop.m = mel;
-  for (int b = 0; b < B; ++b) frames_out[b] = mel->frames[b];
-  CHECK(hifigan_precheck(ctx, hm, vocoder, mel->frames.data(), B, mel->M, mel->max_frames, v));
-  return hifigan_run(ctx, w, hm, mel, v);
+  return run_fused_call(ctx, gm, hm, vocoder, g, Pmax, v, frames_out);
+}
+// the vocoder side of a fused entry point's arguments (`flags` carries both sides' residency bits)
+static VocCall synth_voc_call(float denoiser_strength, int32_t pad_before, int32_t pad_after, float* wav_f32, int16_t* wav_i16, int64_t wav_ld,
+                              uint32_t flags) {
+  VocCall v;
+  v.denoiser_strength = denoiser_strength;
+  v.wav_f32 = wav_f32; v.wav_i16 = wav_i16; v.wav_ld = wav_ld;
+  v.flags = flags & MI355TTS_OUT_DEVICE;
+  v.pad_before = pad_before; v.pad_after = pad_after;
+  return v;
 }
 extern "C" int mi355tts_synthesize(mi355tts_ctx* ctx, int glow, int vocoder, const int64_t* ids, const int32_t* id_lens, int B,
                                    int ids_ld, float noise_scale, float length_scale, const float* noise, int noise_ld,
                                    uint64_t seed, const mi355tts_audio_settings* audio, float denoiser_strength,
                                    int32_t pad_before, int32_t pad_after, int32_t* frames_out, float* wav_f32, int16_t* wav_i16,
                                    int64_t wav_ld, uint32_t flags) {
-  return synthesize_impl(ctx, glow, vocoder, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, nullptr, audio,
-                         denoiser_strength, pad_before, pad_after, frames_out, wav_f32, wav_i16, wav_ld, flags);
+  const GlowCall g = glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, audio, flags & MI355TTS_IN_DEVICE);
+  VocCall v = synth_voc_call(denoiser_strength, pad_before, pad_after, wav_f32, wav_i16, wav_ld, flags);
+  return synthesize_impl(ctx, glow, vocoder, g, v, frames_out);
 }
 // the same for a multi-speaker voice (larynx/glow_tts.py:116-130: the `speaker_id` setting)
 extern "C" int mi355tts_synthesize_speakers(mi355tts_ctx* ctx, int glow, int vocoder, const int64_t* ids, const int32_t* id_lens, int B,
@@ -1001,8 +959,10 @@ extern "C" int mi355tts_synthesize_speakers(mi355tts_ctx* ctx, int glow, int voc
                                             float denoiser_strength, int32_t pad_before, int32_t pad_after, int32_t* frames_out,
                                             float* wav_f32, int16_t* wav_i16, int64_t wav_ld, uint32_t flags) {
   if (!speaker_ids) return fail(MI355TTS_ERR_INVALID, "speaker_ids null");
-  return synthesize_impl(ctx, glow, vocoder, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, speaker_ids, audio,
-                         denoiser_strength, pad_before, pad_after, frames_out, wav_f32, wav_i16, wav_ld, flags);
+  GlowCall g = glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, audio, flags & MI355TTS_IN_DEVICE);
+  g.speaker_ids = speaker_ids;
+  VocCall v = synth_voc_call(denoiser_strength, pad_before, pad_after, wav_f32, wav_i16, wav_ld, flags);
+  return synthesize_impl(ctx, glow, vocoder, g, v, frames_out);
 }
 
 // the same with per-id timing control and read-out (mi355tts_prosody); speaker_ids NULL for a single-speaker voice
@@ -1012,8 +972,11 @@ extern "C" int mi355tts_synthesize_prosody(mi355tts_ctx* ctx, int glow, int voco
                                            float denoiser_strength, int32_t pad_before, int32_t pad_after, int32_t* frames_out,
                                            float* wav_f32, int16_t* wav_i16, int64_t wav_ld, uint32_t flags,
                                            const mi355tts_prosody* prosody) {
-  return synthesize_impl(ctx, glow, vocoder, ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, speaker_ids, audio,
-                         denoiser_strength, pad_before, pad_after, frames_out, wav_f32, wav_i16, wav_ld, flags, prosody);
+  GlowCall g = glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, audio, flags & MI355TTS_IN_DEVICE);
+  g.speaker_ids = speaker_ids;
+  g.set_prosody(prosody, false);
+  VocCall v = synth_voc_call(denoiser_strength, pad_before, pad_after, wav_f32, wav_i16, wav_ld, flags);
+  return synthesize_impl(ctx, glow, vocoder, g, v, frames_out);
 }
 
 // Pre-create `workers` workers (streams, pinned staging, side streams) and size their

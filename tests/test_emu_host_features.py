@@ -2,6 +2,7 @@
 `mi355tts_synthesize` call, device-side pause padding, `mi355tts_reserve`, the
 load-adaptive vocoder schedule, unusual-but-legal vocoder configurations and
 hyper-parameter validation (round-1 advisor findings)."""
+import dataclasses
 import threading
 
 import numpy as np
@@ -264,6 +265,43 @@ def check_seeded_path_equals_injected_noise(eng, g, num_symbols, channels, lens=
     finally:
         seeded.free()
         injected.free()
+
+
+def check_workspace_growth_keeps_live_buffers(make_engine, length_scale=60.0):
+    """The decoder's workspace is appended to the encoder's; when that outgrows the worker's arena the arena moves, the encoder's
+    region is carried over and every pointer into it is bound again (csrc/glow_forward.h: glow_dec_workspace).  A FRESH engine
+    (empty arenas) runs a multi-speaker batch with per-row seeds, noise and `id_scales` — every optional encoder buffer live:
+    the first arena is sized for the encoder (its few KB + 1 MiB of slack), and `length_scale` stretches the rows until the
+    decoder's planes need more than twice that, so the first call grows and restores.  The identical second call finds the
+    arena grown.  Both must give the same bits, frame counts and durations."""
+    hp = dataclasses.replace(HP.TINY_GLOW, mel_channels=8, n_speakers=3, gin_channels=20)  # hidden 32, 2 blocks x 2 layers
+    eng = make_engine()
+    try:
+        g = eng.load_glow(hp, synthetic.make_glow_state_dict(hp, seed=21))
+        rng = np.random.default_rng(77)
+        ids = [synthetic.synthetic_phoneme_ids(rng, n, hp.num_symbols) for n in (9, 23)]
+        scales = [np.linspace(0.5, 1.7, len(r)).astype(np.float32) for r in ids]
+        out = []
+        for _ in range(2):
+            mel = eng.glow_infer(g, ids, 0.667, length_scale, row_seeds=[11, 77], speaker_ids=[2, 0], id_scales=scales)
+            out.append((mel.numpy("raw"), np.array(mel.frames), mel.durations.copy()))
+            mel.free()
+        (raw0, fr0, du0), (raw1, fr1, du1) = out
+        # the first call did outgrow its first arena: z, h, acts, skip — [B][C + 3 H][frames / n_sqz] floats — against 1 MiB + the
+        # encoder's region (< 64 KB at these sizes) + an eighth
+        C = hp.mel_channels * hp.n_sqz
+        assert 4 * len(ids) * (C + 3 * hp.hidden_channels) * (int(fr0.max()) // hp.n_sqz) > 2 * (1 << 20)
+        assert fr0.min() > 0 and np.array_equal(fr0, fr1) and np.array_equal(du0, du1)
+        assert np.array_equal(du0.sum(axis=1), fr0)
+        assert np.array_equal(raw0, raw1)
+    finally:
+        eng.close()
+
+
+def test_workspace_growth_keeps_live_buffers(emu_library):
+    from larynx_amd.engine import Engine
+
+    check_workspace_growth_keeps_live_buffers(lambda: Engine(device=0, library_path=emu_library))
 
 
 def test_seeded_path_equals_injected_noise(emu_engine, tiny):

@@ -350,6 +350,13 @@ def test_seeded_path_equals_injected_noise(gpu_engine):
     check_seeded_path_equals_injected_noise(gpu_engine, g, hp.num_symbols, hp.mel_channels, lens=(120, 47, 90), seed=99)
 
 
+def test_workspace_growth_keeps_live_buffers():
+    from larynx_amd.engine import Engine
+    from tests.test_emu_host_features import check_workspace_growth_keeps_live_buffers
+
+    check_workspace_growth_keeps_live_buffers(lambda: Engine(device=0))
+
+
 def test_glowtts_launch_counts_on_the_device(gpu_engine):
     """The fused GlowTTS schedule is the one that runs for the released voices' shape: 97 decoder launches (1 start + 12 x (4
     gate convs + 3 res_skip + 1 tail)), 31 encoder conv launches, 12 small kernels per utterance — a shape check that silently
