@@ -36,35 +36,33 @@ static std::string hifi_f16_unsupported(const mi355tts_hifigan_hparams& h) {
   return "";
 }
 
-struct HPackSink {
-  std::vector<uint16_t> w;  // the fp16 arena (host)
-  ArenaBuilder* ab;         // biases ride in the model's float arena
-  HConvW add(const PackedConvH& p, int Cin) {
-    HConvW d;
-    d.w_off = (w.size() + 127) & ~(size_t)127;  // 256-byte alignment
-    w.resize(d.w_off + p.w.size());
-    std::memcpy(w.data() + d.w_off, p.w.data(), p.w.size() * sizeof(uint16_t));
-    d.b_off = ab->add(p.bias);
-    d.mtiles = p.mtiles;
-    d.nslab = p.nslab;
-    d.K = p.K;
-    d.rows = p.rows;
-    d.Cin = Cin;
-    return d;
-  }
-};
+// one conv into the fp16 arena; its f32 bias rides in the model's float arena
+static HConvW add_h(ModelPacker& pk, const PackedConvH& p, int Cin) {
+  HConvW d;
+  d.w_off = ModelPacker::add16(pk.f16, p.w);
+  d.b_off = pk.add(p.bias);
+  d.mtiles = p.mtiles;
+  d.nslab = p.nslab;
+  d.K = p.K;
+  d.rows = p.rows;
+  d.Cin = Cin;
+  return d;
+}
 // a plain conv w[Cout][Cin][K]
-static HConvW add_conv_h(HPackSink& sk, const float* w, const float* bias, int Cout, int Cin, int K) {
-  return sk.add(pack_conv_f16(
+static HConvW add_conv_h(ModelPacker& pk, const float* w, const float* bias, int Cout, int Cin, int K) {
+  return add_h(pk, pack_conv_f16(
                     Cout, 4, Cin, K, 64, [&](int v, int ci, int k) { return w[((size_t)v * Cin + ci) * K + k]; }, [&](int v) { return bias[v]; },
                     bias != nullptr),
                 Cin);
 }
 // ConvTranspose1d(Cin, Cout, 2 u, stride u, padding u / 2) in polyphase form: virtual row v = r * Cout + co (phase-major), two
-// taps over q, tap k reads x[q + k - 1] and carries Wt[ci][co][(1 - k) u + r]  (see add_conv's ROWS_UPSAMPLE for the derivation)
-static HConvW add_ups_h(HPackSink& sk, const float* wt, const float* bias, int Cout, int Cin, int u) {
+// taps over q, tap k reads x[q + k - 1] and carries Wt[ci][co][(1 - k) u + r]  (see PolyphaseW for the derivation).  Not
+// PolyphaseW's row order: the fp16 planes hold 8 channels per 16-byte unit, so a lane's 4 consecutive rows must be 4
+// consecutive channels of ONE output sample (conv_f16.h, EPI_UPSAMPLE); the f32 and split-bf16 tiles write rows of time and
+// keep a channel's u phases together.
+static HConvW add_ups_h(ModelPacker& pk, const float* wt, const float* bias, int Cout, int Cin, int u) {
   const int Ku = 2 * u;
-  return sk.add(pack_conv_f16(
+  return add_h(pk, pack_conv_f16(
                     Cout * u, 4, Cin, 2, 64,
                     [&](int v, int ci, int k) {
                       const int r = v / Cout, co = v % Cout, m = 1 - k;
@@ -83,25 +81,21 @@ static std::string glow_f16_unsupported(const mi355tts_glow_hparams& h) {
   return "";
 }
 // in_layers[j]: w [2H][H][K]; virtual 32-row tile p = the tanh rows of channels 16 p .. 16 p + 15, then their sigmoid rows
-static HConvW add_wn_gate_h(HPackSink& sk, const float* w, const float* bias, int H, int K) {
+static HConvW add_wn_gate_h(ModelPacker& pk, const float* w, const float* bias, int H, int K) {
   auto row_of = [H](int v) {
     const int p = v / 32, i = v % 32, c = 16 * p + (i & 15);
     return i < 16 ? c : H + c;
   };
-  return sk.add(pack_conv_f16(
+  return add_h(pk, pack_conv_f16(
                     2 * H, 1, H, K, 32, [&](int v, int ci, int k) { return w[((size_t)row_of(v) * H + ci) * K + k]; },
                     [&](int v) { return bias[row_of(v)]; }, true),
                 H);
 }
 // res_skip_layers[j] (j < n - 1): w [2H][H][1], rows in natural order [res | skip]
-static HConvW add_wn_rs_h(HPackSink& sk, const float* w, const float* bias, int H) {
-  return sk.add(pack_conv_f16(
+static HConvW add_wn_rs_h(ModelPacker& pk, const float* w, const float* bias, int H) {
+  return add_h(pk, pack_conv_f16(
                     2 * H, 1, H, 1, 32, [&](int v, int ci, int) { return w[(size_t)v * H + ci]; }, [&](int v) { return bias[v]; }, true),
                 H);
-}
-static void fix_h(HConvW& c, const uint16_t* arenaH, const float* arena) {
-  c.w = reinterpret_cast<const uint4*>(arenaH + c.w_off);
-  c.bias = arena + c.b_off;
 }
 
 // ------------------------------------------------------------------ tiles

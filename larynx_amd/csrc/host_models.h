@@ -63,7 +63,48 @@ struct ArenaBuilder {
   size_t add(const std::vector<float>& v) { return add(v.data(), v.size()); }
 };
 
+// The host side of a model's three device arenas while a loader packs it (host_load.h): f32 fragments, biases and tables; the
+// split-bf16 fragments (conv_bf16.h); the fp16 fragments (conv_f16.h, wn_f16.h).  The single operators pack into an
+// ArenaBuilder alone.
+struct ModelPacker {
+  ArenaBuilder f32;
+  std::vector<uint16_t> bf16, f16;
+  size_t add(const float* p, size_t n) { return f32.add(p, n); }
+  size_t add(const std::vector<float>& v) { return f32.add(v); }
+  // the 16-bit arenas' one rule: every block starts on 256 bytes; returns its offset in elements
+  static size_t add16(std::vector<uint16_t>& arena, const std::vector<uint16_t>& v) {
+    const size_t off = (arena.size() + 127) & ~(size_t)127;
+    arena.resize(off + v.size());
+    if (!v.empty()) std::memcpy(arena.data() + off, v.data(), v.size() * sizeof(uint16_t));
+    return off;
+  }
+  // allocate the device arenas, copy, and bind every conv of the model (defined in host_load.h)
+  template <class Model>
+  int upload(mi355tts_ctx* ctx, Model& model);
+};
+
+// device bases of the three arenas (a model's, or a worker's workspace with the float part alone)
+struct ArenaPtrs {
+  const float* f32 = nullptr;
+  const uint16_t* bf16 = nullptr;
+  const uint16_t* f16 = nullptr;
+};
+
 enum RowLayout { ROWS_PLAIN, ROWS_PAIR, ROWS_UPSAMPLE };
+
+// ConvTranspose1d(Cin, Cout, Ku, stride u, padding (Ku-u)/2) as a Kt = Ku/u tap conv over q with virtual rows v = co*u + r
+// (channel-major: a row tile holds whole channels, which the f32 and split-bf16 epilogues scatter to q*u + r):
+//   out[co][q*u + r - p] = sum_ci sum_m x[ci][q - m] * Wt[ci][co][m*u + r]
+// tap k reads x[q + k - (Kt-1)], i.e. m = Kt-1-k.  (The fp16 form orders its rows phase-major: add_ups_h.)
+struct PolyphaseW {
+  const float* wt;  // [Cin][Cout][Ku]
+  int Cout, Ku, u;
+  float operator()(int v, int ci, int k) const {
+    const int co = v / u, r = v % u;
+    const int m = Ku / u - 1 - k;
+    return wt[((size_t)ci * Cout + co) * Ku + m * u + r];
+  }
+};
 
 // Pack a logical conv weight w[Cout][Cin][K] (or, for ROWS_UPSAMPLE, the
 // transposed-conv weight w[Cin][Cout][Ku]) into the arena.
@@ -97,22 +138,12 @@ static DevConv add_conv(ArenaBuilder& ab, const float* w, const float* bias, int
         [&](int co, int ci, int k) { return w[((size_t)co * Cin + ci) * K + k]; }, [&](int co) { return bias[co]; },
         d.has_bias, 8);
   } else {
-    // ConvTranspose1d(Cin, Cout, Ku, stride u, padding (Ku-u)/2) as a Kt = Ku/u tap
-    // conv over q with virtual rows v = co*u + r:
-    //   out[co][q*u + r - p] = sum_ci sum_m x[ci][q - m] * Wt[ci][co][m*u + r]
-    // tap k reads x[q + k - (Kt-1)], i.e. m = Kt-1-k.
     const int u = half_or_up;
     const int Ku = K;  // caller passes the transposed kernel size in K
-    const int Kt = Ku / u;
     d.MB = (Cout * u) <= 32 ? 1 : 2;
     p = pack_conv(
-        Cout * u, d.MB, Cin, Kt, [&](int v) { return v; },
-        [&](int v, int ci, int k) {
-          const int co = v / u, r = v % u;
-          const int m = Kt - 1 - k;
-          return w[((size_t)ci * Cout + co) * Ku + m * u + r];
-        },
-        [&](int v) { return bias[v / u]; }, d.has_bias, 8);
+        Cout * u, d.MB, Cin, Ku / u, [&](int v) { return v; }, PolyphaseW{w, Cout, Ku, u}, [&](int v) { return bias[v / u]; },
+        d.has_bias, 8);
   }
   d.mtiles = p.mtiles;
   d.noct = p.noct;
@@ -167,24 +198,6 @@ static void add_lin16(ArenaBuilder& ab, DevConv& d, const float* w, const float*
   d.l16_b_off = ab.add(p.bias);
 }
 
-struct Blob {
-  const float* p;
-  int64_t n;
-  int64_t pos = 0;
-  std::vector<std::pair<std::string, int64_t>> manifest;
-  size_t idx = 0;
-  const float* take(const char* name, int64_t numel) {
-    if (idx >= manifest.size() || manifest[idx].first != name || manifest[idx].second != numel || pos + numel > n) {
-      fail(MI355TTS_ERR_INVALID, "weight blob does not match manifest at '%s'", name);
-      return nullptr;
-    }
-    const float* r = p + pos;
-    pos += numel;
-    idx++;
-    return r;
-  }
-};
-
 // one conv of the fp16 modes (conv_f16.h, wn_f16.h): fp16 A fragments in the model's fp16 arena, f32 bias in the float arena
 struct HConvW {
   size_t w_off = 0, b_off = 0;  // uint16 elements into arenaH; floats into the model arena
@@ -195,8 +208,34 @@ struct HConvW {
 struct HResConv {
   HConvW c1, c2;
 };
+
+// Point a packed conv's cached pointers at the arenas its offsets index.  A conv that was never packed (mtiles == 0: the c2 of
+// a ResBlock2 step, pre_proj without a prenet) stays all-null; so does a packing the conv's shape did not get — plan_conv and
+// plan_pair branch on w16, run_gate16 on g16_J.
+static void bind(DevConv& c, const ArenaPtrs& a) {
+  if (!c.mtiles) return;
+  c.w = a.f32 + c.w_off;
+  c.bias = c.has_bias ? a.f32 + c.b_off : nullptr;
+  c.w16 = c.mtiles16 ? (const void*)(a.bf16 + c.w16_off) : nullptr;
+  if (c.g16_J) {
+    c.g16_w = a.f32 + c.g16_w_off;
+    c.g16_b = a.f32 + c.g16_b_off;
+  }
+}
+static void bind(HConvW& c, const ArenaPtrs& a) {
+  if (!c.mtiles) return;
+  c.w = reinterpret_cast<const uint4*>(a.f16 + c.w_off);
+  c.bias = a.f32 + c.b_off;
+}
+
+// each_conv(f) of a model (and of the parts it is made of) calls f on every DevConv and every HConvW it owns: it is how
+// ModelPacker::upload binds them.  A new conv member is added to its struct's each_conv and nowhere else.
 struct GlowLayer {
   DevConv qkv, o, ffn1, ffn2;
+  template <class F>
+  void each_conv(F&& f) {
+    f(qkv), f(o), f(ffn1), f(ffn2);
+  }
   size_t ek, ev, g1, b1, g2, b2;
   DevCol o16;  // conv_o once more, packed for oproj_ln_kernel (coltile.h)
 };
@@ -208,6 +247,14 @@ struct GlowBlock {
   DevCol t_rs, t_end, t_st;
   // fp16 packings of the WaveNet for wn_f16_kernel: in_layers (rows paired per 32-row tile), res_skip_layers[0 .. n - 2]
   std::vector<HConvW> h_in, h_rs;
+  template <class F>
+  void each_conv(F&& f) {
+    f(start), f(end);
+    for (auto& c : in) f(c);
+    for (auto& c : rs) f(c);
+    for (auto& c : h_in) f(c);
+    for (auto& c : h_rs) f(c);
+  }
 };
 // Models are handed out as shared_ptr pins: a call keeps its models alive for its whole duration, mi355tts_unload only
 // drops the context's reference, and the device memory goes when the last call that uses the model has returned.
@@ -225,21 +272,29 @@ struct DeviceScope {
   }
 };
 
-struct GlowModel {
-  mi355tts_glow_hparams hp;
+// the device arenas of a model, filled by ModelPacker::upload: f32 (fragments, biases, tables), split-bf16 fragments of the
+// vocoder's ResBlock and upsampler convs, fp16 fragments of the fp16 modes (the last two only where something was packed)
+struct ModelArenas {
   int device = 0;
   float* arena = nullptr;
+  uint16_t* arena16 = nullptr;
+  uint16_t* arenaH = nullptr;
+  ArenaPtrs ptrs() const { return {arena, arena16, arenaH}; }
+  ~ModelArenas() {
+    DeviceScope ds(device);
+    if (arena) hipFree(arena);
+    if (arena16) hipFree(arena16);
+    if (arenaH) hipFree(arenaH);
+  }
+};
+
+struct GlowModel : ModelArenas {
+  mi355tts_glow_hparams hp;
   // the `half` switch: MI355TTS_PRECISION_F16 = the decoder's WaveNets in fp16 (wn_f16.h) when the geometry is covered
   // (f16_ok; f16_why says what is not); everything else of the acoustic model computes in f32 in every mode
   std::atomic<int> precision{0};
-  uint16_t* arenaH = nullptr;
   bool f16_ok = false;
   std::string f16_why;
-  ~GlowModel() {
-    DeviceScope ds(device);
-    if (arena) hipFree(arena);
-    if (arenaH) hipFree(arenaH);
-  }
   size_t emb;
   std::vector<DevConv> pre_conv;
   std::vector<size_t> pre_g, pre_b;
@@ -253,6 +308,14 @@ struct GlowModel {
   // [Fd][gin][k]; the flow blocks' cond_layer weights [n_blocks][2H n_layers][gin] and biases [n_blocks][2H n_layers]
   size_t emb_g = 0, dp_wg = 0, cond_w = 0, cond_b = 0;
   int gin() const { return hp.n_speakers > 1 ? hp.gin_channels : 0; }
+  template <class F>
+  void each_conv(F&& f) {
+    for (auto& c : pre_conv) f(c);
+    f(pre_proj);
+    for (auto& L : layers) L.each_conv(f);
+    f(proj_m), f(dp1), f(dp2), f(dpp);
+    for (auto& B : blocks) B.each_conv(f);
+  }
 };
 struct HifiResConv {
   DevConv c1, c2;
@@ -268,14 +331,10 @@ struct MrfStage {
   int dil[3][MRF_MAX_STEPS] = {};
   double mac_per_col = 0;  // algorithmic MACs per output column (all 18 convs)
 };
-struct HifiModel {
+struct HifiModel : ModelArenas {
   mi355tts_hifigan_hparams hp;
-  int device = 0;
-  float* arena = nullptr;
-  uint16_t* arena16 = nullptr;  // split-bf16 weight fragments of the ResBlock convs
   // the native fp16 mode (MI355TTS_PRECISION_F16): every conv of the generator packed for conv_f16.h; f16_ok = the model's
   // geometry is one the fp16 tiles cover (f16_why says what is not)
-  uint16_t* arenaH = nullptr;
   bool f16_ok = false;
   std::string f16_why;
   HConvW h_pre;
@@ -292,6 +351,18 @@ struct HifiModel {
   std::vector<std::vector<std::vector<HifiResConv>>> rb;
   std::vector<MrfStage> mrf;  // per stage
   int hop = 1;
+  template <class F>
+  void each_conv(F&& f) {
+    f(pre), f(post), f(h_pre);
+    for (auto& c : ups) f(c);
+    for (auto& c : h_ups) f(c);
+    for (auto& st : rb)
+      for (auto& chain : st)
+        for (auto& rc : chain) f(rc.c1), f(rc.c2);
+    for (auto& st : h_rb)
+      for (auto& chain : st)
+        for (auto& rc : chain) f(rc.c1), f(rc.c2);
+  }
   // denoiser bias spectrum |STFT(generator(zeros))|[:, 0] (larynx/hifi_gan.py:181-203), built on first use
   // one per arithmetic: [0] the f32-plane modes, [1] the fp16 mode (the reference derives the bias from the model it runs,
   // half or not: larynx/hifi_gan.py:181-203)
@@ -300,9 +371,6 @@ struct HifiModel {
   bool bias_ready[2] = {false, false};
   ~HifiModel() {
     DeviceScope ds(device);
-    if (arena) hipFree(arena);
-    if (arena16) hipFree(arena16);
-    if (arenaH) hipFree(arenaH);
     for (float* b : bias_spec)
       if (b) hipFree(b);
   }

@@ -53,6 +53,7 @@ using namespace mi355tts;
 #include "host_group.h"
 #include "host_launch.h"
 #include "hifigan_f16.h"
+#include "host_load.h"
 
 // ------------------------------------------------------------------ C ABI: basics
 extern "C" int mi355tts_abi_version(void) { return MI355TTS_ABI_VERSION; }
@@ -149,282 +150,36 @@ static int check_hifi_hp(const mi355tts_hifigan_hparams* h) {
   return 0;
 }
 
-extern "C" int mi355tts_glow_manifest(const mi355tts_glow_hparams* hp, int index, char* name, int cap, int64_t* numel) {
-  CHECK(check_glow_hp(hp));
-  auto m = glow_manifest(*hp);
+// entry `index` of a manifest: 0 with the name and size, 1 past the end
+static int manifest_entry(const std::vector<std::pair<std::string, int64_t>>& m, int index, char* name, int cap, int64_t* numel) {
   if (index < 0) return fail(MI355TTS_ERR_INVALID, "negative index");
   if ((size_t)index >= m.size()) return 1;
   copy_name(m[index].first, name, cap);
   if (numel) *numel = m[index].second;
   return 0;
+}
+extern "C" int mi355tts_glow_manifest(const mi355tts_glow_hparams* hp, int index, char* name, int cap, int64_t* numel) {
+  CHECK(check_glow_hp(hp));
+  return manifest_entry(glow_manifest(*hp), index, name, cap, numel);
 }
 extern "C" int mi355tts_hifigan_manifest(const mi355tts_hifigan_hparams* hp, int index, char* name, int cap, int64_t* numel) {
   CHECK(check_hifi_hp(hp));
-  auto m = hifigan_manifest(*hp);
-  if (index < 0) return fail(MI355TTS_ERR_INVALID, "negative index");
-  if ((size_t)index >= m.size()) return 1;
-  copy_name(m[index].first, name, cap);
-  if (numel) *numel = m[index].second;
-  return 0;
-}
-
-static int fetch_blob(mi355tts_ctx* ctx, const float* blob, int64_t numel, int on_device, std::vector<float>& host,
-                      const float** p) {
-  if (!on_device) {
-    *p = blob;
-    return 0;
-  }
-  HIPCHECK(hipSetDevice(ctx->device));
-  host.resize((size_t)numel);
-  HIPCHECK(hipMemcpy(host.data(), blob, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-  *p = host.data();
-  return 0;
-}
-
-static int upload_arena(mi355tts_ctx* ctx, ArenaBuilder& ab, float** dev) {
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipError_t e = hipMalloc(dev, ab.host.size() * sizeof(float) + 256);
-  if (e != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc model arena: %s", hipGetErrorString(e));
-  HIPCHECK(hipMemcpy(*dev, ab.host.data(), ab.host.size() * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
-}
-static void fix(DevConv& c, const float* arena) {
-  c.w = arena + c.w_off;
-  c.bias = c.has_bias ? arena + c.b_off : nullptr;
-  if (c.g16_J) {
-    c.g16_w = arena + c.g16_w_off;
-    c.g16_b = arena + c.g16_b_off;
-  }
+  return manifest_entry(hifigan_manifest(*hp), index, name, cap, numel);
 }
 
 extern "C" int mi355tts_load_glow(mi355tts_ctx* ctx, const mi355tts_glow_hparams* hp, const float* blob, int64_t numel,
                                   int on_device, int* model_out) {
   if (!ctx || !blob || !model_out) return fail(MI355TTS_ERR_INVALID, "null argument");
   CHECK(check_glow_hp(hp));
-  const mi355tts_glow_hparams& h = *hp;
-  std::vector<float> tmp;
-  Blob bl;
-  CHECK(fetch_blob(ctx, blob, numel, on_device, tmp, &bl.p));
-  bl.n = numel;
-  bl.manifest = glow_manifest(h);
-  int64_t total = 0;
-  for (auto& kv : bl.manifest) total += kv.second;
-  if (total != numel) return fail(MI355TTS_ERR_INVALID, "GlowTTS blob has %lld floats, manifest needs %lld", (long long)numel, (long long)total);
-
+  std::vector<float> host;
+  BlobReader r;
+  CHECK(open_blob(ctx, "GlowTTS", glow_manifest(*hp), blob, numel, on_device, host, &r));
   auto gm = std::make_shared<GlowModel>();
-  gm->hp = h;
   gm->device = ctx->device;
-  ArenaBuilder ab;
-  const int H = h.hidden_channels, Fc = h.filter_channels, Fd = h.filter_channels_dp, M = h.mel_channels;
-  const int k = h.kernel_size, dk = H / h.n_heads, nrel = 2 * h.window_size + 1;
-#define TAKE(var, name, n)                         \
-  const float* var = bl.take((name).c_str(), (n)); \
-  if (!var) return MI355TTS_ERR_INVALID;
-  {
-    TAKE(emb, std::string("encoder.emb.weight"), (int64_t)h.num_symbols * H);
-    gm->emb = ab.add(emb, (size_t)h.num_symbols * H);
-  }
-  if (gm->gin()) {
-    TAKE(eg, std::string("emb_g.weight"), (int64_t)h.n_speakers * gm->gin());
-    gm->emb_g = ab.add(eg, (size_t)h.n_speakers * gm->gin());
-  }
-  if (h.prenet) {
-    for (int i = 0; i < h.prenet_layers; ++i) {
-      std::string p = "encoder.pre.conv_layers." + std::to_string(i);
-      std::string q = "encoder.pre.norm_layers." + std::to_string(i);
-      TAKE(w, p + ".weight", (int64_t)H * H * h.prenet_kernel_size);
-      TAKE(b, p + ".bias", H);
-      TAKE(g, q + ".gamma", H);
-      TAKE(be, q + ".beta", H);
-      gm->pre_conv.push_back(add_conv(ab, w, b, H, H, h.prenet_kernel_size, ROWS_PLAIN));
-      add_lin16(ab, gm->pre_conv.back(), w, b, H, H, h.prenet_kernel_size);
-      gm->pre_g.push_back(ab.add(g, H));
-      gm->pre_b.push_back(ab.add(be, H));
-    }
-    TAKE(w, std::string("encoder.pre.proj.weight"), (int64_t)H * H);
-    TAKE(b, std::string("encoder.pre.proj.bias"), H);
-    gm->pre_proj = add_conv(ab, w, b, H, H, 1, ROWS_PLAIN);
-    add_lin16(ab, gm->pre_proj, w, b, H, H, 1);
-  }
-  for (int l = 0; l < h.n_layers_enc; ++l) {
-    GlowLayer L;
-    std::string a = "encoder.encoder.attn_layers." + std::to_string(l);
-    TAKE(ek, a + ".emb_rel_k", (int64_t)nrel * dk);
-    TAKE(ev, a + ".emb_rel_v", (int64_t)nrel * dk);
-    TAKE(wq, a + ".conv_q.weight", (int64_t)H * H);
-    TAKE(bq, a + ".conv_q.bias", H);
-    TAKE(wk, a + ".conv_k.weight", (int64_t)H * H);
-    TAKE(bk, a + ".conv_k.bias", H);
-    TAKE(wv, a + ".conv_v.weight", (int64_t)H * H);
-    TAKE(bv, a + ".conv_v.bias", H);
-    TAKE(wo, a + ".conv_o.weight", (int64_t)H * H);
-    TAKE(bo, a + ".conv_o.bias", H);
-    // q, k, v share their input: one GEMM with 3H output rows (attentions.py:205-207)
-    std::vector<float> wqkv((size_t)3 * H * H), bqkv((size_t)3 * H);
-    std::memcpy(wqkv.data(), wq, sizeof(float) * H * H);
-    std::memcpy(wqkv.data() + (size_t)H * H, wk, sizeof(float) * H * H);
-    std::memcpy(wqkv.data() + (size_t)2 * H * H, wv, sizeof(float) * H * H);
-    std::memcpy(bqkv.data(), bq, sizeof(float) * H);
-    std::memcpy(bqkv.data() + H, bk, sizeof(float) * H);
-    std::memcpy(bqkv.data() + 2 * H, bv, sizeof(float) * H);
-    L.qkv = add_conv(ab, wqkv.data(), bqkv.data(), 3 * H, H, 1, ROWS_PLAIN);
-    add_lin16(ab, L.qkv, wqkv.data(), bqkv.data(), 3 * H, H, 1);
-    L.o = add_conv(ab, wo, bo, H, H, 1, ROWS_PLAIN);
-    L.o16 = add_col16(ab, wo, bo, H, H);
-    L.ek = ab.add(ek, (size_t)nrel * dk);
-    L.ev = ab.add(ev, (size_t)nrel * dk);
-    TAKE(g1, "encoder.encoder.norm_layers_1." + std::to_string(l) + ".gamma", H);
-    TAKE(b1, "encoder.encoder.norm_layers_1." + std::to_string(l) + ".beta", H);
-    L.g1 = ab.add(g1, H);
-    L.b1 = ab.add(b1, H);
-    std::string f = "encoder.encoder.ffn_layers." + std::to_string(l);
-    TAKE(w1, f + ".conv_1.weight", (int64_t)Fc * H * k);
-    TAKE(c1, f + ".conv_1.bias", Fc);
-    TAKE(w2, f + ".conv_2.weight", (int64_t)H * Fc * k);
-    TAKE(c2, f + ".conv_2.bias", H);
-    L.ffn1 = add_conv(ab, w1, c1, Fc, H, k, ROWS_PLAIN);
-    L.ffn2 = add_conv(ab, w2, c2, H, Fc, k, ROWS_PLAIN);
-    add_lin16(ab, L.ffn1, w1, c1, Fc, H, k);
-    add_lin16(ab, L.ffn2, w2, c2, H, Fc, k);
-    TAKE(g2, "encoder.encoder.norm_layers_2." + std::to_string(l) + ".gamma", H);
-    TAKE(b2, "encoder.encoder.norm_layers_2." + std::to_string(l) + ".beta", H);
-    L.g2 = ab.add(g2, H);
-    L.b2 = ab.add(b2, H);
-    gm->layers.push_back(L);
-  }
-  {
-    TAKE(w, std::string("encoder.proj_m.weight"), (int64_t)M * H);
-    TAKE(b, std::string("encoder.proj_m.bias"), M);
-    gm->proj_m = add_conv(ab, w, b, M, H, 1, ROWS_PLAIN);
-    add_lin16(ab, gm->proj_m, w, b, M, H, 1);
-    TAKE(w1, std::string("encoder.proj_w.conv_1.weight"), (int64_t)Fd * (H + gm->gin()) * k);
-    TAKE(b1, std::string("encoder.proj_w.conv_1.bias"), Fd);
-    TAKE(g1, std::string("encoder.proj_w.norm_1.gamma"), Fd);
-    TAKE(e1, std::string("encoder.proj_w.norm_1.beta"), Fd);
-    TAKE(w2, std::string("encoder.proj_w.conv_2.weight"), (int64_t)Fd * Fd * k);
-    TAKE(b2, std::string("encoder.proj_w.conv_2.bias"), Fd);
-    TAKE(g2, std::string("encoder.proj_w.norm_2.gamma"), Fd);
-    TAKE(e2, std::string("encoder.proj_w.norm_2.beta"), Fd);
-    TAKE(wp, std::string("encoder.proj_w.proj.weight"), Fd);
-    TAKE(bp, std::string("encoder.proj_w.proj.bias"), 1);
-    const int gin = gm->gin();
-    std::vector<float> w1x;  // multi-speaker: conv_1's weight is [Fd][H + gin][k]; the encoder half goes to the conv kernels
-    if (gin) {
-      std::vector<float> wg((size_t)Fd * gin * k);
-      w1x.resize((size_t)Fd * H * k);
-      for (int co = 0; co < Fd; ++co) {
-        std::memcpy(&w1x[(size_t)co * H * k], w1 + (size_t)co * (H + gin) * k, sizeof(float) * (size_t)H * k);
-        std::memcpy(&wg[(size_t)co * gin * k], w1 + ((size_t)co * (H + gin) + H) * k, sizeof(float) * (size_t)gin * k);
-      }
-      gm->dp_wg = ab.add(wg);
-      w1 = w1x.data();
-    }
-    gm->dp1 = add_conv(ab, w1, b1, Fd, H, k, ROWS_PLAIN);
-    gm->dp2 = add_conv(ab, w2, b2, Fd, Fd, k, ROWS_PLAIN);
-    add_lin16(ab, gm->dp1, w1, b1, Fd, H, k);
-    add_lin16(ab, gm->dp2, w2, b2, Fd, Fd, k);
-    gm->dpp = add_conv(ab, wp, bp, 1, Fd, 1, ROWS_PLAIN);
-    gm->dpp_w = ab.add(wp, Fd);
-    gm->dpp_b = ab.add(bp, 1);
-    gm->dg1 = ab.add(g1, Fd);
-    gm->db1 = ab.add(e1, Fd);
-    gm->dg2 = ab.add(g2, Fd);
-    gm->db2 = ab.add(e2, Fd);
-  }
-  const int C = M * h.n_sqz, half = C / 2;
-  std::vector<float> cond_w_all, cond_b_all;
-  // the fp16 form of the decoder's WaveNets (wn_f16.h), when the geometry is one its kernel is built for
-  gm->f16_why = glow_f16_unsupported(h);
-  gm->f16_ok = gm->f16_why.empty();
-  HPackSink gsink;
-  gsink.ab = &ab;
-  for (int b = 0; b < h.n_blocks_dec; ++b) {
-    GlowBlock B;
-    std::string an = "decoder.flows." + std::to_string(3 * b);
-    std::string ic = "decoder.flows." + std::to_string(3 * b + 1);
-    std::string cp = "decoder.flows." + std::to_string(3 * b + 2);
-    TAKE(logs, an + ".logs", C);
-    TAKE(abias, an + ".bias", C);
-    TAKE(winv, ic + ".weight_inv", (int64_t)h.n_split * h.n_split);
-    std::vector<float> scale(C);
-    for (int c = 0; c < C; ++c) scale[c] = std::exp(-logs[c]);  // ActNorm reverse, layers.py:192-194
-    B.an_bias = ab.add(abias, C);
-    B.an_scale = ab.add(scale);
-    B.winv = ab.add(winv, (size_t)h.n_split * h.n_split);
-    TAKE(ws, cp + ".start.weight", (int64_t)H * half);
-    TAKE(bs, cp + ".start.bias", H);
-    B.start = add_conv(ab, ws, bs, H, half, 1, ROWS_PLAIN);
-    B.t_st = add_col16(ab, ws, bs, H, half);
-    if (gm->gin()) {  // WN.cond_layer (layers.py:109-113): all blocks' weights side by side for speaker_cond_kernel
-      const int64_t n2 = (int64_t)2 * H * h.n_block_layers;
-      TAKE(wc, cp + ".wn.cond_layer.weight", n2 * gm->gin());
-      TAKE(bc, cp + ".wn.cond_layer.bias", n2);
-      cond_w_all.insert(cond_w_all.end(), wc, wc + n2 * gm->gin());
-      cond_b_all.insert(cond_b_all.end(), bc, bc + n2);
-    }
-    for (int j = 0; j < h.n_block_layers; ++j) {
-      std::string il = cp + ".wn.in_layers." + std::to_string(j);
-      std::string rl = cp + ".wn.res_skip_layers." + std::to_string(j);
-      const int rsn = (j < h.n_block_layers - 1) ? 2 * H : H;
-      TAKE(wi, il + ".weight", (int64_t)2 * H * H * h.kernel_size_dec);
-      TAKE(bi, il + ".bias", 2 * H);
-      TAKE(wr, rl + ".weight", (int64_t)rsn * H);
-      TAKE(br, rl + ".bias", rsn);
-      B.in.push_back(add_conv(ab, wi, bi, 2 * H, H, h.kernel_size_dec, ROWS_PAIR, H));
-      add_gate16(ab, B.in.back(), wi, bi, H, H, h.kernel_size_dec);
-      B.rs.push_back(add_conv(ab, wr, br, rsn, H, 1, ROWS_PLAIN));
-      add_lin16(ab, B.rs.back(), wr, br, rsn, H, 1);
-      if (j == h.n_block_layers - 1) B.t_rs = add_col16(ab, wr, br, H, H);
-      if (gm->f16_ok) {
-        B.h_in.push_back(add_wn_gate_h(gsink, wi, bi, H, h.kernel_size_dec));
-        if (j < h.n_block_layers - 1) B.h_rs.push_back(add_wn_rs_h(gsink, wr, br, H));
-      }
-    }
-    TAKE(we, cp + ".end.weight", (int64_t)C * H);
-    TAKE(be, cp + ".end.bias", C);
-    B.end = add_conv(ab, we, be, C, H, 1, ROWS_PAIR, half);
-    B.t_end = add_col16(ab, we, be, C, H);
-    gm->blocks.push_back(std::move(B));
-  }
-#undef TAKE
-  if (gm->gin()) {
-    gm->cond_w = ab.add(cond_w_all);
-    gm->cond_b = ab.add(cond_b_all);
-  }
-  CHECK(upload_arena(ctx, ab, &gm->arena));
-  const float* A = gm->arena;
-  for (auto& c : gm->pre_conv) fix(c, A);
-  if (h.prenet) fix(gm->pre_proj, A);
-  for (auto& L : gm->layers) {
-    fix(L.qkv, A);
-    fix(L.o, A);
-    fix(L.ffn1, A);
-    fix(L.ffn2, A);
-  }
-  fix(gm->proj_m, A);
-  fix(gm->dp1, A);
-  fix(gm->dp2, A);
-  fix(gm->dpp, A);
-  for (auto& B : gm->blocks) {
-    fix(B.start, A);
-    fix(B.end, A);
-    for (auto& c : B.in) fix(c, A);
-    for (auto& c : B.rs) fix(c, A);
-  }
-  if (gm->f16_ok) {
-    hipError_t e = hipMalloc(&gm->arenaH, gsink.w.size() * sizeof(uint16_t) + 256);
-    if (e != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc fp16 weight arena: %s", hipGetErrorString(e));
-    HIPCHECK(hipMemcpy(gm->arenaH, gsink.w.data(), gsink.w.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    for (auto& B : gm->blocks) {
-      for (auto& c : B.h_in) fix_h(c, gm->arenaH, A);
-      for (auto& c : B.h_rs) fix_h(c, gm->arenaH, A);
-    }
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const int id = ctx->next_id++;
-  ctx->glow[id] = std::move(gm);
-  *model_out = id;
-  return 0;
+  ModelPacker pk;
+  CHECK(build_glow_model(*hp, r, pk, *gm));
+  CHECK(pk.upload(ctx, *gm));
+  return register_model(ctx, ctx->glow, std::move(gm), model_out);
 }
 
 static int dispatch_selfcheck_run(mi355tts_ctx* ctx);
@@ -432,225 +187,17 @@ extern "C" int mi355tts_load_hifigan(mi355tts_ctx* ctx, const mi355tts_hifigan_h
                                      int64_t numel, int on_device, int* model_out) {
   if (!ctx || !blob || !model_out) return fail(MI355TTS_ERR_INVALID, "null argument");
   CHECK(check_hifi_hp(hp));
-  const mi355tts_hifigan_hparams& h = *hp;
-  std::vector<float> tmp;
-  Blob bl;
-  CHECK(fetch_blob(ctx, blob, numel, on_device, tmp, &bl.p));
-  bl.n = numel;
-  bl.manifest = hifigan_manifest(h);
-  int64_t total = 0;
-  for (auto& kv : bl.manifest) total += kv.second;
-  if (total != numel) return fail(MI355TTS_ERR_INVALID, "HiFi-GAN blob has %lld floats, manifest needs %lld", (long long)numel, (long long)total);
+  std::vector<float> host;
+  BlobReader r;
+  CHECK(open_blob(ctx, "HiFi-GAN", hifigan_manifest(*hp), blob, numel, on_device, host, &r));
   auto hm = std::make_shared<HifiModel>();
-  hm->hp = h;
   hm->device = ctx->device;
-  ArenaBuilder ab;
-  std::vector<uint16_t> ab16;  // split-bf16 fragments (conv_bf16.h) of the ResBlock convs
-  auto add16 = [&](DevConv& d, const float* w, int ch, int k) {
-    if (ch < 32 || (ch % 32)) return;
-    PackedConv16 p = pack_conv_bf16(ch, ch >= 128 ? 4 : ch / 32, ch, k, [&](int co, int ci, int kk) { return w[((size_t)co * ch + ci) * k + kk]; });
-    d.w16_off = (ab16.size() + 127) & ~(size_t)127;  // 256-byte alignment
-    ab16.resize(d.w16_off + p.w.size());
-    std::memcpy(ab16.data() + d.w16_off, p.w.data(), p.w.size() * sizeof(uint16_t));
-    d.mtiles16 = p.mtiles;
-    d.nslab16 = p.nslab;
-  };
-  // the native fp16 mode's packing of every conv (hifigan_f16.h), when the geometry is one its tiles cover
-  hm->f16_why = hifi_f16_unsupported(h);
-  hm->f16_ok = hm->f16_why.empty();
-  HPackSink hsink;
-  hsink.ab = &ab;
-  const int C0 = h.upsample_initial_channel;
-#define TAKE(var, name, n)                         \
-  const float* var = bl.take((name).c_str(), (n)); \
-  if (!var) return MI355TTS_ERR_INVALID;
-  {
-    TAKE(w, std::string("conv_pre.weight"), (int64_t)C0 * h.num_mels * 7);
-    TAKE(b, std::string("conv_pre.bias"), C0);
-    hm->pre = add_conv(ab, w, b, C0, h.num_mels, 7, ROWS_PLAIN);
-    if (hm->f16_ok) hm->h_pre = add_conv_h(hsink, w, b, C0, h.num_mels, 7);
-  }
-  int ch = C0;
-  hm->hop = 1;
-  hm->rb.resize(h.num_upsamples);
-  for (int i = 0; i < h.num_upsamples; ++i) {
-    const int cin = C0 >> i, cout = C0 >> (i + 1);
-    const int u = h.upsample_rates[i], ku = h.upsample_kernel_sizes[i];
-    hm->hop *= u;
-    TAKE(w, "ups." + std::to_string(i) + ".weight", (int64_t)cin * cout * ku);
-    TAKE(b, "ups." + std::to_string(i) + ".bias", cout);
-    hm->ups.push_back(add_conv(ab, w, b, cout, cin, ku, ROWS_UPSAMPLE, u));
-    if (hm->f16_ok) hm->h_ups.push_back(add_ups_h(hsink, w, b, cout, cin, u));
-    if (cin % 32 == 0 && (cout * u) % 32 == 0 && ku / u == 2) {
-      // split-bf16 fragments of the polyphase form (virtual rows v = co * u + r, taps k = 0, 1 <-> m = 1, 0; see add_conv)
-      DevConv& d = hm->ups.back();
-      const int rows = cout * u, Kt = ku / u;
-      PackedConv16 p16 = pack_conv_bf16(rows, rows >= 128 ? 4 : rows / 32, cin, Kt, [&](int v, int ci, int k) {
-        const int co = v / u, r = v % u, m = Kt - 1 - k;
-        return w[((size_t)ci * cout + co) * ku + m * u + r];
-      });
-      d.w16_off = (ab16.size() + 127) & ~(size_t)127;
-      ab16.resize(d.w16_off + p16.w.size());
-      std::memcpy(ab16.data() + d.w16_off, p16.w.data(), p16.w.size() * sizeof(uint16_t));
-      d.mtiles16 = p16.mtiles;
-      d.nslab16 = p16.nslab;
-    }
-    ch = cout;
-    hm->rb[i].resize(h.num_kernels);
-    if (hm->f16_ok) {
-      hm->h_rb.resize(h.num_upsamples);
-      hm->h_rb[i].resize(h.num_kernels);
-    }
-    // narrow stages additionally get the packing of the one-launch MRF kernel (mrf_small.h): ResBlock1 chains
-    // with taps (3, 7, 11), <= 3 dilation steps and a receptive half-width within the staged halo
-    MrfStage ms;
-    std::vector<float> mrf_w, mrf_b, mrf_w8;
-    int woff8[3][MRF_MAX_STEPS][2] = {};
-    ms.ok = h.resblock_type == 1 && h.num_kernels == 3 && (ch == 8 || ch == 16) && h.num_dilations <= MRF_MAX_STEPS &&
-            h.resblock_kernel_sizes[0] == 3 && h.resblock_kernel_sizes[1] == 7 && h.resblock_kernel_sizes[2] == 11;
-    for (int j = 0; ms.ok && j < h.num_kernels; ++j) {
-      int need = 0;
-      for (int d = 0; d < h.num_dilations; ++d) {
-        if (h.resblock_dilations[j][d] < 1) ms.ok = false;
-        need += (h.resblock_kernel_sizes[j] - 1) / 2 * (h.resblock_dilations[j][d] + 1);
-      }
-      if (need > MRF_HALO) ms.ok = false;
-    }
-    ms.C = ch;
-    ms.nsteps = h.num_dilations;
-    if (ms.ok) mrf_b.assign((size_t)3 * MRF_MAX_STEPS * 2 * 16, 0.f);
-    for (int j = 0; j < h.num_kernels; ++j) {
-      const int n = i * h.num_kernels + j;
-      const int k = h.resblock_kernel_sizes[j];
-      std::string rb = "resblocks." + std::to_string(n);
-      for (int d = 0; d < h.num_dilations; ++d) {
-        HifiResConv rc;
-        rc.dil = h.resblock_dilations[j][d];
-        if (h.resblock_type == 1) {
-          TAKE(w1, rb + ".convs1." + std::to_string(d) + ".weight", (int64_t)ch * ch * k);
-          TAKE(b1, rb + ".convs1." + std::to_string(d) + ".bias", ch);
-          TAKE(w2, rb + ".convs2." + std::to_string(d) + ".weight", (int64_t)ch * ch * k);
-          TAKE(b2, rb + ".convs2." + std::to_string(d) + ".bias", ch);
-          rc.c1 = add_conv(ab, w1, b1, ch, ch, k, ROWS_PLAIN);
-          rc.c2 = add_conv(ab, w2, b2, ch, ch, k, ROWS_PLAIN);
-          add16(rc.c1, w1, ch, k);
-          add16(rc.c2, w2, ch, k);
-          if (hm->f16_ok) {
-            HResConv hr;
-            hr.c1 = add_conv_h(hsink, w1, b1, ch, ch, k);
-            hr.c2 = add_conv_h(hsink, w2, b2, ch, ch, k);
-            hm->h_rb[i][j].push_back(hr);
-          }
-          if (ms.ok) {
-            const float* ws[2] = {w1, w2};
-            const float* bs[2] = {b1, b2};
-            ms.dil[j][d] = rc.dil;
-            for (int cv = 0; cv < 2; ++cv) {
-              const float* wsrc = ws[cv];
-              std::vector<float> pk = pack_mrf_conv(ch, k, [&](int co, int ci, int kk) { return wsrc[((size_t)co * ch + ci) * k + kk]; });
-              ms.woff[j][d][cv] = (int)mrf_w.size();
-              mrf_w.insert(mrf_w.end(), pk.begin(), pk.end());
-              if (ch == 8) {
-                std::vector<float> p8 = pack_mrf8_conv(k, [&](int co, int ci, int kk) { return wsrc[((size_t)co * ch + ci) * k + kk]; });
-                woff8[j][d][cv] = (int)mrf_w8.size();
-                mrf_w8.insert(mrf_w8.end(), p8.begin(), p8.end());
-              }
-              std::memcpy(&mrf_b[(((size_t)j * MRF_MAX_STEPS + d) * 2 + cv) * 16], bs[cv], sizeof(float) * ch);
-            }
-            ms.mac_per_col += 2.0 * ch * ch * k;
-          }
-        } else {
-          TAKE(w1, rb + ".convs." + std::to_string(d) + ".weight", (int64_t)ch * ch * k);
-          TAKE(b1, rb + ".convs." + std::to_string(d) + ".bias", ch);
-          rc.c1 = add_conv(ab, w1, b1, ch, ch, k, ROWS_PLAIN);
-          add16(rc.c1, w1, ch, k);
-          if (hm->f16_ok) {
-            HResConv hr;
-            hr.c1 = add_conv_h(hsink, w1, b1, ch, ch, k);
-            hm->h_rb[i][j].push_back(hr);
-          }
-        }
-        hm->rb[i][j].push_back(rc);
-      }
-    }
-    if (ms.ok) {
-      ms.w_off = ab.add(mrf_w);
-      ms.b_off = ab.add(mrf_b);
-      int tab[MRF_TAB_INTS] = {};
-      for (int j = 0; j < 3; ++j)
-        for (int d = 0; d < MRF_MAX_STEPS; ++d) {
-          tab[(j * MRF_MAX_STEPS + d) * 2 + 0] = ms.woff[j][d][0];
-          tab[(j * MRF_MAX_STEPS + d) * 2 + 1] = ms.woff[j][d][1];
-          tab[MRF_TAB_DIL + j * MRF_MAX_STEPS + d] = ms.dil[j][d];
-        }
-      static_assert(sizeof(int) == sizeof(float), "the table rides in the float arena");
-      ms.t_off = ab.add(reinterpret_cast<const float*>(tab), MRF_TAB_INTS);
-      if (ch == 8) {
-        mrf_w8.resize(mrf_w8.size() + 64, 0.f);  // the tap loop's prefetch reads one fragment past the last conv
-        ms.w8_off = ab.add(mrf_w8);
-        for (int j = 0; j < 3; ++j)
-          for (int d = 0; d < MRF_MAX_STEPS; ++d) {
-            tab[(j * MRF_MAX_STEPS + d) * 2 + 0] = woff8[j][d][0];
-            tab[(j * MRF_MAX_STEPS + d) * 2 + 1] = woff8[j][d][1];
-          }
-        ms.t8_off = ab.add(reinterpret_cast<const float*>(tab), MRF_TAB_INTS);
-      }
-    }
-    hm->mrf.push_back(ms);
-  }
-  {
-    TAKE(w, std::string("conv_post.weight"), (int64_t)ch * 7);
-    TAKE(b, std::string("conv_post.bias"), 1);
-    hm->post = add_conv(ab, w, b, 1, ch, 7, ROWS_PLAIN);
-    hm->post_w_off = ab.add(w, (size_t)ch * 7);  // raw [C][7] + bias for post_conv_kernel (voc_out.h)
-    hm->post_b_off = ab.add(b, 1);
-    hm->post_C = ch;
-  }
-#undef TAKE
-  CHECK(upload_arena(ctx, ab, &hm->arena));
-  if (!ab16.empty()) {
-    hipError_t e = hipMalloc(&hm->arena16, ab16.size() * sizeof(uint16_t) + 256);
-    if (e != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc bf16 weight arena: %s", hipGetErrorString(e));
-    HIPCHECK(hipMemcpy(hm->arena16, ab16.data(), ab16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  }
-  auto fix16 = [&](DevConv& c) { c.w16 = c.mtiles16 ? (const void*)(hm->arena16 + c.w16_off) : nullptr; };
-  const float* A = hm->arena;
-  if (hm->f16_ok) {
-    hipError_t e = hipMalloc(&hm->arenaH, hsink.w.size() * sizeof(uint16_t) + 256);
-    if (e != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc fp16 weight arena: %s", hipGetErrorString(e));
-    HIPCHECK(hipMemcpy(hm->arenaH, hsink.w.data(), hsink.w.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    fix_h(hm->h_pre, hm->arenaH, A);
-    for (auto& c : hm->h_ups) fix_h(c, hm->arenaH, A);
-    for (auto& st : hm->h_rb)
-      for (auto& kk : st)
-        for (auto& rc : kk) {
-          fix_h(rc.c1, hm->arenaH, A);
-          if (h.resblock_type == 1) fix_h(rc.c2, hm->arenaH, A);
-        }
-  }
-  fix(hm->pre, A);
-  fix(hm->post, A);
-  for (auto& c : hm->ups) {
-    fix(c, A);
-    fix16(c);
-  }
-  for (auto& st : hm->rb)
-    for (auto& kk : st)
-      for (auto& rc : kk) {
-        fix(rc.c1, A);
-        fix16(rc.c1);
-        if (h.resblock_type == 1) {
-          fix(rc.c2, A);
-          fix16(rc.c2);
-        }
-      }
+  ModelPacker pk;
+  CHECK(build_hifi_model(*hp, r, pk, *hm));
+  CHECK(pk.upload(ctx, *hm));
   // the first vocoder with a 256-channel stage: check the dispatcher rule its batch-1 schedule relies on (once per context)
-  if ((C0 >> 1) >= 256 && h.resblock_type == 1) dispatch_selfcheck_run(ctx);  // (a failed check leaves the defaults)
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const int id = ctx->next_id++;
-  ctx->hifi[id] = std::move(hm);
-  *model_out = id;
-  return 0;
+  if ((hp->upsample_initial_channel >> 1) >= 256 && hp->resblock_type == 1) dispatch_selfcheck_run(ctx);  // (a failed check leaves the defaults)
+  return register_model(ctx, ctx->hifi, std::move(hm), model_out);
 }
 
 // Safe while other threads are synthesising with the model: every call pins its models (find_glow / find_hifi hand out
@@ -1148,19 +695,18 @@ static int op_conv_common(mi355tts_ctx* ctx, const float* x, int B, int Cin, int
   CHECK(acquire_worker(ctx, &w));
   WorkerGuard guard{ctx, w};
   Carver cv;
-  const size_t o_w = cv.take(ab.host.size() * sizeof(float));
+  const WorkerWeights ww(ab, cv);
   const int Lp = (L + 3) & ~3;
   const size_t o_x = cv.take(sizeof(float) * (size_t)B * Cin * Lp);
   const size_t o_y = cv.take(sizeof(float) * (size_t)B * Cout * Lout);
   const size_t o_l = cv.take(sizeof(int) * B);
   CHECK(reserve(w, cv.pos));
   char* base = w->arena;
-  float* dw = (float*)(base + o_w);
   float* dx = (float*)(base + o_x);
   float* dy = (float*)(base + o_y);
   int* dl = (int*)(base + o_l);
   hipStream_t s = w->stream;
-  HIPCHECK(hipMemcpyAsync(dw, ab.host.data(), ab.host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  CHECK(ww.copy_and_bind(w, &c, 1));
   HIPCHECK(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)B * Cin * Lp, s));
   HIPCHECK(hipMemcpy2DAsync(dx, sizeof(float) * Lp, x, sizeof(float) * L, sizeof(float) * L, (size_t)B * Cin, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemsetAsync(dy, 0, sizeof(float) * (size_t)B * Cout * Lout, s));
@@ -1171,7 +717,6 @@ static int op_conv_common(mi355tts_ctx* ctx, const float* x, int B, int Cin, int
       hl[b] = lens[b];
     }
   HIPCHECK(hipMemcpyAsync(dl, hl.data(), sizeof(int) * B, hipMemcpyHostToDevice, s));
-  fix(c, dw);
   int rc;
   if (transposed) {
     const int u = dil_or_stride;
@@ -1277,18 +822,16 @@ extern "C" int mi355tts_bench_conv1d(mi355tts_ctx* ctx, int B, int Cin, int Cout
   CHECK(acquire_worker(ctx, &w));
   WorkerGuard guard{ctx, w};
   Carver cv;
-  const size_t o_w = cv.take(ab.host.size() * sizeof(float));
+  const WorkerWeights ww(ab, cv);
   const size_t o_x = cv.take(sizeof(float) * xh.size());
   const size_t o_y = cv.take(sizeof(float) * (size_t)B * Cout * L);
   CHECK(reserve(w, cv.pos));
   char* base = w->arena;
-  float* dw = (float*)(base + o_w);
   float* dx = (float*)(base + o_x);
   float* dy = (float*)(base + o_y);
   hipStream_t s = w->stream;
-  HIPCHECK(hipMemcpyAsync(dw, ab.host.data(), ab.host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  CHECK(ww.copy_and_bind(w, &c, 1));
   HIPCHECK(hipMemcpyAsync(dx, xh.data(), sizeof(float) * xh.size(), hipMemcpyHostToDevice, s));
-  fix(c, dw);
   ConvArgs a = base_args(dx, (long long)Cin * L, L, nullptr, 1, dy, (long long)Cout * L, L, nullptr, 1, dilation,
                          (K * dilation - dilation) / 2);
   a.in_const = L;
@@ -1360,21 +903,19 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
   CHECK(acquire_worker(ctx, &w));
   WorkerGuard guard{ctx, w};
   Carver cvr;
-  const size_t o_w = cvr.take(ab.host.size() * sizeof(float));
+  const WorkerWeights ww(ab, cvr);
   const size_t o_x = cvr.take(sizeof(float) * (size_t)C * L);
   size_t o_y[3];
   for (int m = 0; m < 3; ++m) o_y[m] = cvr.take(sizeof(float) * (size_t)C * L);
   CHECK(reserve(w, cvr.pos));
   char* base = w->arena;
-  float* dw = (float*)(base + o_w);
   float* dx = (float*)(base + o_x);
   hipStream_t s = w->stream;
-  HIPCHECK(hipMemcpyAsync(dw, ab.host.data(), ab.host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  CHECK(ww.copy_and_bind(w, cv, 3));
   HIPCHECK(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)C * L, s));
   ConvPlan plans[3];
   ConvPlan* pp[3] = {&plans[0], &plans[1], &plans[2]};
   for (int m = 0; m < 3; ++m) {
-    fix(cv[m], dw);
     ConvArgs a = base_args(dx, (long long)C * L, L, nullptr, 1, (float*)(base + o_y[m]), (long long)C * L, L, nullptr, 1, 1, (Ks[m] - 1) / 2);
     a.in_const = a.out_const = L;
     a.in_slope = 0.1f;

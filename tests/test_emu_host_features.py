@@ -304,6 +304,100 @@ def test_workspace_growth_keeps_live_buffers(emu_library):
     check_workspace_growth_keeps_live_buffers(lambda: Engine(device=0, library_path=emu_library))
 
 
+# the models of the two loader checks: a 3-speaker voice (emb_g, the conv_1 split, the cond_layer tables) and a vocoder whose
+# stages run 64 -> 32 -> 16 -> 8 channels (bf16 ResBlock and upsampler fragments, both MRF small-stage packings, the C = 8 tables)
+LOADER_GLOW = dataclasses.replace(HP.TINY_GLOW, mel_channels=8, n_speakers=3, gin_channels=20)
+LOADER_HIFIGAN = HP.HifiGanHParams(upsample_rates=(2, 2, 2), upsample_kernel_sizes=(4, 4, 4), upsample_initial_channel=64, num_mels=8)
+ERR_INVALID = -1  # MI355TTS_ERR_INVALID
+
+
+def _loader_ids():
+    rng = np.random.default_rng(77)
+    return [synthetic.synthetic_phoneme_ids(rng, n, LOADER_GLOW.num_symbols) for n in (9, 23)]
+
+
+def check_load_from_device_blob(eng, to_device):
+    """`on_device = 1`: the loaders copy a device-resident blob (the receive side of the weight broadcast) to the host and pack
+    it like a host blob.  `to_device(blob)` gives (device pointer, the object that keeps it alive).  Each model once from the
+    host and once from the device; mel, waveform and frame counts through either pair are the same bits, the vocoder's also in
+    the modes that read the bf16 and the fp16 arena."""
+    gblob = eng.glow_blob(LOADER_GLOW, synthetic.make_glow_state_dict(LOADER_GLOW, seed=21))
+    vblob = eng.hifigan_blob(LOADER_HIFIGAN, synthetic.make_hifigan_state_dict(LOADER_HIFIGAN, seed=31))
+    gptr, gkeep = to_device(gblob)
+    vptr, vkeep = to_device(vblob)
+    pairs = [(eng.load_glow(LOADER_GLOW, blob=gblob), eng.load_hifigan(LOADER_HIFIGAN, blob=vblob)),
+             (eng.load_glow(LOADER_GLOW, device_ptr=gptr), eng.load_hifigan(LOADER_HIFIGAN, device_ptr=vptr))]
+    del gkeep, vkeep  # the loaders keep nothing of the caller's blob
+    ids = _loader_ids()
+    try:
+        for precision in (ffi.PRECISION_F32, ffi.PRECISION_BF16X3, ffi.PRECISION_F16):
+            got = []
+            for g, v in pairs:
+                eng.set_precision(v, precision)
+                mel = eng.glow_infer(g, ids, 0.667, 1.0, row_seeds=[11, 77], speaker_ids=[2, 0])
+                frames, f32, i16 = eng.synthesize(g, v, ids, 0.667, 1.0, seed=11, speaker_ids=[2, 0], want_float=True)
+                got.append((mel.numpy("raw"), np.array(mel.frames), frames.copy(), f32, i16))
+                mel.free()
+            (raw_h, mfr_h, fr_h, f_h, i_h), (raw_d, mfr_d, fr_d, f_d, i_d) = got
+            assert fr_h.min() > 0 and np.abs(f_h).max() > 1e-3
+            assert np.array_equal(mfr_h, mfr_d) and np.array_equal(fr_h, fr_d)
+            assert np.array_equal(raw_h, raw_d) and np.array_equal(f_h, f_d) and np.array_equal(i_h, i_d)
+    finally:
+        for g, v in pairs:
+            eng.unload(g)
+            eng.unload(v)
+
+
+def check_load_rejects_bad_blob(eng, device_probe):
+    """A blob whose size is not the manifest's total is refused, `MI355TTS_ERR_INVALID` and the counts in the message, host or
+    device; a device blob before anything is copied — `device_probe` is a valid device pointer with LESS behind it than the
+    claimed size, so a loader that copied first would answer with a runtime error instead (or read past it).  A null pointer is
+    the null-argument error, whatever the size.  A geometry the upsampler tile has no form for is refused by name.  After each
+    refusal the same context loads a good model and synthesises."""
+    import ctypes as C
+
+    ghp, vhp = ffi.glow_hparams_c(LOADER_GLOW), ffi.hifigan_hparams_c(LOADER_HIFIGAN)
+    gblob = eng.glow_blob(LOADER_GLOW, synthetic.make_glow_state_dict(LOADER_GLOW, seed=21))
+    vblob = eng.hifigan_blob(LOADER_HIFIGAN, synthetic.make_hifigan_state_dict(LOADER_HIFIGAN, seed=31))
+    ids = _loader_ids()
+    loaded = []
+
+    def good_models_still_load():
+        g, v = eng.load_glow(LOADER_GLOW, blob=gblob), eng.load_hifigan(LOADER_HIFIGAN, blob=vblob)
+        loaded.extend((g, v))
+        frames, _, i16 = eng.synthesize(g, v, ids, 0.667, 1.0, seed=11, speaker_ids=[2, 0])
+        assert frames.min() > 0 and np.abs(i16).max() > 0
+
+    def refused(fn, hp_c, ptr, numel, on_device):
+        model = C.c_int(-7)
+        rc = fn(eng._ctx, C.byref(hp_c), C.c_void_p(ptr), numel, on_device, C.byref(model))
+        assert rc == ERR_INVALID and model.value == -7, (rc, model.value)
+        return eng.lib.mi355tts_last_error().decode()
+
+    for fn, hp_c, blob, what in ((eng.lib.mi355tts_load_glow, ghp, gblob, "GlowTTS"), (eng.lib.mi355tts_load_hifigan, vhp, vblob, "HiFi-GAN")):
+        padded = np.concatenate([blob, np.zeros(1, np.float32)])  # (one float more than the manifest, really there)
+        for numel in (blob.size - 1, blob.size + 1):
+            want = f"{what} blob has {numel} floats, manifest needs {blob.size}"
+            assert refused(fn, hp_c, padded.ctypes.data, numel, 0) == want
+            assert refused(fn, hp_c, device_probe, numel, 1) == want
+            assert refused(fn, hp_c, None, numel, 1) == "null argument"
+            good_models_still_load()
+    bad = HP.HifiGanHParams(upsample_rates=(3,), upsample_kernel_sizes=(8,), upsample_initial_channel=64, num_mels=8)
+    assert refused(eng.lib.mi355tts_load_hifigan, ffi.hifigan_hparams_c(bad), vblob.ctypes.data, vblob.size, 0) == "unsupported upsample (3,8)"
+    good_models_still_load()
+    for m in loaded:
+        eng.unload(m)
+
+
+def test_load_from_device_blob(emu_engine):
+    check_load_from_device_blob(emu_engine, lambda blob: (blob.ctypes.data, blob))  # the emulator's device memory is the host's
+
+
+def test_load_rejects_bad_blob(emu_engine):
+    probe = np.zeros(1, np.float32)
+    check_load_rejects_bad_blob(emu_engine, probe.ctypes.data)
+
+
 def test_seeded_path_equals_injected_noise(emu_engine, tiny):
     hp = HP.TINY_GLOW
     check_seeded_path_equals_injected_noise(emu_engine, tiny["g"], hp.num_symbols, hp.mel_channels, lens=(23,), length_scale=1.0)

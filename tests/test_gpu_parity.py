@@ -357,6 +357,31 @@ def test_workspace_growth_keeps_live_buffers():
     check_workspace_growth_keeps_live_buffers(lambda: Engine(device=0))
 
 
+def _torch_device_blob(blob):
+    import torch
+
+    t = torch.from_numpy(blob).cuda()
+    torch.cuda.synchronize()
+    return t.data_ptr(), t
+
+
+def test_load_from_device_blob(gpu_engine):
+    """Both loaders from a blob in device memory (a torch tensor's `data_ptr()`) against the same blob from the host."""
+    from tests.test_emu_host_features import check_load_from_device_blob
+
+    check_load_from_device_blob(gpu_engine, _torch_device_blob)
+
+
+def test_load_rejects_bad_blob(gpu_engine):
+    """Wrong blob sizes are refused before a device blob is copied: the probe is a 4-byte allocation, which a copy of the
+    claimed size could not come from."""
+    from tests.test_emu_host_features import check_load_rejects_bad_blob
+
+    ptr, keep = _torch_device_blob(np.zeros(1, np.float32))
+    check_load_rejects_bad_blob(gpu_engine, ptr)
+    del keep
+
+
 def test_glowtts_launch_counts_on_the_device(gpu_engine):
     """The fused GlowTTS schedule is the one that runs for the released voices' shape: 97 decoder launches (1 start + 12 x (4
     gate convs + 3 res_skip + 1 tail)), 31 encoder conv launches, 12 small kernels per utterance — a shape check that silently
