@@ -216,6 +216,33 @@ int mi355tts_glow_infer_prosody(mi355tts_ctx* ctx, int glow, const int64_t* ids,
  * durations: one wrapped by mi355tts_mel_from_buffer, or made by a call without prosody. */
 int mi355tts_mel_durations(const mi355tts_mel* mel, int32_t* dst, int ld);
 
+/* ---- forced alignment: which frames of a given mel belong to which phoneme id ------
+ * Glow-TTS's own training-time alignment (the reference carries the pieces: FlowSpecDecoder.forward with reverse=False,
+ * glow_tts/models.py:191-209; the reverse=False branches of ActNorm, InvConvNear and CouplingBlock, layers.py:192-197, :238-272,
+ * attentions.py:119-142; maximum_path, glow_tts/utils.py:59-96), per batch row (row b of a batch equals its own batch-1 call):
+ *   1. F = (frames[b] / n_sqz) * n_sqz, later frames are ignored (FlowGenerator.preprocess, models.py:356-363); F >= id_lens[b].
+ *   2. the encoder exactly as in mi355tts_glow_infer: x_m [M][P] (and the speaker vector of a multi-speaker voice).
+ *   3. z = decoder(mel, reverse=False): squeeze; per flow block ActNorm (bias + exp(logs) x), InvConvNear with the forward
+ *      weight (the inverse, computed in double at load time, of the weight_inv the blob carries), coupling z1 = m + exp(logs) x1;
+ *      unsqueeze; masked to F.  Always f32, whatever mi355tts_model_set_precision says.  No log-determinant.
+ *   4. scores (Glow-TTS's likelihood with x_logs = 0 — mean_only voices, the only ones loaded; not a line of the reference):
+ *        logp[t][j] = -0.5 M ln(2 pi) - 0.5 sum_c z[c][j]^2 + sum_c x_m[c][t] z[c][j] - 0.5 sum_c x_m[c][t]^2
+ *      every sum over c ascending in f32 (one fma per term), combined as ((c0 - 0.5 zz) + xz) - 0.5 xx.
+ *   5. the best monotonic path as maximum_path computes it in float32: v = 0; per frame j: v0[t] = v[t-1] (-inf at t = 0),
+ *      stay = v[t] >= v0[t] (a tie stays), v[t] = max(v[t], v0[t]) + logp[t][j] for t <= j, else -inf; backtrack from t = P - 1
+ *      at j = F - 1.  One max and one add per cell: v is numpy's bit for bit.
+ * ids / id_lens / speaker_ids as in mi355tts_glow_infer_speakers (HOST memory; speaker_ids NULL for a single-speaker voice).
+ * mel: host [B][M][mel_ld] (device with MI355TTS_IN_DEVICE), in the GlowTTS output domain (plane 0 of mi355tts_mel_copy, before
+ * the AudioSettings transforms), frames[b] <= mel_ld valid columns.  durations_out: host [B][dur_ld], dur_ld >= the longest
+ * row: frames per id, each >= 1, row sum F, entries past id_lens[b] zero.  score_out: host [B] or NULL, the path's total
+ * v[P - 1].  z_out: host (device with MI355TTS_OUT_DEVICE) [B][M][mel_ld] or NULL, zero past F.
+ * MI355TTS_ERR_INVALID with the reason: F < id_lens[b], more than 2048 ids in a row (the path kernel's registers), dur_ld too
+ * small, speaker ids missing or superfluous, null pointers.  Durations from here go into mi355tts_prosody.durations_in
+ * ("the timing of one take onto another").  Added in ABI version 2 (additive: the version number is unchanged). */
+int mi355tts_glow_align(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
+                        const float* mel, const int32_t* frames, int mel_ld, const int32_t* speaker_ids, uint32_t flags,
+                        int32_t* durations_out, int dur_ld, float* score_out, float* z_out);
+
 int mi355tts_mel_batch(const mi355tts_mel* mel);
 int mi355tts_mel_channels(const mi355tts_mel* mel);
 int mi355tts_mel_max_frames(const mi355tts_mel* mel);
@@ -317,7 +344,8 @@ int mi355tts_synthesize_prosody(mi355tts_ctx* ctx, int glow, int vocoder, const 
  * their workspaces and the result-block pool for calls of up to max_batch rows x max_ids ids
  * x max_frames mel frames (+ max_pad_samples of pause padding; denoiser != 0 also sizes the
  * STFT scratch), so that no steady-state call allocates device memory.  glow / vocoder may
- * be 0 to size for one model only. */
+ * be 0 to size for one model only.  With a GlowTTS model the workspaces also cover mi355tts_glow_align on the same shapes
+ * (its [F][P] score matrix and direction bits; a mel_ld up to max_frames rounded up to 4). */
 int mi355tts_reserve(mi355tts_ctx* ctx, int workers, int glow, int vocoder, int max_batch, int max_ids, int max_frames,
                      int denoiser, int max_pad_samples);
 /* Measurement: the hardware-queue group of every worker of the context, in creation order (groups[i] for worker i; -1 = not probed:
@@ -351,6 +379,12 @@ int mi355tts_op_denoise(mi355tts_ctx* ctx, const float* wav, int B, int64_t N, c
  * the stand-in for torch.randn_like (glow_tts/models.py:348) that mi355tts_glow_infer uses when
  * `noise` is NULL; exposed so its distribution can be tested. */
 int mi355tts_op_gauss_noise(mi355tts_ctx* ctx, uint64_t seed, int B, int C, int T, float* out);
+
+/* maximum_path alone (glow_tts/utils.py:59-96): value host [B][P_ld][F_ld] (the reference's layout), row b is
+ * id_lens[b] x frames[b] with frames[b] >= id_lens[b], at most 2048 ids; durations_out host [B][dur_ld] (the path's row sums,
+ * zero past id_lens[b]); score_out host [B] or NULL */
+int mi355tts_op_maximum_path(mi355tts_ctx* ctx, const float* value, int B, int P_ld, int F_ld, const int32_t* id_lens,
+                             const int32_t* frames, int32_t* durations_out, int dur_ld, float* score_out);
 
 /* Kernel micro-benchmark: `iters` back-to-back launches of the conv kernel on
  * device-resident random data of the given geometry (tile_shape -1 = the

@@ -1,5 +1,6 @@
 """Phoneme timings: from the frames every phoneme id occupies (`MelBatch.durations`, the reference's
-`attn.sum(-1)`, glow_tts/models.py:350-354) to sample positions in the delivered audio."""
+`attn.sum(-1)`, glow_tts/models.py:350-354) to sample positions in the delivered audio; `align_spans` does the same for a
+mel that already exists (forced alignment, `HipGlowTextToSpeech.align`)."""
 from __future__ import annotations
 
 import numpy as np
@@ -20,3 +21,9 @@ def phoneme_spans(durations, hop: int, pad_before: int = 0) -> np.ndarray:
     end = np.cumsum(d)
     spans = np.stack([end - d, end], axis=1) * int(hop) + int(pad_before)
     return spans.astype(np.int64)
+
+
+def align_spans(tts_model, phoneme_ids, mels, hop: int, pad_before: int = 0, settings=None) -> np.ndarray:
+    """The `phoneme_spans` of an existing mel: `tts_model.align(phoneme_ids, mels, settings)` (the best monotonic path of the
+    ids through the mel under the voice's own likelihood) -> int64 [P, 2] sample positions."""
+    return phoneme_spans(tts_model.align(phoneme_ids, mels, settings), hop, pad_before)

@@ -9,6 +9,7 @@
 //                         z1     = (z1 - m) * exp(-logs)
 //                         z      = ActNorm^-1(InvConvNear^-1(z))               (n_split = 4 channel groups)
 //                         h      = start_next(z0)                              (1 x 1, half -> H; next block in reverse order)
+//   glow_fwd_kernel   — the same seam of the flow in its forward direction (mel -> z, forced alignment): below
 //   oproj_ln_kernel   — conv_o of the encoder's attention + residual + LayerNorm (attentions.py:62-68, :205-212)
 //
 // Why column owners here and not in the WaveNet layers: these steps are 15-37 k MAC per column — a 16-column tile is
@@ -363,6 +364,187 @@ __global__ __launch_bounds__(512) void glow_tail_kernel(const GlowTailArgs a) {
       }
   }
   COL_STAMP(5);
+}
+
+// glow_fwd_kernel — glow_tail_kernel's mirror for the flow in its FORWARD direction (mel -> z: FlowSpecDecoder.forward with
+// reverse=False, glow_tts/models.py:191-209; the reverse=False branches of layers.py:192-197, :260-272, attentions.py:134-139):
+//     s      = skip + res_skip_layers[last](acts)          } the end of block b (PREV; the launch in front of block 0 has none)
+//     m|logs = end(s)                                      }
+//     z1     = m + exp(logs) * z1                          }
+//     z      = InvConvNear(ActNorm(z))                     } the start of block b + 1 (hnext; the launch behind the last block
+//     h      = start_next(z0)                              }  has none): ActNorm bias + exp(logs) x, the forward 4 x 4
+// Same tile, same LDS regions, same thread maps as glow_tail_kernel.
+struct GlowFwdArgs {
+  const float* acts;  // [B][H][h_ld]: gate output of block b's last WaveNet layer (PREV only)
+  const float* skip;  // [B][H][h_ld]: skip sum of the earlier layers (nullptr when the block has one layer)
+  float* hnext;       // [B][H][h_ld]: start(z0) of block b + 1 (nullptr = b is the last block)
+  long long h_bs;
+  int h_ld;
+  float* z;  // [B][2 half][z_ld]: the flow tensor, updated in place
+  long long z_bs;
+  int z_ld;
+  const int* len;  // valid columns of row b: len ? len[b] * len_mul : len_const
+  int len_mul, len_const;
+  const float *w_rs, *b_rs;    // pack_col16 of block b's res_skip_layers[last]: H rows, K = H
+  const float *w_end, *b_end;  // block b's end: 2 half rows (m rows first, then logs), K = H
+  const float *w_st, *b_st;    // block b + 1's start: H rows, K = half
+  const float* mix_w;          // [4][4] block b + 1's forward InvConvNear weight (the inverse of weight_inv)
+  const float* mix_bias;       // [2 half] block b + 1's ActNorm bias
+  const float* mix_scale;      // [2 half] exp(+logs) of block b + 1's ActNorm
+  int H, half;
+};
+
+template <bool PREV>
+__global__ __launch_bounds__(512) void glow_fwd_kernel(const GlowFwdArgs a) {
+  GLOW_PRIO();
+  // R1: acts, then m|logs;  R2: skip -> s, then the new z0;  R3: z
+  __shared__ float lds[3 * COL_MAXROWS * COL_T];
+  float* R1 = lds;
+  float* R2 = lds + COL_MAXROWS * COL_T;
+  float* R3 = lds + 2 * COL_MAXROWS * COL_T;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.y;
+  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int t0 = blockIdx.x * COL_T;
+  if (t0 >= L) return;
+  const int H = a.H, half = a.half, C = 2 * half;
+  const int KH = (H + 15) & ~15, KZ = (half + 15) & ~15, CP = (C + 15) & ~15;
+  const ColStep s_rs{reinterpret_cast<const float4*>(a.w_rs), KH / 16, KH / 16};
+  const ColStep s_end{reinterpret_cast<const float4*>(a.w_end), CP / 16, KH / 16};
+  const ColStep s_st{reinterpret_cast<const float4*>(a.w_st), KH / 16, KZ / 16};
+  const int col = lane & 15, rq = 4 * (lane >> 4);
+  const bool mix = a.hnext != nullptr;
+
+  // ---- every load whose address is known at entry in one batch (as in glow_tail_kernel)
+  float4 a0[COL_RING], a1[COL_RING];
+  ColTileRegs t_acts, t_skip, t_z;
+  if constexpr (PREV) {
+    col_tile_issue(a.acts + (long long)b * a.h_bs, H, a.h_ld, t0, t_acts);
+    col_tile_issue((a.skip ? a.skip : a.acts) + (long long)b * a.h_bs, H, a.h_ld, t0, t_skip);
+  }
+  col_tile_issue(a.z + (long long)b * a.z_bs, C, a.z_ld, t0, t_z);
+  col_step_fill(PREV ? s_rs : s_st, wave, a0, a1);
+  float bb_rs[2][4], bb_end[2][4], bb_st[2][4];
+  if constexpr (PREV) {
+    col_bias_issue(a.b_rs, s_rs.RT, wave, rq, bb_rs);
+    col_bias_issue(a.b_end, s_end.RT, wave, rq, bb_end);
+  }
+  col_bias_issue(a.b_st, s_st.RT, wave, rq, bb_st);
+  // items of this thread: channel group k = (tid >> 4) + 32 i (i < 2: half <= 128), column tid & 15
+  const int ngroups = half / 2;
+  float mb[2][4], ms[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int k = (tid >> 4) + 32 * i;
+    const int c0 = 2 * (k < ngroups ? k : ngroups - 1);
+    mb[i][0] = a.mix_bias[c0];
+    mb[i][1] = a.mix_bias[c0 + 1];
+    mb[i][2] = a.mix_bias[half + c0];
+    mb[i][3] = a.mix_bias[half + c0 + 1];
+    ms[i][0] = a.mix_scale[c0];
+    ms[i][1] = a.mix_scale[c0 + 1];
+    ms[i][2] = a.mix_scale[half + c0];
+    ms[i][3] = a.mix_scale[half + c0 + 1];
+  }
+  float w[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) w[i] = a.mix_w[i];
+  if constexpr (PREV) {
+    col_tile_land(t_acts, true, H, KH, t0, L, R1);
+    col_tile_land(t_skip, a.skip != nullptr, H, KH, t0, L, R2);
+  }
+  col_tile_land(t_z, true, C, C, t0, L, R3);
+  __syncthreads();
+
+  col_floatx4 acc0, acc1;
+  if constexpr (PREV) {
+    // ---- s = (W_rs acts + b) + skip
+    col_step_run(s_rs, wave, R1, a0, a1, acc0, acc1);
+    col_step_fill(s_end, wave, a0, a1);
+    {
+      const int nt = col_tiles_of(wave, s_rs.RT);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (i < nt) {
+          const int r0 = (wave + 8 * i) * 16 + rq;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float* p = R2 + (r0 + r) * COL_T + col;
+            *p = ((i ? acc1[r] : acc0[r]) + bb_rs[i][r]) + *p;
+          }
+        }
+    }
+    __syncthreads();
+    // ---- m | logs = W_end s + b
+    col_step_run(s_end, wave, R2, a0, a1, acc0, acc1);
+    col_step_fill(s_st, wave, a0, a1);
+    {
+      const int nt = col_tiles_of(wave, s_end.RT);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (i < nt) {
+          const int r0 = (wave + 8 * i) * 16 + rq;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) R1[(r0 + r) * COL_T + col] = (i ? acc1[r] : acc0[r]) + bb_end[i][r];
+        }
+    }
+    __syncthreads();
+  }
+  // ---- coupling forward, then the next block's ActNorm and InvConvNear on the channel groups {2k, 2k+1, half+2k, half+2k+1}
+  {
+    float* zb = a.z + (long long)b * a.z_bs;
+    const int n = tid & 15;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = (tid >> 4) + 32 * i;
+      if (k < ngroups) {
+        const int c0 = 2 * k;
+        float y0 = R3[c0 * COL_T + n], y1 = R3[(c0 + 1) * COL_T + n];
+        float y2 = R3[(half + c0) * COL_T + n], y3 = R3[(half + c0 + 1) * COL_T + n];
+        if constexpr (PREV) {
+          const float m0 = R1[c0 * COL_T + n], m1 = R1[(c0 + 1) * COL_T + n];
+          const float l0 = R1[(half + c0) * COL_T + n], l1 = R1[(half + c0 + 1) * COL_T + n];
+          y2 = m0 + expf(l0) * y2;
+          y3 = m1 + expf(l1) * y3;
+        }
+        if (mix) {
+          const float in0 = mb[i][0] + ms[i][0] * y0, in1 = mb[i][1] + ms[i][1] * y1;
+          const float in2 = mb[i][2] + ms[i][2] * y2, in3 = mb[i][3] + ms[i][3] * y3;
+          y0 = w[0] * in0 + w[1] * in1 + w[2] * in2 + w[3] * in3;
+          y1 = w[4] * in0 + w[5] * in1 + w[6] * in2 + w[7] * in3;
+          y2 = w[8] * in0 + w[9] * in1 + w[10] * in2 + w[11] * in3;
+          y3 = w[12] * in0 + w[13] * in1 + w[14] * in2 + w[15] * in3;
+        }
+        const int t = t0 + n;
+        if (t < L) {
+          zb[(long long)c0 * a.z_ld + t] = y0;
+          zb[(long long)(c0 + 1) * a.z_ld + t] = y1;
+          zb[(long long)(half + c0) * a.z_ld + t] = y2;
+          zb[(long long)(half + c0 + 1) * a.z_ld + t] = y3;
+        }
+        R2[c0 * COL_T + n] = y0;
+        R2[(c0 + 1) * COL_T + n] = y1;
+      }
+    }
+    for (int e = half * COL_T + tid; e < KZ * COL_T; e += 512) R2[e] = 0.f;  // K padding of the next step
+  }
+  if (!mix) return;
+  __syncthreads();
+  // ---- h = W_start z0 + b
+  col_step_run(s_st, wave, R2, a0, a1, acc0, acc1);
+  {
+    const int nt = col_tiles_of(wave, s_st.RT);
+    float* hb = a.hnext + (long long)b * a.h_bs;
+    const int t = t0 + col;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (i < nt) {
+        const int r0 = (wave + 8 * i) * 16 + rq;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (r0 + r < H && t < L) hb[(long long)(r0 + r) * a.h_ld + t] = (i ? acc1[r] : acc0[r]) + bb_st[i][r];
+      }
+  }
 }
 
 struct OprojLnArgs {

@@ -603,6 +603,41 @@ static int glow_dec_workspace(GlowRun& r, const GlowDecLayout& dl, GlowDecView* 
   return 0;
 }
 
+// The WaveNet of a coupling block is the same function in both directions of the flow (layers.py:138-162); these two launches
+// serve glow_flow_block and the forward flow of align_forward.h.
+// layer j's gate conv: acts = tanh . sigmoid (in_layers[j](h) + g_l) on the 16-row gate tile, else the generic tile
+static int glow_wn_gate(const GlowPass& p, const GlowDecView& dv, const float* spk_cond, int blk, int j, int dil) {
+  const mi355tts_glow_hparams& h = p.gm->hp;
+  const GlowBlock& Bk = p.gm->blocks[blk];
+  const int H = h.hidden_channels, kd = h.kernel_size_dec, n2 = 2 * H * h.n_block_layers;  // n2: gate offsets per flow block
+  const long long bsD = (long long)H * p.ld;
+  ConvArgs a = p.args(dv.h, bsD, dv.acts, bsD, dil, (kd * dil - dil) / 2);
+  a.half = H;
+  if (spk_cond) {  // x_in + g_l (layers.py:144-154): this block's, this layer's [2H] slice of cond_layer(g), per batch row
+    a.cond = spk_cond + (size_t)blk * n2 + (size_t)j * 2 * H;
+    a.cond_bs = (long long)h.n_blocks_dec * n2;
+  }
+  // one row: the length is known on the host, no device length array to chase
+  a.in_len = a.out_len = p.rows().len;
+  a.in_const = a.out_const = p.rows().len_const;
+  const int g16 = p.gate16(Bk.in[j], a);
+  if (g16 < 0) return g16;
+  if (g16 == 1) CHECK(p.conv(Bk.in[j], a, EPI_GATE));
+  return 0;
+}
+// layer j's res_skip: h += its first half (not for the last layer, which is all skip), skip (+)= the rest
+static int glow_wn_res_skip(const GlowPass& p, const GlowDecView& dv, const GlowBlock& Bk, int j) {
+  const int H = p.gm->hp.hidden_channels;
+  const bool last = j == p.gm->hp.n_block_layers - 1;
+  const long long bsD = (long long)H * p.ld;
+  ConvArgs r = p.args(dv.acts, bsD, dv.h, bsD);
+  r.split = last ? 0 : H;    // last layer: everything is skip
+  if (!last) r.res = dv.h;  // x = x + res_skip[:H]
+  r.y2 = dv.skip; r.y2_bs = bsD; r.y2_ld = p.ld; r.accum2 = j > 0;
+  if (p.lin16(Bk.rs[j], r) != 0) CHECK(p.conv(Bk.rs[j], r));
+  return 0;
+}
+
 // Flow block `blk` in reverse (CouplingBlock, attentions.py:119-142; WN.forward, layers.py:138-162).  Three forms of the same
 // arithmetic, fastest first:
 //   * the WaveNet: the fp16 mode's one launch for every layer but the last tail (wn16), else per layer the 16-row gate tile or
@@ -614,7 +649,6 @@ static int glow_flow_block(const GlowPass& p, const GlowDecView& dv, const float
   const mi355tts_glow_hparams& h = p.gm->hp;
   const GlowBlock& Bk = p.gm->blocks[blk];
   const int H = h.hidden_channels, C = h.mel_channels * h.n_sqz, half = C / 2, F2 = p.ld, n = h.n_block_layers;
-  const int n2 = 2 * H * n;  // gate offsets per flow block
   const long long bsZ = (long long)C * F2, bsD = (long long)H * F2;
   float* const hcur = dv.h;  // the WaveNet's hidden state
   if (!*start_done) CHECK(p.conv(Bk.start, p.args(dv.z, bsZ, hcur, bsD)));  // h = start(x0)
@@ -623,32 +657,14 @@ static int glow_flow_block(const GlowPass& p, const GlowDecView& dv, const float
   // the fp16 mode: layers 0 .. n - 1 up to the last gated tile in ONE launch (wn_f16.h); the loop then runs the last layer's tail
   const bool wn16 = glow_f16 && run_wn_f16(p, dv, Bk) == 0;
   for (int j = wn16 ? n - 1 : 0; j < n; ++j) {
-    const int kd = h.kernel_size_dec;
     const bool last = j == n - 1;
-    if (!wn16) {
-      ConvArgs a = p.args(hcur, bsD, dv.acts, bsD, dil, (kd * dil - dil) / 2);
-      a.half = H;
-      if (spk_cond) {  // x_in + g_l (layers.py:144-154): this block's, this layer's [2H] slice of cond_layer(g), per batch row
-        a.cond = spk_cond + (size_t)blk * n2 + (size_t)j * 2 * H;
-        a.cond_bs = (long long)h.n_blocks_dec * n2;
-      }
-      // one row: the length is known on the host, no device length array to chase
-      a.in_len = a.out_len = p.rows().len;
-      a.in_const = a.out_const = p.rows().len_const;
-      const int g16 = p.gate16(Bk.in[j], a);
-      if (g16 < 0) return g16;
-      if (g16 == 1) CHECK(p.conv(Bk.in[j], a, EPI_GATE));
-    }
+    if (!wn16) CHECK(glow_wn_gate(p, dv, spk_cond, blk, j, dil));
     if (last) {
       const GlowBlock* next = blk > 0 ? &p.gm->blocks[blk - 1] : nullptr;
       *start_done = run_glow_tail(p, dv, Bk, next) == 0;
       if (*start_done) return 0;
     }
-    ConvArgs r = p.args(dv.acts, bsD, hcur, bsD);
-    r.split = last ? 0 : H;    // last layer: everything is skip
-    if (!last) r.res = hcur;  // x = x + res_skip[:H]
-    r.y2 = dv.skip; r.y2_bs = bsD; r.y2_ld = F2; r.accum2 = j > 0;
-    if (p.lin16(Bk.rs[j], r) != 0) CHECK(p.conv(Bk.rs[j], r));
+    CHECK(glow_wn_res_skip(p, dv, Bk, j));
     dil *= h.dilation_rate;
   }
   // m, logs = end(wn_out);  z1 = (x1 - m) * exp(-logs)

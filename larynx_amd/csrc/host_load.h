@@ -203,6 +203,33 @@ static int build_glow_projections(const mi355tts_glow_hparams& h, BlobReader& r,
   return 0;
 }
 
+// out = in^-1 (n x n, row-major), Gauss-Jordan with partial pivoting in double; false when singular
+static bool invert_small(const float* in, int n, std::vector<float>& out) {
+  std::vector<double> a((size_t)n * 2 * n, 0.0);
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) a[(size_t)i * 2 * n + j] = in[i * n + j];
+    a[(size_t)i * 2 * n + n + i] = 1.0;
+  }
+  for (int c = 0; c < n; ++c) {
+    int piv = c;
+    for (int r = c + 1; r < n; ++r)
+      if (std::fabs(a[(size_t)r * 2 * n + c]) > std::fabs(a[(size_t)piv * 2 * n + c])) piv = r;
+    if (!(std::fabs(a[(size_t)piv * 2 * n + c]) > 0.0)) return false;
+    for (int j = 0; j < 2 * n; ++j) std::swap(a[(size_t)c * 2 * n + j], a[(size_t)piv * 2 * n + j]);
+    const double d = a[(size_t)c * 2 * n + c];
+    for (int j = 0; j < 2 * n; ++j) a[(size_t)c * 2 * n + j] /= d;
+    for (int r = 0; r < n; ++r) {
+      const double f = a[(size_t)r * 2 * n + c];
+      if (r == c || f == 0.0) continue;
+      for (int j = 0; j < 2 * n; ++j) a[(size_t)r * 2 * n + j] -= f * a[(size_t)c * 2 * n + j];
+    }
+  }
+  out.resize((size_t)n * n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) out[(size_t)i * n + j] = (float)a[(size_t)i * 2 * n + n + j];
+  return true;
+}
+
 // one flow block: ActNorm, InvConvNear, the coupling block's WaveNet.  cond_w / cond_b collect the blocks' cond_layer tensors.
 static int build_glow_block(const mi355tts_glow_hparams& h, int b, BlobReader& r, ModelPacker& pk, GlowModel& gm,
                             std::vector<float>& cond_w, std::vector<float>& cond_b) {
@@ -219,6 +246,13 @@ static int build_glow_block(const mi355tts_glow_hparams& h, int b, BlobReader& r
   B.an_bias = pk.add(abias, C);
   B.an_scale = pk.add(scale);
   B.winv = pk.add(winv, (size_t)h.n_split * h.n_split);
+  // the flow forwards (forced alignment, align_forward.h): exp(+logs), and the forward n x n weight as the inverse of weight_inv
+  // in double — the one form every loader can serve (an ONNX-exported voice carries only the inverse)
+  for (int c = 0; c < C; ++c) scale[c] = std::exp(logs[c]);
+  B.an_escale = pk.add(scale);
+  std::vector<float> wfwd;
+  if (!invert_small(winv, h.n_split, wfwd)) return fail(MI355TTS_ERR_INVALID, "%s.weight_inv is singular", ic.c_str());
+  B.wfwd = pk.add(wfwd);
   WB st, cond, in, rs, end;
   CHECK(r.conv(cp + ".start", H, half, 1, &st));
   B.start = add_conv(pk.f32, st.w, st.b, H, half, 1, ROWS_PLAIN);
@@ -245,6 +279,7 @@ static int build_glow_block(const mi355tts_glow_hparams& h, int b, BlobReader& r
   CHECK(r.conv(cp + ".end", C, H, 1, &end));
   B.end = add_conv(pk.f32, end.w, end.b, C, H, 1, ROWS_PAIR, half);
   B.t_end = add_col16(pk.f32, end.w, end.b, C, H);
+  B.end_lin = add_conv(pk.f32, end.w, end.b, C, H, 1, ROWS_PLAIN);  // rows in natural order: the forward flow's un-fused form
   gm.blocks.push_back(std::move(B));
   return 0;
 }

@@ -243,13 +243,16 @@ struct GlowBlock {
   DevConv start, end;
   std::vector<DevConv> in, rs;
   size_t winv, an_bias, an_scale;
+  // the flow forwards (align_forward.h): the forward InvConvNear weight, exp(+logs), and `end` with its rows in natural order
+  size_t wfwd = 0, an_escale = 0;
+  DevConv end_lin;
   // the column-owner packings of glow_tail_kernel (coltile.h): res_skip_layers[last], end (rows in natural order), start
   DevCol t_rs, t_end, t_st;
   // fp16 packings of the WaveNet for wn_f16_kernel: in_layers (rows paired per 32-row tile), res_skip_layers[0 .. n - 2]
   std::vector<HConvW> h_in, h_rs;
   template <class F>
   void each_conv(F&& f) {
-    f(start), f(end);
+    f(start), f(end), f(end_lin);
     for (auto& c : in) f(c);
     for (auto& c : rs) f(c);
     for (auto& c : h_in) f(c);

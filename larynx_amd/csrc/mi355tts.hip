@@ -41,6 +41,7 @@
 #include "voc_out.h"
 #include "small_kernels.h"
 #include "griffin_lim.h"
+#include "align.h"
 #include "conv_f16.h"
 #include "pair_f16.h"
 #include "wn_f16.h"
@@ -441,6 +442,7 @@ extern "C" int mi355tts_mel_from_buffer(mi355tts_ctx* ctx, const float* mel, con
 #include "hifigan_forward.h"
 #include "host_join.h"
 #include "griffin_lim_forward.h"
+#include "align_forward.h"
 
 // ------------------------------------------------------------------ fused call + reservation
 // ids -> int16/f32 waveform in ONE call on ONE worker: GlowTTS and the vocoder are queued
@@ -617,6 +619,13 @@ extern "C" int mi355tts_reserve(mi355tts_ctx* ctx, int workers, int glow, int vo
     M = gm->hp.mel_channels;
   }
   size_t out_bytes = 0;
+  if (gm && max_frames >= gm->hp.n_sqz) {
+    // mi355tts_glow_align on the same shapes: the [F][P] scores, the direction bits and the staging of its results
+    const int P = std::min(std::min(max_ids, max_frames), PATH_MAX_P), ld = (max_frames + 3) & ~3;
+    const AlignLayout al = glow_align_layout(gm->hp, glow_enc_layout(gm->hp, max_batch, max_ids, P), max_batch, P, max_frames, ld, nullptr);
+    need = std::max(need, al.total);
+    out_bytes = sizeof(float) * (size_t)max_batch * M * ld + sizeof(int) * (size_t)max_batch * al.dur_ld + sizeof(float) * max_batch;
+  }
   if (hm) {
     const bool dn = denoiser != 0 && (long long)max_frames * hm->hop > DN_FFT;
     // both vocoder schedules (forked MRF chains / one stream) carve the same planes unless serial_branches is set
@@ -624,7 +633,7 @@ extern "C" int mi355tts_reserve(mi355tts_ctx* ctx, int workers, int glow, int vo
     const HifiLayout b = hifi_layout(hm->hp, hm->hop, max_batch, max_frames, dn, false, max_pad_samples);
     need = std::max(need, std::max(a.total, b.total));
     M = std::max(M, (int)hm->hp.num_mels);
-    out_bytes = (size_t)max_batch * ((size_t)max_frames * hm->hop + max_pad_samples) * (sizeof(float) + sizeof(short));
+    out_bytes = std::max(out_bytes, (size_t)max_batch * ((size_t)max_frames * hm->hop + max_pad_samples) * (sizeof(float) + sizeof(short)));
     if (dn) CHECK(ensure_denoiser_bias(ctx, hm, vocoder, hm->precision.load()));
   }
   mel_bytes = (size_t)max_batch * M * (size_t)((max_frames + 3) & ~3) * sizeof(float);

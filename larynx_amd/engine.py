@@ -257,6 +257,63 @@ class Engine:
         )
         return MelBatch(self, out.value)
 
+    def glow_align(self, model: int, ids, mel, frames=None, speaker_ids: typing.Union[None, int, typing.Sequence[int]] = None,
+                   want_latent: bool = False):
+        """Forced alignment (`mi355tts_glow_align`): which frames of `mel` belong to which phoneme id.  `ids` as in
+        `glow_infer`; `mel`: a `MelBatch` (its raw plane and frame counts) or an array [B, M, F] / [M, F] in the GlowTTS output
+        domain with `frames` valid columns per row (default: all).  Returns (durations int32 [B, P] — frames per id, zeros past
+        a row's length, each row summing to its frame count cut down to a multiple of n_sqz —, scores float32 [B]) and, with
+        `want_latent`, the latent z [B, M, F] as a third item.  Feed a row's durations to `glow_infer(durations=...)` to put
+        this mel's timing onto another take."""
+        rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
+        B = len(rows)
+        lens = np.array([len(r) for r in rows], np.int32)
+        ld = max(int(lens.max()) if B else 0, 1)
+        packed = np.zeros((B, ld), np.int64)
+        for b, r in enumerate(rows):
+            packed[b, : len(r)] = r
+        if isinstance(mel, MelBatch):
+            if frames is None:
+                frames = mel.frames
+            mel = mel.numpy("raw")
+        mel = np.ascontiguousarray(mel, np.float32)
+        if mel.ndim == 2:
+            mel = mel[None]
+        if mel.ndim != 3 or mel.shape[0] != B or mel.shape[2] < 1:
+            raise ValueError("mel: [B, M, F] with one row per id sequence")
+        fr = np.full(B, mel.shape[2], np.int32) if frames is None else np.ascontiguousarray(np.asarray(frames, np.int32).reshape(-1))
+        if fr.shape != (B,):
+            raise ValueError("frames: one count per row")
+        spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
+        dur = np.zeros((B, ld), np.int32)
+        score = np.zeros(B, np.float32)
+        z = np.zeros_like(mel) if want_latent else None
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_glow_align(
+                self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, ld, mel.ctypes.data,
+                fr.ctypes.data_as(C.POINTER(C.c_int32)), mel.shape[2], spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
+                0, dur.ctypes.data_as(C.POINTER(C.c_int32)), ld, score.ctypes.data_as(C.POINTER(C.c_float)), ffi.ptr(z),
+            ),
+        )
+        return (dur, score, z) if want_latent else (dur, score)
+
+    def maximum_path(self, value: np.ndarray, id_lens=None, frames=None):
+        """`mi355tts_op_maximum_path`: the reference's `maximum_path` (glow_tts/utils.py:59-96) on `value` [B, P, F] (or [P, F]),
+        rows `id_lens[b]` x `frames[b]` -> (durations int32 [B, P], scores float32 [B])."""
+        value = np.ascontiguousarray(value, np.float32)
+        if value.ndim == 2:
+            value = value[None]
+        B, P, F = value.shape
+        pl = np.full(B, P, np.int32) if id_lens is None else np.ascontiguousarray(id_lens, np.int32)
+        fr = np.full(B, F, np.int32) if frames is None else np.ascontiguousarray(frames, np.int32)
+        dur = np.zeros((B, P), np.int32)
+        score = np.zeros(B, np.float32)
+        i32 = C.POINTER(C.c_int32)
+        ffi.check(self.lib, self.lib.mi355tts_op_maximum_path(self._ctx, value.ctypes.data, B, P, F, pl.ctypes.data_as(i32), fr.ctypes.data_as(i32),
+                                                             dur.ctypes.data_as(i32), P, score.ctypes.data_as(C.POINTER(C.c_float))))
+        return dur, score
+
     @staticmethod
     def _prosody(lens: np.ndarray, ld: int, id_scales, durations, want_out: bool):
         """The `mi355tts_prosody` of a call and the arrays it points into (keep them alive until the call returns;

@@ -123,6 +123,16 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
         [_VP, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,
          C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(AudioSettingsC), C.c_uint32, C.POINTER(ProsodyC), C.POINTER(_VP)],
     ),
+    "mi355tts_glow_align": (
+        C.c_int,
+        [_VP, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
+         C.c_uint32, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), _VP],
+    ),
+    "mi355tts_op_maximum_path": (
+        C.c_int,
+        [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+         C.POINTER(C.c_float)],
+    ),
     "mi355tts_mel_durations": (C.c_int, [_VP, C.POINTER(C.c_int32), C.c_int]),
     "mi355tts_mel_batch": (C.c_int, [_VP]),
     "mi355tts_mel_channels": (C.c_int, [_VP]),

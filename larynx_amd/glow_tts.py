@@ -122,6 +122,19 @@ class HipGlowTextToSpeech(TextToSpeechModel):
             want_durations=want_durations,
         )
 
+    def align(self, phoneme_ids: np.ndarray, mels: typing.Union[MelBatch, np.ndarray],
+              settings: typing.Optional[SettingsType] = None) -> np.ndarray:
+        """Forced alignment: the mel frames every phoneme id occupies in `mels` (a `MelBatch` or an array [1, 80, F] / [80, F]
+        in this model's output domain: another take, another speaker, a mel from a training cache) -> int32 [P], each >= 1,
+        summing to F cut down to a multiple of n_sqz.  Honours the `speaker_id` setting.  `settings={"durations": d}` then
+        synthesises with this timing; `larynx_amd.alignment.align_spans` turns it into sample positions."""
+        speaker_idx = settings.get("speaker_id") if settings else None
+        ids = np.asarray(phoneme_ids, dtype=np.int64).reshape(-1)
+        if ids.size == 0:
+            raise ValueError("empty phoneme id sequence")
+        dur, _ = self.engine.glow_align(self.model_id, ids, mels, speaker_ids=None if speaker_idx is None else int(speaker_idx))
+        return dur[0]
+
 
 def mels_as_numpy(mels: typing.Union[MelBatch, np.ndarray]) -> np.ndarray:
     return mels.numpy("raw") if isinstance(mels, MelBatch) else np.asarray(mels)
