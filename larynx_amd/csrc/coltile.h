@@ -26,6 +26,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "prio.h"
+#include "tile_grid.h"
 #include <type_traits>
 
 namespace mi355tts {
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(512) void glow_tail_kernel(const GlowTailArgs a) {
   float* R3 = lds + 2 * COL_MAXROWS * COL_T;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.y;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int t0 = blockIdx.x * COL_T;
   if (t0 >= L) return;
   const int H = a.H, half = a.half, C = 2 * half;
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(512) void glow_fwd_kernel(const GlowFwdArgs a) {
   float* R3 = lds + 2 * COL_MAXROWS * COL_T;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.y;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int t0 = blockIdx.x * COL_T;
   if (t0 >= L) return;
   const int H = a.H, half = a.half, C = 2 * half;
@@ -569,7 +570,7 @@ __global__ __launch_bounds__(512) void oproj_ln_kernel(const OprojLnArgs a) {
   float* R2 = lds + COL_MAXROWS * COL_T;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.y;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int t0 = blockIdx.x * COL_T;
   if (t0 >= L) return;
   const int H = a.H;

@@ -81,8 +81,8 @@ __device__ __forceinline__ void conv_bf16_tile(const ConvArgs& a, const int tile
   const int t0 = tile_x * T_T;
   const int mt0 = (tile_y * WM + wm) * MB;
 
-  const int Lin = a.in_len ? a.in_len[b] * a.in_mul : a.in_const;
-  const int Lout = a.out_len ? a.out_len[b] * a.out_mul : a.out_const;
+  const int Lin = tile_len(a.in_len, a.in_mul, a.in_const, b);
+  const int Lout = tile_len(a.out_len, a.out_mul, a.out_const, b);
   const int n_len = (EPI == EPI_UPSAMPLE) ? (Lin > 0 ? Lin + (K - 1) : 0) : Lout;  // extent of the GEMM's N axis
   if (t0 >= n_len) return;  // uniform per workgroup
 
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void conv_bf16_kernel(const Conv
   int tile_x, tile_y;
   int gx = gridDim.x;
   const int lin = blockIdx.x + blockIdx.y * gridDim.x;
-  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (conv_mfma.h, row_tiles)
+  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (tile_grid.h, row_tiles)
     gx = row_tiles(conv_n_len<K, EPI>(a, blockIdx.z), 32 * NB * WN);
     if (lin >= gx * (int)gridDim.y) return;
   }
@@ -464,10 +464,10 @@ template <int K0, int K1, int K2, int MB, int NB, int WM, int WN, int H0, int H1
 #endif
 __global__ __launch_bounds__(64 * WM * WN * KS, (NB == 4 && KS == 1) ? BF16_OCC : 1) void conv_bf16_group_kernel(const ConvGroupArgs g) {
   constexpr int L0 = conv_bf16_lds_units<NB, WN, H0>(), L1 = conv_bf16_lds_units<NB, WN, H1>(), L2 = conv_bf16_lds_units<NB, WN, H2>();
-  __shared__ uint4 xs[L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2)];
+  __shared__ uint4 xs[max3(L0, L1, L2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
-  const bool ragged = gridDim.z > 1;  // a row deals only its own tiles (conv_mfma.h, row_tiles)
+  const bool ragged = gridDim.z > 1;  // a row deals only its own tiles (tile_grid.h, row_tiles)
   constexpr int T_T = 32 * NB * WN;
   int tx, ty;
   if (lin < g.off[1]) {

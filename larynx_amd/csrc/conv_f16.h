@@ -341,8 +341,8 @@ __device__ __forceinline__ void conv_f16_tile(const HConvArgs& a, const int tile
   const int t0 = tile_x * T_T;
   const int mt0 = (tile_y * WM + wm) * MB;
 
-  const int Lin = a.in_len ? a.in_len[b] * a.in_mul : a.in_const;
-  const int Lout = a.out_len ? a.out_len[b] * a.out_mul : a.out_const;
+  const int Lin = tile_len(a.in_len, a.in_mul, a.in_const, b);
+  const int Lout = tile_len(a.out_len, a.out_mul, a.out_const, b);
   const int n_len = (EPI == EPI_UPSAMPLE) ? (Lin > 0 ? Lin + (K - 1) : 0) : Lout;
   if (t0 >= n_len) return;  // uniform per workgroup
   F16_STAMP(0);
@@ -437,10 +437,10 @@ __device__ __forceinline__ void conv_f16_tile(const HConvArgs& a, const int tile
 template <int K, int EPI>
 __device__ __forceinline__ int conv_f16_n_len(const HConvArgs& a, int b) {
   if (EPI == EPI_UPSAMPLE) {
-    const int Lin = a.in_len ? a.in_len[b] * a.in_mul : a.in_const;
+    const int Lin = tile_len(a.in_len, a.in_mul, a.in_const, b);
     return Lin > 0 ? Lin + (K - 1) : 0;
   }
-  return a.out_len ? a.out_len[b] * a.out_mul : a.out_const;
+  return tile_len(a.out_len, a.out_mul, a.out_const, b);
 }
 
 template <int K, int MB, int NB, int WM, int WN, int HALO, int CH, int EPI, bool MRF, int RING = 3>
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(64 * WM * WN, F16_MIN_WAVES) void conv_f16_kernel(c
   int tile_x, tile_y;
   int gx = gridDim.x;
   const int lin = blockIdx.x + blockIdx.y * gridDim.x;
-  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (conv_mfma.h, row_tiles)
+  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (tile_grid.h, row_tiles)
     gx = row_tiles(conv_f16_n_len<K, EPI>(a, blockIdx.z), 32 * NB * WN);
     if (lin >= gx * (int)gridDim.y) return;
   }
@@ -467,7 +467,7 @@ struct HConvGroupArgs {
 template <int K0, int K1, int K2, int MB, int NB, int WM, int WN, int H0, int H1, int H2, int CH, int RING = 3>
 __global__ __launch_bounds__(64 * WM * WN, F16_MIN_WAVES) void conv_f16_group_kernel(const HConvGroupArgs g) {
   constexpr int L0 = conv_f16_lds_units<NB, WN, H0, CH, RING>(), L1 = conv_f16_lds_units<NB, WN, H1, CH, RING>(), L2 = conv_f16_lds_units<NB, WN, H2, CH, RING>();
-  __shared__ uint4 xs[L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2)];
+  __shared__ uint4 xs[max3(L0, L1, L2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
   const bool ragged = gridDim.z > 1;
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(256) void post_f16_kernel(const HPostArgs a) {
   __shared__ float wsm[MAXOCT * 8 * K];
   __shared__ float pm[4];
   const int b = blockIdx.y;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int t0 = blockIdx.x * HPOST_TW;
   if (t0 >= L) return;
   const int tid = threadIdx.x;

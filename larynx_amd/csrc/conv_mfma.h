@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "prio.h"
+#include "tile_grid.h"
 
 // Micro-benchmark ablations (tools/conv_probe.py) are compiled in only for probe builds
 // (-DMI355TTS_ABLATION): a runtime test around the weight loads puts them behind a branch,
@@ -123,41 +124,6 @@ struct ConvArgs {
   const void* w16;
   int nslab;
 };
-
-// XCD-aware tile order.  The dispatcher deals workgroup `lin` to XCD `lin % 8`, each XCD
-// with its own L2.  Tiles that share input (the m-tiles of one time tile, and
-// neighbouring time tiles through the halo) should meet in ONE L2, so the linear id is
-// re-dealt: XCD x gets a contiguous run of tiles, m-tile fastest.  Bijective for any n
-// (MI355X_MICROARCH.md, T1); a wrong placement guess costs speed, never correctness.
-//
-// `rows_major` != 0 flips the order inside the run: XCD x then owns a contiguous range of ROW tiles (with all
-// their time tiles), i.e. 1/8 of the weights — for launches whose packed weights do not fit one 4 MB L2 while
-// their input does (the stage-0 upsampler of HiFi-GAN 'high': 8.4 MB of weights, 1.3 MB of input; with time
-// dealt across the XCDs every XCD streamed all 8.4 MB once per time tile: 86 MB fetched per launch).
-__device__ __forceinline__ void xcd_tile_lin(int lin, int gx, int gy, int& tx, int& ty, int rows_major = 0) {
-  const int n = gx * gy;
-  const int xcd = lin & 7, slot = lin >> 3;
-  const int q = n >> 3, r = n & 7;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  if (rows_major) {
-    tx = id % gx;
-    ty = id / gx;
-  } else {
-    ty = id % gy;
-    tx = id / gy;
-  }
-}
-__device__ __forceinline__ void xcd_tile(int gx, int gy, int& tx, int& ty, int rows_major = 0) {
-  xcd_tile_lin(blockIdx.x + blockIdx.y * gx, gx, gy, tx, ty, rows_major);
-}
-
-// Ragged batches (gridDim.z > 1 rows of different lengths): the grid is sized for the longest row, and dealing
-// contiguous runs of the GRID's tiles to the XCDs would hand a short row's few real tiles to XCD 0 (and 1) alone —
-// over a batch of 8 rows with lengths 0.14 ... 1.0 of the longest, XCD 0 gets 8 shares of work and XCD 7 one
-// (measured on BASELINE config 4: the 32-channel fused pair launches ran at 0.24 of peak against 0.59 at batch 1).
-// So a row deals only ITS OWN tiles: the first gx_row * gy workgroups of the row's grid slice take them (spread
-// evenly over the XCDs by the dispatcher's round-robin), the rest exit.
-__device__ __forceinline__ int row_tiles(int n_len, int tile) { return (n_len + tile - 1) / tile; }
 
 // extent of the implicit GEMM's N axis for batch row b (conv_tile derives the same value)
 template <int K, int EPI>
@@ -572,7 +538,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int tile_x, c
 #pragma unroll
     for (int rr = 0; rr < R; ++rr) {
       const int r = kg * R + rr;
-      rowin[rr] = (r & 3) + 8 * (r >> 2) + rbase;
+      rowin[rr] = acc_row(r) + rbase;
     }
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
@@ -667,7 +633,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int tile_x, c
 #pragma unroll
     for (int rr = 0; rr < H; ++rr) {
       const int r = kg * H + rr;
-      const int i = (r & 3) + 8 * (r >> 2) + rbase;  // 0..15
+      const int i = acc_row(r) + rbase;  // 0..15
       b0[rr] = a.bias ? a.bias[mt0 * 32 + i] : 0.f;
       b1[rr] = a.bias ? a.bias[mt0 * 32 + 16 + i] : 0.f;
       const int c = tile_y * 16 + i;
@@ -851,7 +817,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS, ((EPI == EPI_LINEAR && ((NB == 1
   int tile_x, tile_y;
   int gx = gridDim.x;
   const int lin = blockIdx.x + blockIdx.y * gridDim.x;
-  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (see row_tiles)
+  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (tile_grid.h, row_tiles)
     gx = row_tiles(conv_n_len<K, EPI>(a, blockIdx.z), WN * NB * 32);
     if (lin >= gx * (int)gridDim.y) return;
   }
@@ -958,10 +924,10 @@ __global__ __launch_bounds__(64 * WM * WN * KS, ((NB == 1 && MB == 2) || WM == 4
   constexpr int L0 = conv_lds_floats<K0, CI_C, MB, NB, WN, KS, H0, EPI_LINEAR, WM>();
   constexpr int L1 = conv_lds_floats<K1, CI_C, MB, NB, WN, KS, H1, EPI_LINEAR, WM>();
   constexpr int L2 = conv_lds_floats<K2, CI_C, MB, NB, WN, KS, H2, EPI_LINEAR, WM>();
-  __shared__ float xs[L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2)];
+  __shared__ float xs[max3(L0, L1, L2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
-  const bool ragged = gridDim.z > 1;  // rows of different lengths: a row deals only its own tiles (see row_tiles)
+  const bool ragged = gridDim.z > 1;  // rows of different lengths: a row deals only its own tiles (tile_grid.h, row_tiles)
   constexpr int T_T = WN * NB * 32;
   int tx, ty;
   CONV_WG_STAMP(lin, 0);

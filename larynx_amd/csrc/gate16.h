@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "prio.h"
+#include "tile_grid.h"
 
 namespace mi355tts {
 
@@ -69,8 +70,8 @@ __global__ __launch_bounds__(512) void gate16_kernel(const Gate16Args a) {
   __shared__ float xs[(32 * J * GATE16_XW > 4096 * RTW) ? 32 * J * GATE16_XW : 4096 * RTW];  // [32 J][48]; afterwards the partial tiles [RTW][8][2][4][64]
   const int tid = threadIdx.x, lane = tid & 63, kg = tid >> 6;
   const int b = blockIdx.z;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
-  // ragged batch: a row deals only its own tiles (conv_mfma.h, row_tiles); XCD x takes a contiguous run of them, time
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
+  // ragged batch: a row deals only its own tiles (tile_grid.h, row_tiles); XCD x takes a contiguous run of them, time
   // tile fastest: an XCD's L2 then holds 1/8 of the weights (the bigger operand here) and the whole input
   const int gx = (L + 31) / 32, gy = gridDim.y;
   const int lin = blockIdx.x + blockIdx.y * gridDim.x;
@@ -249,7 +250,7 @@ __global__ __launch_bounds__(512) void lin16_kernel(const Lin16Args a) {
   static_assert(!LN || XW <= 64, "LayerNorm prologue: one lane per staged column");
   const int tid = threadIdx.x, lane = tid & 63, kg = tid >> 6;
   const int b = blockIdx.z;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int gx = (L + TC - 1) / TC, gy = gridDim.y;
   const int lin = blockIdx.x + blockIdx.y * gridDim.x;
   if (lin >= gx * gy) return;  // ragged batch: a row deals only its own tiles

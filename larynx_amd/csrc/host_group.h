@@ -3,10 +3,9 @@
 // (one translation unit: included once by mi355tts.hip, ahead of host_launch.h)
 #pragma once
 
-#include <type_traits>
+#include "tile_grid.h"
 
-template <int V>
-using int_c = std::integral_constant<int, V>;
+using mi355tts::int_c;
 
 // Maps a run-time integer onto a list of compile-time values: switch_const<3, 5, 7, 11>(K, [&](auto k) { ... }) calls the lambda
 // with int_c<K> (decltype(k)::value is a template argument) and returns false when v is not in the list.
@@ -22,7 +21,7 @@ constexpr bool halo_fits(int K, int dil, int pad, int halo) { return (K - 1) * d
 
 // The layout of a grouped launch: the same-geometry steps of a stage's three MRF chains as ONE 1-D grid.  Members run in tap
 // order, longest-running first; member ord[i] owns workgroups [off[i], off[i + 1]) and off[3] is the grid size.  Every member's
-// range is padded to a multiple of 8: the hardware deals workgroup i to XCD i % 8, and xcd_tile_lin (conv_mfma.h) maps a member's
+// range is padded to a multiple of 8: the hardware deals workgroup i to XCD i % 8, and xcd_tile_lin (tile_grid.h) maps a member's
 // local workgroup id onto its tiles assuming exactly that — a range that started off a multiple of 8 would put neighbouring tiles
 // on different XCDs' L2s.  The padding workgroups exit at once.
 struct GroupLayout {

@@ -178,8 +178,8 @@ __global__ __launch_bounds__(64 * NW, MRF_OCC(T, NW)) void mrf_small_kernel(cons
   const int wave = tid >> 6;
   const int b = blockIdx.z;
   int tile_x, tile_y;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
-  const int gx = gridDim.z > 1 ? row_tiles(L, T) : (int)gridDim.x / 2;  // ragged batch: this row's own tiles only (conv_mfma.h)
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
+  const int gx = gridDim.z > 1 ? row_tiles(L, T) : (int)gridDim.x / 2;  // ragged batch: this row's own tiles only (tile_grid.h)
   // 1-D grid of 2 * tiles workgroups: runs of MRF_MIX "k = 11" workgroups alternate with runs of MRF_MIX "k = 3 + 7"
   // ones, so that the workgroups that end up sharing a CU (dispatch order: one per CU, then the second, ...) are of
   // both kinds and at different points of their conv sequence — workgroups of one kind started together run their
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(128) void mrf8_kernel(const MrfArgs a) {
   const int wave = tid >> 6;
   const int b = blockIdx.z;
   int tile_x, tile_y;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int gx = gridDim.z > 1 ? row_tiles(L, T) : (int)gridDim.x / 2;
   const int lin = blockIdx.x;
   if (lin >= 2 * gx) return;

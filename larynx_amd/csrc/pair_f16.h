@@ -62,7 +62,7 @@ __device__ __forceinline__ void pair_f16_tile(const HPairArgs& a, const int tile
   const int wm = wave % WM;
   const int wn = wave / WM;
   const int mt0 = wm * MB;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int t0 = tile_x * TO;  // first output column of the tile
   if (t0 >= L) return;
   constexpr int P2 = (K - 1) / 2;
@@ -278,25 +278,25 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void pair_f16_group_kernel(cons
   constexpr int ROWS = 32 * MB * WM;
   constexpr int L0 = pair_f16_lds_units<K0, NB, WN, H0, CH, RING>(ROWS), L1 = pair_f16_lds_units<K1, NB, WN, H1, CH, RING>(ROWS),
                 L2 = pair_f16_lds_units<K2, NB, WN, H2, CH, RING>(ROWS);
-  __shared__ uint4 lds[L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2)];
+  __shared__ uint4 lds[max3(L0, L1, L2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
   const bool ragged = gridDim.z > 1;
   if (lin < g.off[1]) {
     const HPairArgs& a = g.p[0];
-    const int gx = ragged ? pair_f16_tiles<K0, NB, WN>(a.len ? a.len[b] * a.len_mul : a.len_const) : g.gx[0];
+    const int gx = ragged ? pair_f16_tiles<K0, NB, WN>(tile_len(a.len, a.len_mul, a.len_const, b)) : g.gx[0];
     if (lin >= gx) return;
     pair_f16_tile<K0, MB, NB, WM, WN, H0, CH, RING>(a, lin, b, lds);
   } else if (lin < g.off[2]) {
     const HPairArgs& a = g.p[1];
     const int l = lin - g.off[1];
-    const int gx = ragged ? pair_f16_tiles<K1, NB, WN>(a.len ? a.len[b] * a.len_mul : a.len_const) : g.gx[1];
+    const int gx = ragged ? pair_f16_tiles<K1, NB, WN>(tile_len(a.len, a.len_mul, a.len_const, b)) : g.gx[1];
     if (l >= gx) return;
     pair_f16_tile<K1, MB, NB, WM, WN, H1, CH, RING>(a, l, b, lds);
   } else {
     const HPairArgs& a = g.p[2];
     const int l = lin - g.off[2];
-    const int gx = ragged ? pair_f16_tiles<K2, NB, WN>(a.len ? a.len[b] * a.len_mul : a.len_const) : g.gx[2];
+    const int gx = ragged ? pair_f16_tiles<K2, NB, WN>(tile_len(a.len, a.len_mul, a.len_const, b)) : g.gx[2];
     if (l >= gx) return;
     pair_f16_tile<K2, MB, NB, WM, WN, H2, CH, RING>(a, l, b, lds);
   }

@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256, CI_C == 16 ? 4 : 3) void rb_conv_kernel(const 
   int tile_x, tile_y;
   int gx = gridDim.x;
   const int lin = blockIdx.x + blockIdx.y * gridDim.x;
-  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (conv_mfma.h, row_tiles)
+  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (tile_grid.h, row_tiles)
     gx = row_tiles(conv_n_len<K, EPI>(a, blockIdx.z), 64);
     if (lin >= gx * (int)gridDim.y) return;
   }
@@ -436,7 +436,7 @@ template <int K0, int K1, int K2, int NB = 2>
 __global__ __launch_bounds__(256, NB > 2 ? 3 : 4) void rb_group_kernel(const ConvGroupArgs g) {
   constexpr int H0 = RbCfg<K0>::HALO, H1 = RbCfg<K1>::HALO, H2 = RbCfg<K2>::HALO;
   constexpr int L0 = rb_lds_floats<H0, NB>(), L1 = rb_lds_floats<H1, NB>(), L2 = rb_lds_floats<H2, NB>();
-  __shared__ float xs[L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2)];
+  __shared__ float xs[max3(L0, L1, L2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
   const bool ragged = gridDim.z > 1;

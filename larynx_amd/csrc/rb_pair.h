@@ -107,7 +107,7 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
   const int mb = wave % CB, tg = wave / CB;
   const int col = lane & 31, half = lane >> 5, rbase = 4 * half;
   const int wcol0 = tg * 64;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int j0 = tile_x * T2;  // first output column of this workgroup
   if (j0 >= L) return;
   const int gt0 = j0 - P2;             // global column of parked-tile column 0
@@ -169,7 +169,7 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
   {
     float bb[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bb[r] = a.b1[mb * 32 + (r & 3) + 8 * (r >> 2) + rbase];
+    for (int r = 0; r < 16; ++r) bb[r] = a.b1[mb * 32 + acc_row(r) + rbase];
     __syncthreads();  // every wave has read its last x column: the parked tile goes over the x tile
     // park lrelu(conv1 + bias); columns outside the sequence are conv2's ZERO padding
 #pragma unroll
@@ -179,7 +179,7 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
       const bool inside = g >= 0 && g < L;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + rbase;
+        const int row = mb * 32 + acc_row(r) + rbase;
         float v = acc[nb][r] + bb[r];
         v = v > 0.f ? v : v * slope;
         xs[row * TW + jj] = inside ? v : 0.f;
@@ -201,11 +201,11 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
   }
   auto epi_loads = [&]() {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bb2[r] = a.b2[mb * 32 + (r & 3) + 8 * (r >> 2) + rbase];
+    for (int r = 0; r < 16; ++r) bb2[r] = a.b2[mb * 32 + acc_row(r) + rbase];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) rv[nb][r] = xb[(mb * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld + gcs[nb]];
+      for (int r = 0; r < 16; ++r) rv[nb][r] = xb[(mb * 32 + acc_row(r) + rbase) * a.ld + gcs[nb]];
   };
   constexpr bool PREFETCH = CB == 2 ? (RBP_PREFETCH64 != 0) : (RBP_PREFETCH32 != 0);
   const bool interior = RBP_WIDE_STORES && !PREFETCH && j0 + T1 <= L;  // uniform: every column of the tile is inside the sequence
@@ -219,13 +219,13 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
     // arithmetic, same order: ((acc + bias) + x) * alpha [+ y].
     typedef float rbp_f4 __attribute__((ext_vector_type(4), aligned(4)));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bb2[r] = a.b2[mb * 32 + (r & 3) + 8 * (r >> 2) + rbase];
+    for (int r = 0; r < 16; ++r) bb2[r] = a.b2[mb * 32 + acc_row(r) + rbase];
     __syncthreads();  // every wave has read its last parked column
     float* tw = xs + wave * (32 * 64);
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tw[((r & 3) + 8 * (r >> 2) + rbase) * 64 + nb * 32 + col] = acc[nb][r] + bb2[r];
+      for (int r = 0; r < 16; ++r) tw[(acc_row(r) + rbase) * 64 + nb * 32 + col] = acc[nb][r] + bb2[r];
     __builtin_amdgcn_wave_barrier();  // no instruction: a wave's LDS operations execute in order
     float* yb = a.y + (long long)b * a.bs;
     const float alpha = a.alpha;
@@ -287,13 +287,13 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
     if (a.accum) {
       float ov[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ov[r] = yb[(mb * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld];
+      for (int r = 0; r < 16; ++r) ov[r] = yb[(mb * 32 + acc_row(r) + rbase) * a.ld];
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] += ov[r];
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (toks[nb]) yb[(mb * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld] = v[r];
+      if (toks[nb]) yb[(mb * 32 + acc_row(r) + rbase) * a.ld] = v[r];
   }
 }
 
@@ -302,8 +302,8 @@ __global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rb_pair_kernel(co
   __shared__ float xs[RbPairGeom<K, CB>::LDS];
   int tile_x, tile_y;
   int gx = gridDim.x;
-  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (conv_mfma.h, row_tiles)
-    gx = row_tiles(a.len ? a.len[blockIdx.z] * a.len_mul : a.len_const, RbPairGeom<K, CB>::T1 - (K - 1));
+  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (tile_grid.h, row_tiles)
+    gx = row_tiles(tile_len(a.len, a.len_mul, a.len_const, blockIdx.z), RbPairGeom<K, CB>::T1 - (K - 1));
     if ((int)blockIdx.x >= gx) return;
   }
   xcd_tile_lin(blockIdx.x, gx, 1, tile_x, tile_y);  // neighbouring tiles share their halo through one XCD's L2
@@ -314,10 +314,10 @@ __global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rb_pair_kernel(co
 template <int K0, int K1, int K2, int CB>
 __global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rb_pair_group_kernel(const PairGroupArgs g) {
   constexpr int L0 = RbPairGeom<K0, CB>::LDS, L1 = RbPairGeom<K1, CB>::LDS, L2 = RbPairGeom<K2, CB>::LDS;
-  __shared__ float xs[L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2)];
+  __shared__ float xs[max3(L0, L1, L2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
-  auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(p.len ? p.len[b] * p.len_mul : p.len_const, t2) : gx_grid; };
+  auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(tile_len(p.len, p.len_mul, p.len_const, b), t2) : gx_grid; };
   constexpr int T1 = RbPairGeom<K0, CB>::T1;
   int tx, ty;
   CONV_WG_STAMP(lin, 0);

@@ -145,7 +145,7 @@ __device__ __forceinline__ void pair_tile(const PairArgs& a, const int tile_x, c
   const int kg = wave >> 2;
   const int col = lane & 31, half = lane >> 5;
   const int rbase = 4 * half;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int j0 = tile_x * T2;  // first output column of this workgroup
   if (j0 >= L) return;
   const int gt0 = j0 - P2;                  // global column of parked-tile column 0
@@ -243,13 +243,13 @@ __device__ __forceinline__ void pair_tile(const PairArgs& a, const int tile_x, c
     // park lrelu(conv1 + bias); columns outside the sequence are conv2's ZERO padding
     float bb[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bb[r] = a.b1[mb_own * 32 + (r & 3) + 8 * (r >> 2) + rbase];
+    for (int r = 0; r < 16; ++r) bb[r] = a.b1[mb_own * 32 + acc_row(r) + rbase];
     const int jj = (wn * NB + nb_own) * 32 + col;
     const int g = gt0 + jj;
     const bool inside = g >= 0 && g < L;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = mb_own * 32 + (r & 3) + 8 * (r >> 2) + rbase;
+      const int row = mb_own * 32 + acc_row(r) + rbase;
       float v = own[r] + bb[r];
       v = v > 0.f ? v : v * slope;
       ts[row * TW + jj] = inside ? v : 0.f;
@@ -265,7 +265,7 @@ __device__ __forceinline__ void pair_tile(const PairArgs& a, const int tile_x, c
   {
     float bb[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bb[r] = a.b2[mb_own * 32 + (r & 3) + 8 * (r >> 2) + rbase];
+    for (int r = 0; r < 16; ++r) bb[r] = a.b2[mb_own * 32 + acc_row(r) + rbase];
     const int jj = (wn * NB + nb_own) * 32 + col;
     const int g = j0 + jj;
     const bool tok = jj < T2 && g < L;
@@ -274,19 +274,19 @@ __device__ __forceinline__ void pair_tile(const PairArgs& a, const int tile_x, c
     float* yb = a.y + (long long)b * a.bs + gc;
     float rv[16], v[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) rv[r] = rb[(mb_own * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld];
+    for (int r = 0; r < 16; ++r) rv[r] = rb[(mb_own * 32 + acc_row(r) + rbase) * a.ld];
 #pragma unroll
     for (int r = 0; r < 16; ++r) v[r] = (own[r] + bb[r] + rv[r]) * a.alpha;
     if (a.accum) {
       float ov[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ov[r] = yb[(mb_own * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld];
+      for (int r = 0; r < 16; ++r) ov[r] = yb[(mb_own * 32 + acc_row(r) + rbase) * a.ld];
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] += ov[r];
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (tok) yb[(mb_own * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld] = v[r];
+      if (tok) yb[(mb_own * 32 + acc_row(r) + rbase) * a.ld] = v[r];
   }
 }
 
@@ -296,8 +296,8 @@ __global__ __launch_bounds__(512, CB == 2 ? 4 : 1) void resblock_pair_kernel(con
   float* const ts = xs + PairGeom<K, CB, NB>::RED;
   int tile_x, tile_y;
   int gx = gridDim.x;
-  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (conv_mfma.h, row_tiles)
-    gx = row_tiles(a.len ? a.len[blockIdx.z] * a.len_mul : a.len_const, PairGeom<K, CB, NB>::T1 - (K - 1));
+  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (tile_grid.h, row_tiles)
+    gx = row_tiles(tile_len(a.len, a.len_mul, a.len_const, blockIdx.z), PairGeom<K, CB, NB>::T1 - (K - 1));
     if ((int)blockIdx.x >= gx) return;
   }
   xcd_tile_lin(blockIdx.x, gx, 1, tile_x, tile_y);  // neighbouring tiles share their halo through one XCD's L2
@@ -315,12 +315,12 @@ template <int K0, int K1, int K2, int CB, int NB>
 // (C = 64: capped at 128 VGPRs so that two of the 52 KB workgroups share a CU)
 __global__ __launch_bounds__(512, CB == 2 ? 4 : 1) void pair_group_kernel(const PairGroupArgs g) {
   constexpr int L0 = PairGeom<K0, CB, NB>::LDS, L1 = PairGeom<K1, CB, NB>::LDS, L2 = PairGeom<K2, CB, NB>::LDS;
-  __shared__ float xs[L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2)];
+  __shared__ float xs[max3(L0, L1, L2)];
   float* const ts = xs + PairGeom<K0, CB, NB>::RED;
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
-  // ragged batch: a row deals only its own tiles (conv_mfma.h, row_tiles)
-  auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(p.len ? p.len[b] * p.len_mul : p.len_const, t2) : gx_grid; };
+  // ragged batch: a row deals only its own tiles (tile_grid.h, row_tiles)
+  auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(tile_len(p.len, p.len_mul, p.len_const, b), t2) : gx_grid; };
   constexpr int T1 = PairGeom<K0, CB, NB>::T1;
   int tx, ty;
   if (lin < g.off[1]) {

@@ -127,7 +127,7 @@ __device__ __forceinline__ void pair_bf16_tile(const PairArgs& a, const int tile
   const int wn = wave % WN;
   const int wm = wave / WN;
   const int col = lane & 31, half = lane >> 5;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int j0 = tile_x * T2;  // first output column of this workgroup
   if (j0 >= L) return;
   const int gt0 = j0 - P2;                  // global column of parked-tile column 0
@@ -214,7 +214,7 @@ __device__ __forceinline__ void pair_bf16_tile(const PairArgs& a, const int tile
     // channels 8*o + 4*half + (0..3) of its column for the four octets o of its m-block: one 8-byte store per plane.
     float bb[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bb[r] = a.b1[wm * 32 + (r & 3) + 8 * (r >> 2) + rbase];
+    for (int r = 0; r < 16; ++r) bb[r] = a.b1[wm * 32 + acc_row(r) + rbase];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const int jj = (wn * NB + nb) * 32 + col;
@@ -247,7 +247,7 @@ __device__ __forceinline__ void pair_bf16_tile(const PairArgs& a, const int tile
   // ---- epilogue: + bias + f32 residual, batched loads from clamped addresses
   float bb[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) bb[r] = a.b2[wm * 32 + (r & 3) + 8 * (r >> 2) + rbase];
+  for (int r = 0; r < 16; ++r) bb[r] = a.b2[wm * 32 + acc_row(r) + rbase];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int jj = (wn * NB + nb) * 32 + col;
@@ -258,19 +258,19 @@ __device__ __forceinline__ void pair_bf16_tile(const PairArgs& a, const int tile
     float* yb = a.y + (long long)b * a.bs + gc;
     float rv[16], v[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) rv[r] = rb[(wm * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld];
+    for (int r = 0; r < 16; ++r) rv[r] = rb[(wm * 32 + acc_row(r) + rbase) * a.ld];
 #pragma unroll
     for (int r = 0; r < 16; ++r) v[r] = (acc[nb][r] + bb[r] + rv[r]) * a.alpha;
     if (a.accum) {
       float ov[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ov[r] = yb[(wm * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld];
+      for (int r = 0; r < 16; ++r) ov[r] = yb[(wm * 32 + acc_row(r) + rbase) * a.ld];
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] += ov[r];
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (tok) yb[(wm * 32 + (r & 3) + 8 * (r >> 2) + rbase) * a.ld] = v[r];
+      if (tok) yb[(wm * 32 + acc_row(r) + rbase) * a.ld] = v[r];
   }
 }
 
@@ -280,8 +280,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM == 2 && WN == 4) ? 4 : 1) void pa
   __shared__ uint4 xs[PairBf16Geom<K, WM, WN, NB>::UNITS];
   int tile_x, tile_y;
   int gx = gridDim.x;
-  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (conv_mfma.h, row_tiles)
-    gx = row_tiles(a.len ? a.len[blockIdx.z] * a.len_mul : a.len_const, PairBf16Geom<K, WM, WN, NB>::T1 - (K - 1));
+  if (gridDim.z > 1) {  // ragged batch: this row's own tiles only (tile_grid.h, row_tiles)
+    gx = row_tiles(tile_len(a.len, a.len_mul, a.len_const, blockIdx.z), PairBf16Geom<K, WM, WN, NB>::T1 - (K - 1));
     if ((int)blockIdx.x >= gx) return;
   }
   xcd_tile_lin(blockIdx.x, gx, 1, tile_x, tile_y);  // neighbouring tiles share their halo through one XCD's L2
@@ -292,11 +292,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM == 2 && WN == 4) ? 4 : 1) void pa
 template <int K0, int K1, int K2, int WM, int WN, int NB, int TERMS>
 __global__ __launch_bounds__(64 * WM * WN, (WM == 2 && WN == 4) ? 4 : 1) void pair_bf16_group_kernel(const PairGroupArgs g) {
   constexpr int U0 = PairBf16Geom<K0, WM, WN, NB>::UNITS, U1 = PairBf16Geom<K1, WM, WN, NB>::UNITS, U2 = PairBf16Geom<K2, WM, WN, NB>::UNITS;
-  __shared__ uint4 xs[U0 > U1 ? (U0 > U2 ? U0 : U2) : (U1 > U2 ? U1 : U2)];
+  __shared__ uint4 xs[max3(U0, U1, U2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
-  // ragged batch: a row deals only its own tiles (conv_mfma.h, row_tiles)
-  auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(p.len ? p.len[b] * p.len_mul : p.len_const, t2) : gx_grid; };
+  // ragged batch: a row deals only its own tiles (tile_grid.h, row_tiles)
+  auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(tile_len(p.len, p.len_mul, p.len_const, b), t2) : gx_grid; };
   constexpr int T1 = PairBf16Geom<K0, WM, WN, NB>::T1;
   int tx, ty;
   if (lin < g.off[1]) {

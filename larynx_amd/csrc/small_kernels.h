@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "prio.h"
+#include "tile_grid.h"
 #include <stdint.h>
 
 namespace mi355tts {
@@ -393,7 +394,7 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const float* qkv, l
       float* dst = band ? relS + rbase * 33 + col : S + rbase * PS + nb * 32 + col;
       const int rs = band ? 33 : PS;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dst[((r & 3) + 8 * (r >> 2)) * rs] = acc[r] * scale;  // keys >= P: never read
+      for (int r = 0; r < 16; ++r) dst[acc_row(r) * rs] = acc[r] * scale;  // keys >= P: never read
     }
   }
   ATT_STAMP(3);
@@ -510,7 +511,7 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const float* qkv, l
   if (unit) {
     float* dst = red + ((ks * ncb + cb) * 32 + rbase) * 32 + col;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dst[((r & 3) + 8 * (r >> 2)) * 32] = acc[r];
+    for (int r = 0; r < 16; ++r) dst[acc_row(r) * 32] = acc[r];
   }
   __syncthreads();
   // ---- ... and thread t sums and stores channels (t >> 5) + 16 m of query t & 31, lanes along time

@@ -13,6 +13,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "tile_grid.h"
+
 namespace mi355tts {
 
 constexpr int POST_TW = 256;          // output columns per workgroup
@@ -49,7 +51,7 @@ __global__ __launch_bounds__(256) void post_conv_kernel(const PostArgs a) {
   __shared__ float red[3 * POST_TW];
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
-  const int L = a.len ? a.len[b] * a.len_mul : a.len_const;
+  const int L = tile_len(a.len, a.len_mul, a.len_const, b);
   const int t0 = blockIdx.x * POST_TW;
   if (t0 >= L) return;
   const int i = tid & 63, h = tid >> 6;  // wave h: outputs t0 + 4 i ... + 3, channels 4 h ... 4 h + 3 of each chunk
