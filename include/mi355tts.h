@@ -307,6 +307,52 @@ int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi355tts_mel*
                                float* phase_out, float* wav_f32, int16_t* wav_i16, int64_t wav_ld, int iterations,
                                uint32_t flags);
 
+/* ---- mel analysis: a recording into the voice's own mel domain -----------------
+ * waveform -> mi355tts_mel, the inverse direction of the transforms above, in ONE launch (csrc/mel_analysis.h): 1024-point
+ * frames every 256 samples (fft and hop are not parameters, as for Griffin-Lim), mag[k] = sqrt(re^2 + im^2 + mag_eps) in f32,
+ * amp[m] = sum_k mel_basis[m][k] mag[k] (k ascending, one fma per term, over the row's non-zero band), then
+ *   vocoder plane (1): ln(max(amp, 1e-5)) with do_dynamic_range_compression (AudioSettings.dynamic_range_compression,
+ *                      larynx/audio.py:106-108), else amp;
+ *   raw plane (0):     the inverse of the mel transforms, switch by switch: convert_db_to_amp gives spec_gain * log10(max(1e-5,
+ *                      amp)) (amp_to_db, audio.py:55-56), otherwise the vocoder plane's value; signal_norm then applies
+ *                      AudioSettings.normalize (audio.py:65-81) in its operation order, both clip variants;
+ *   audio == NULL:     both planes ln(max(amp, 1e-5)).
+ * The reference carries these functions and never calls them on its inference path; it has no framing of a recording for a
+ * VOICE at all.  The two framings offered, and what each one is:
+ *   MI355TTS_FRAMING_HIFIGAN (0)    the published HiFi-GAN training convention — not a line of the reference: the signal is
+ *       reflect-padded by 384 samples on each side (frame t reads 256 t - 384 + i; an index < 0 maps to -idx, one >= N to
+ *       2 (N - 1) - idx), periodic Hann window 0.5 - 0.5 cos(2 pi i / 1024).  N samples give N / 256 frames (floor) for
+ *       N >= 385, none below (one reflection would not be enough).  Frame t is centred on hop t: the "frame j <-> samples
+ *       [j hop, (j + 1) hop)" relation of the phoneme spans.
+ *   MI355TTS_FRAMING_REFERENCE (1)  the reference's own stft (audio.py:232-249: what transform() and its Griffin-Lim vocoder
+ *       use): no padding, frame t reads x[256 t : 256 t + 1024), symmetric np.hanning(1024).  ceil((N - 1024) / 256) frames for
+ *       N > 1024, none below.  (mi355tts_griffin_lim_infer on an F-frame mel comes back as F - 1 such frames.)
+ * Which of them — if either — equals what a given released voice was trained with is not known to this library: the choice
+ * is the caller's.  Both windows are computed in double precision and rounded once.
+ * mi355tts_load_analysis: mel_basis is the host array [num_mels][513]; mi355tts_unload frees the model.
+ * mi355tts_mel_from_audio: exactly one of wav_f32 / wav_i16 [B][wav_ld] (host, or device with MI355TTS_IN_DEVICE); int16 samples
+ * are converted as s * 2^-15 (exact) inside the same launch; row b holds samples[b] <= wav_ld samples (host array, each
+ * <= 2^30).  The mel's leading dimension is the longest row's frame count rounded up to 4, columns past a row's frames are zero
+ * in both planes, row b of a batch is bit-identical to its own batch-1 call, a batch whose rows all have 0 frames is a valid
+ * empty mel (max_frames 0), and the mel has no durations (like one from mi355tts_mel_from_buffer).  Inputs are expected in
+ * [-1, 1] (|X| <= 1024: nothing is rescaled before the square).
+ * MI355TTS_ERR_INVALID with the reason: null pointers, both or neither waveform, samples[b] outside [0, wav_ld], num_mels
+ * outside [1, 256], a negative or non-finite mag_eps, an unknown framing.
+ * Added in ABI version 2 (additive: the version number is unchanged). */
+#define MI355TTS_FRAMING_HIFIGAN 0
+#define MI355TTS_FRAMING_REFERENCE 1
+typedef struct {
+  int32_t num_mels; /* 1 .. 256 */
+  int32_t framing;  /* MI355TTS_FRAMING_* */
+  float mag_eps;    /* >= 0; 1e-9 in the HiFi-GAN convention, 0 in the reference's */
+} mi355tts_analysis_params;
+int mi355tts_load_analysis(mi355tts_ctx* ctx, const mi355tts_analysis_params* params, const float* mel_basis, int* model_out);
+int mi355tts_mel_from_audio(mi355tts_ctx* ctx, int model, const float* wav_f32, const int16_t* wav_i16, const int64_t* samples,
+                            int B, int64_t wav_ld, const mi355tts_audio_settings* audio, uint32_t flags, mi355tts_mel** out);
+/* The device planes of a mel (which: 0 = raw, 1 = vocoder input; [B][M][*ld] floats, valid until mi355tts_mel_free), so that a
+ * mel can feed mi355tts_glow_align with MI355TTS_IN_DEVICE without a host round trip. */
+int mi355tts_mel_plane(const mi355tts_mel* mel, int which, const float** device_ptr, int* ld);
+
 /* ---- fused call: replaces the model half of _sentence_task -------------------
  * (larynx/__init__.py:229-283: phonemes_to_mels -> mel transforms -> mels_to_audio -> pause
  * padding) with ONE call on one stream: arguments as in mi355tts_glow_infer +

@@ -1,6 +1,6 @@
 """Phoneme timings: from the frames every phoneme id occupies (`MelBatch.durations`, the reference's
 `attn.sum(-1)`, glow_tts/models.py:350-354) to sample positions in the delivered audio; `align_spans` does the same for a
-mel that already exists (forced alignment, `HipGlowTextToSpeech.align`)."""
+mel that already exists (forced alignment, `HipGlowTextToSpeech.align`), `align_audio_spans` for a recording."""
 from __future__ import annotations
 
 import numpy as np
@@ -27,3 +27,11 @@ def align_spans(tts_model, phoneme_ids, mels, hop: int, pad_before: int = 0, set
     """The `phoneme_spans` of an existing mel: `tts_model.align(phoneme_ids, mels, settings)` (the best monotonic path of the
     ids through the mel under the voice's own likelihood) -> int64 [P, 2] sample positions."""
     return phoneme_spans(tts_model.align(phoneme_ids, mels, settings), hop, pad_before)
+
+
+def align_audio_spans(tts_model, phoneme_ids, audio, hop: int = 256, pad_before: int = 0, settings=None,
+                      framing: str = "hifigan") -> np.ndarray:
+    """The `phoneme_spans` of a recording: `tts_model.align_audio(phoneme_ids, audio, settings, framing)` -> int64 [P, 2]
+    sample positions in `audio`.  Under the "hifigan" framing frame j is centred on samples [j * hop, (j + 1) * hop), the
+    relation `phoneme_spans` relies on; under "reference" frame j covers [j * hop, j * hop + 1024)."""
+    return phoneme_spans(tts_model.align_audio(phoneme_ids, audio, settings, framing), hop, pad_before)

@@ -19,6 +19,22 @@ static void gl_build_table(std::vector<float>& t) {
   }
 }
 
+// the context's copy of the table: built and uploaded by whichever load needs it first
+static int ensure_gl_table(mi355tts_ctx* ctx) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (ctx->gl_table) return 0;
+  std::vector<float> t;
+  gl_build_table(t);
+  float* d = nullptr;
+  if (hipMalloc(&d, t.size() * sizeof(float)) != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc Griffin-Lim table");
+  if (hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(d);
+    return fail(MI355TTS_ERR_HIP, "Griffin-Lim table upload failed");
+  }
+  ctx->gl_table = d;
+  return 0;
+}
+
 static int find_griffin(mi355tts_ctx* ctx, int model, std::shared_ptr<GriffinLimModel>* out) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   auto it = ctx->griffin.find(model);
@@ -34,20 +50,7 @@ extern "C" int mi355tts_load_griffin_lim(mi355tts_ctx* ctx, const mi355tts_griff
   if (params->iterations < 0 || params->iterations > 100000) return fail(MI355TTS_ERR_INVALID, "iterations %d outside [0, 100000]", params->iterations);
   if (!(params->mel_scaling > 0.f) || !std::isfinite(params->mel_scaling)) return fail(MI355TTS_ERR_INVALID, "mel_scaling must be positive");
   HIPCHECK(hipSetDevice(ctx->device));
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!ctx->gl_table) {
-      std::vector<float> t;
-      gl_build_table(t);
-      float* d = nullptr;
-      if (hipMalloc(&d, t.size() * sizeof(float)) != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc Griffin-Lim table");
-      if (hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(d);
-        return fail(MI355TTS_ERR_HIP, "Griffin-Lim table upload failed");
-      }
-      ctx->gl_table = d;
-    }
-  }
+  CHECK(ensure_gl_table(ctx));
   auto gm = std::make_shared<GriffinLimModel>();
   gm->p = *params;
   gm->device = ctx->device;

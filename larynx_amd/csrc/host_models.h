@@ -390,6 +390,20 @@ struct GriffinLimModel {
   }
 };
 
+// Mel analysis (mel_analysis.h) has no weights either: the filter bank, the non-zero band [first, one past last) of each of its
+// rows (made from the uploaded basis at load time, not from the mel scale) and the framing
+struct AnalysisModel {
+  mi355tts_analysis_params p;
+  int device = 0;
+  float* basis = nullptr;
+  int2* band = nullptr;
+  ~AnalysisModel() {
+    DeviceScope ds(device);
+    if (basis) hipFree(basis);
+    if (band) hipFree(band);
+  }
+};
+
 static std::vector<std::pair<std::string, int64_t>> glow_manifest(const mi355tts_glow_hparams& h) {
   std::vector<std::pair<std::string, int64_t>> m;
   auto add = [&](const std::string& n, int64_t e) { m.emplace_back(n, e); };

@@ -41,6 +41,7 @@
 #include "voc_out.h"
 #include "small_kernels.h"
 #include "griffin_lim.h"
+#include "mel_analysis.h"
 #include "align.h"
 #include "conv_f16.h"
 #include "pair_f16.h"
@@ -103,6 +104,7 @@ extern "C" void mi355tts_destroy(mi355tts_ctx* ctx) {
   }
   for (auto& pe : ctx->mel_pool) hipFree(pe.first);
   if (ctx->gl_table) hipFree(ctx->gl_table);
+  if (ctx->hann_periodic) hipFree(ctx->hann_periodic);
   delete ctx;  // the models free their device memory in their destructors
 }
 
@@ -210,16 +212,21 @@ extern "C" int mi355tts_unload(mi355tts_ctx* ctx, int model) {
   std::shared_ptr<GlowModel> g;
   std::shared_ptr<HifiModel> v;
   std::shared_ptr<GriffinLimModel> gl;
+  std::shared_ptr<AnalysisModel> an;
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
     auto gi = ctx->glow.find(model);
     auto li = ctx->griffin.find(model);
+    auto ai = ctx->analysis.find(model);
     if (gi != ctx->glow.end()) {
       g = std::move(gi->second);
       ctx->glow.erase(gi);
     } else if (li != ctx->griffin.end()) {
       gl = std::move(li->second);
       ctx->griffin.erase(li);
+    } else if (ai != ctx->analysis.end()) {
+      an = std::move(ai->second);
+      ctx->analysis.erase(ai);
     } else {
       auto vi = ctx->hifi.find(model);
       if (vi == ctx->hifi.end()) return fail(MI355TTS_ERR_NO_MODEL, "no model %d", model);
@@ -227,7 +234,7 @@ extern "C" int mi355tts_unload(mi355tts_ctx* ctx, int model) {
       ctx->hifi.erase(vi);
     }
   }
-  return 0;  // g / v / gl released outside the lock (hipFree synchronises the device)
+  return 0;  // g / v / gl / an released outside the lock (hipFree synchronises the device)
 }
 
 // §8(e): the one collective of the path.  The library does not link RCCL: the entry point is resolved from the
@@ -443,6 +450,7 @@ extern "C" int mi355tts_mel_from_buffer(mi355tts_ctx* ctx, const float* mel, con
 #include "host_join.h"
 #include "griffin_lim_forward.h"
 #include "align_forward.h"
+#include "analysis_forward.h"
 
 // ------------------------------------------------------------------ fused call + reservation
 // ids -> int16/f32 waveform in ONE call on ONE worker: GlowTTS and the vocoder are queued

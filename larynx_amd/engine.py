@@ -49,6 +49,13 @@ class MelBatch:
             ffi.check(lib, lib.mi355tts_mel_copy(self.handle, 0 if which == "raw" else 1, out.ctypes.data, self.max_frames))
         return out
 
+    def plane(self, which: str = "raw") -> typing.Tuple[int, int]:
+        """(device pointer, leading dimension) of a plane, [B][M][ld] float32 (`mi355tts_mel_plane`): valid until `free`."""
+        p, ld = C.c_void_p(), C.c_int()
+        lib = self._engine.lib
+        ffi.check(lib, lib.mi355tts_mel_plane(self.handle, 0 if which == "raw" else 1, C.byref(p), C.byref(ld)))
+        return int(p.value or 0), int(ld.value)
+
     @property
     def shape(self):
         return (self.batch, self.channels, self.max_frames)
@@ -260,7 +267,7 @@ class Engine:
     def glow_align(self, model: int, ids, mel, frames=None, speaker_ids: typing.Union[None, int, typing.Sequence[int]] = None,
                    want_latent: bool = False):
         """Forced alignment (`mi355tts_glow_align`): which frames of `mel` belong to which phoneme id.  `ids` as in
-        `glow_infer`; `mel`: a `MelBatch` (its raw plane and frame counts) or an array [B, M, F] / [M, F] in the GlowTTS output
+        `glow_infer`; `mel`: a `MelBatch` (its raw plane, read on the device, and its frame counts) or an array [B, M, F] / [M, F] in the GlowTTS output
         domain with `frames` valid columns per row (default: all).  Returns (durations int32 [B, P] — frames per id, zeros past
         a row's length, each row summing to its frame count cut down to a multiple of n_sqz —, scores float32 [B]) and, with
         `want_latent`, the latent z [B, M, F] as a third item.  Feed a row's durations to `glow_infer(durations=...)` to put
@@ -272,31 +279,38 @@ class Engine:
         packed = np.zeros((B, ld), np.int64)
         for b, r in enumerate(rows):
             packed[b, : len(r)] = r
-        if isinstance(mel, MelBatch):
+        flags = 0
+        if isinstance(mel, MelBatch):  # its raw plane where it lies: no host round trip
+            if mel.batch != B or mel.max_frames < 1:
+                raise ValueError("mel: one non-empty row per id sequence")
             if frames is None:
                 frames = mel.frames
-            mel = mel.numpy("raw")
-        mel = np.ascontiguousarray(mel, np.float32)
-        if mel.ndim == 2:
-            mel = mel[None]
-        if mel.ndim != 3 or mel.shape[0] != B or mel.shape[2] < 1:
-            raise ValueError("mel: [B, M, F] with one row per id sequence")
-        fr = np.full(B, mel.shape[2], np.int32) if frames is None else np.ascontiguousarray(np.asarray(frames, np.int32).reshape(-1))
+            mel_ptr, mel_ld = mel.plane("raw")
+            shape, z_frames = (B, mel.channels, mel_ld), mel.max_frames
+            flags = ffi.IN_DEVICE
+        else:
+            mel = np.ascontiguousarray(mel, np.float32)
+            if mel.ndim == 2:
+                mel = mel[None]
+            if mel.ndim != 3 or mel.shape[0] != B or mel.shape[2] < 1:
+                raise ValueError("mel: [B, M, F] with one row per id sequence")
+            mel_ptr, mel_ld, shape, z_frames = mel.ctypes.data, mel.shape[2], mel.shape, mel.shape[2]
+        fr = np.full(B, mel_ld, np.int32) if frames is None else np.ascontiguousarray(np.asarray(frames, np.int32).reshape(-1))
         if fr.shape != (B,):
             raise ValueError("frames: one count per row")
         spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
         dur = np.zeros((B, ld), np.int32)
         score = np.zeros(B, np.float32)
-        z = np.zeros_like(mel) if want_latent else None
+        z = np.zeros(shape, np.float32) if want_latent else None
         ffi.check(
             self.lib,
             self.lib.mi355tts_glow_align(
-                self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, ld, mel.ctypes.data,
-                fr.ctypes.data_as(C.POINTER(C.c_int32)), mel.shape[2], spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
-                0, dur.ctypes.data_as(C.POINTER(C.c_int32)), ld, score.ctypes.data_as(C.POINTER(C.c_float)), ffi.ptr(z),
+                self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, ld, mel_ptr,
+                fr.ctypes.data_as(C.POINTER(C.c_int32)), mel_ld, spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
+                flags, dur.ctypes.data_as(C.POINTER(C.c_int32)), ld, score.ctypes.data_as(C.POINTER(C.c_float)), ffi.ptr(z),
             ),
         )
-        return (dur, score, z) if want_latent else (dur, score)
+        return (dur, score, z[:, :, :z_frames]) if want_latent else (dur, score)
 
     def maximum_path(self, value: np.ndarray, id_lens=None, frames=None):
         """`mi355tts_op_maximum_path`: the reference's `maximum_path` (glow_tts/utils.py:59-96) on `value` [B, P, F] (or [P, F]),
@@ -566,6 +580,52 @@ class Engine:
         ffi.check(self.lib, self.lib.mi355tts_griffin_lim_infer(self._ctx, int(model), mel.handle, phase0_ptr,
                                                                 int(seed) & (2 ** 64 - 1), phase_out_ptr, f32_ptr, i16_ptr,
                                                                 int(wav_ld), int(iterations), int(flags)))
+
+    # ---- mel analysis ------------------------------------------------------------
+    def load_analysis(self, mel_basis: np.ndarray, framing: typing.Union[str, int] = "hifigan",
+                      mag_eps: typing.Optional[float] = None) -> int:
+        """`mi355tts_load_analysis`: waveform -> mel in one launch.  `mel_basis` is [num_mels, 513]
+        (`larynx_amd.audio.mel_basis`); `framing` "hifigan" (the published HiFi-GAN training convention: reflect padding,
+        periodic Hann) or "reference" (the reference's own `stft`: no padding, symmetric Hann); `mag_eps` goes under the
+        square root of the magnitudes (default: the framing's own, 1e-9 / 0).  `unload` frees it."""
+        basis = np.ascontiguousarray(mel_basis, np.float32)
+        if basis.ndim != 2 or basis.shape[1] != 513:
+            raise ValueError(f"mel_basis must be [num_mels, 513] (1024-point frames), got {basis.shape}")
+        fr = ffi.FRAMINGS[framing] if isinstance(framing, str) else int(framing)
+        if mag_eps is None:
+            mag_eps = 1e-9 if fr == ffi.FRAMING_HIFIGAN else 0.0
+        p = ffi.AnalysisParamsC(int(basis.shape[0]), fr, float(mag_eps))
+        model = C.c_int()
+        ffi.check(self.lib, self.lib.mi355tts_load_analysis(self._ctx, C.byref(p), basis.ctypes.data, C.byref(model)))
+        return int(model.value)
+
+    def mel_from_audio(self, model: int, audio: np.ndarray, samples=None, audio_settings=None) -> MelBatch:
+        """`audio`: float32 (in [-1, 1]) or int16, [N] or [B, N], row b valid for `samples[b]` entries (default: all) -> the
+        `MelBatch` of the recording: plane "vocoder" feeds `hifigan_infer` / `griffin_lim_infer`, plane "raw" is the
+        GlowTTS domain `glow_align` expects.  `audio_settings` as everywhere; None leaves ln(max(amp, 1e-5)) in both."""
+        audio = np.asarray(audio)
+        if audio.dtype != np.int16:
+            audio = audio.astype(np.float32, copy=False)
+        audio = np.ascontiguousarray(audio)
+        if audio.ndim == 1:
+            audio = audio[None]
+        if audio.ndim != 2:
+            raise ValueError("audio: [N] or [B, N]")
+        B, N = audio.shape
+        f32, i16 = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
+        return self.mel_from_audio_raw(model, f32, i16, np.full(B, N, np.int64) if samples is None else samples, N, audio_settings)
+
+    def mel_from_audio_raw(self, model: int, f32_ptr, i16_ptr, samples, wav_ld: int, audio_settings=None, flags: int = 0) -> MelBatch:
+        """Pointer-level entry: exactly one of the two pointers, [B][wav_ld] (device memory with flags=ffi.IN_DEVICE)."""
+        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
+        out = C.c_void_p()
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_mel_from_audio(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n),
+                                             int(wav_ld), C.byref(a) if a is not None else None, int(flags), C.byref(out)),
+        )
+        return MelBatch(self, out.value)
 
     # ---- single operators ------------------------------------------------------
     def conv1d(self, x, w, bias=None, dilation=1, in_slope=1.0, out_act=0, lens=None) -> np.ndarray:

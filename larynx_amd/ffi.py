@@ -76,6 +76,15 @@ class GriffinLimParamsC(C.Structure):
     _fields_ = [("num_mels", C.c_int32), ("mel_scaling", C.c_float), ("iterations", C.c_int32)]
 
 
+class AnalysisParamsC(C.Structure):
+    _fields_ = [("num_mels", C.c_int32), ("framing", C.c_int32), ("mag_eps", C.c_float)]
+
+
+FRAMING_HIFIGAN = 0  # MI355TTS_FRAMING_*: the published HiFi-GAN training convention / the reference's own stft
+FRAMING_REFERENCE = 1
+FRAMINGS = {"hifigan": FRAMING_HIFIGAN, "reference": FRAMING_REFERENCE}
+
+
 class ProsodyC(C.Structure):
     """`mi355tts_prosody`: host arrays [B][ld] (or NULL): a rate per id, durations in, durations out."""
 
@@ -149,6 +158,12 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
     "mi355tts_hifigan_infer_padded": (C.c_int, [_VP, C.c_int, _VP, C.c_float, _VP, _VP, C.c_int64, C.c_uint32, C.c_int32, C.c_int32]),
     "mi355tts_load_griffin_lim": (C.c_int, [_VP, C.POINTER(GriffinLimParamsC), _VP, C.POINTER(C.c_int)]),
     "mi355tts_griffin_lim_infer": (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_uint32]),
+    "mi355tts_load_analysis": (C.c_int, [_VP, C.POINTER(AnalysisParamsC), _VP, C.POINTER(C.c_int)]),
+    "mi355tts_mel_from_audio": (
+        C.c_int,
+        [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, C.POINTER(AudioSettingsC), C.c_uint32, C.POINTER(_VP)],
+    ),
+    "mi355tts_mel_plane": (C.c_int, [_VP, C.c_int, C.POINTER(_VP), C.POINTER(C.c_int)]),
     "mi355tts_synthesize": (
         C.c_int,
         [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,

@@ -72,6 +72,7 @@ class HipGlowTextToSpeech(TextToSpeechModel):
         # without an explicit `seed` setting each call takes the next value of a per-model
         # counter that starts at a random 63-bit number (thread-safe: itertools.count is atomic).
         self._seeds = itertools.count(int.from_bytes(os.urandom(8), "little") >> 1)
+        self._analyzers: typing.Dict[str, typing.Any] = {}  # one MelAnalyzer per framing (align_audio)
 
     # -- `get_tts_model` does setattr(model, "audio_settings", ...) and `text_to_speech`
     #    reads it back with getattr (larynx/__init__.py:117-120, 362-363)
@@ -134,6 +135,19 @@ class HipGlowTextToSpeech(TextToSpeechModel):
             raise ValueError("empty phoneme id sequence")
         dur, _ = self.engine.glow_align(self.model_id, ids, mels, speaker_ids=None if speaker_idx is None else int(speaker_idx))
         return dur[0]
+
+    def align_audio(self, phoneme_ids: np.ndarray, audio: np.ndarray, settings: typing.Optional[SettingsType] = None,
+                    framing: str = "hifigan") -> np.ndarray:
+        """`align` for a RECORDING: `audio` ([N] float32 in [-1, 1] or int16, at the voice's sample rate) goes through
+        `larynx_amd.analysis.MelAnalyzer` with this voice's audio settings (`framing`: see there) and its raw plane, still on
+        the device, into `align` -> int32 [P] frames per id."""
+        if self._audio_settings is None:
+            raise ValueError("this voice carries no audio settings: its mel domain is unknown")
+        if framing not in self._analyzers:
+            from .analysis import MelAnalyzer
+
+            self._analyzers[framing] = MelAnalyzer(self.engine, self._audio_settings, framing)
+        return self.align(phoneme_ids, self._analyzers[framing].audio_to_mels(np.asarray(audio).reshape(-1)), settings)
 
 
 def mels_as_numpy(mels: typing.Union[MelBatch, np.ndarray]) -> np.ndarray:
