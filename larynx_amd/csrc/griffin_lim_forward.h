@@ -86,17 +86,8 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
   CHECK(acquire_worker(ctx, &w));
   WorkerGuard guard{ctx, w};
   hipStream_t s = w->stream;
-  if (T == 0) {  // every row has fewer than 2 frames: empty signals
-    if (out_dev) {
-      if (wav_f32 && wav_ld) HIPCHECK(hipMemsetAsync(wav_f32, 0, sizeof(float) * (size_t)B * wav_ld, s));
-      if (wav_i16 && wav_ld) HIPCHECK(hipMemsetAsync(wav_i16, 0, sizeof(int16_t) * (size_t)B * wav_ld, s));
-      HIPCHECK(mi355_sync(s));
-    } else {
-      if (wav_f32) std::memset(wav_f32, 0, sizeof(float) * (size_t)B * wav_ld);
-      if (wav_i16) std::memset(wav_i16, 0, sizeof(int16_t) * (size_t)B * wav_ld);
-    }
-    return 0;
-  }
+  const OutRows rows = {nullptr, nullptr, 0, {wav_f32, wav_i16, wav_ld, 0, 0, (size_t)N}};
+  if (T == 0) return zero_outputs(rows, B, RowWriter{out_dev, s});  // every row has fewer than 2 frames: empty signals
   const size_t nph = (size_t)B * GL_BINS * T;
   const size_t Nld = (size_t)((N + 3) & ~3LL);
   Carver cv;
@@ -174,18 +165,7 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
     if (ph_b) HIPCHECK(hipMemcpyAsync(pp, dph_out, ph_b, hipMemcpyDeviceToHost, s));
     HIPCHECK(mi355_sync(s));
     HIPCHECK(hipGetLastError());
-    for (int b = 0; b < B; ++b) {
-      if (wav_f32) {
-        float* dst = wav_f32 + (size_t)b * wav_ld;
-        std::memcpy(dst, (const float*)pf + (size_t)b * Nld, sizeof(float) * (size_t)N);
-        std::memset(dst + N, 0, sizeof(float) * (size_t)(wav_ld - N));
-      }
-      if (wav_i16) {
-        int16_t* dst = wav_i16 + (size_t)b * wav_ld;
-        std::memcpy(dst, (const short*)pi + (size_t)b * Nld, sizeof(short) * (size_t)N);
-        std::memset(dst + N, 0, sizeof(int16_t) * (size_t)(wav_ld - N));
-      }
-    }
+    CHECK(scatter_rows(rows, B, WavRows{(float*)pf, Nld, (short*)pi, Nld}, RowWriter{false, s}));
     if (phase_out) std::memcpy(phase_out, pp, ph_b);
     return 0;
   }

@@ -1,6 +1,6 @@
 // mi355tts host runtime — the native fp16 vocoder (MI355TTS_PRECISION_F16): what the reference's `half` switch is, `.half()` on
 // the whole HiFi-GAN generator (larynx/hifi_gan.py:96-97; hifi_gan/models.py:91-98, 136-141, 186-202).  Weight packing at load,
-// the tile choice and the layer schedule over conv_f16.h's kernels.  Every layer of the generator runs in this mode: conv_pre,
+// the tile choice, the plans and the launches of conv_f16.h's kernels; the layer schedule is hifigan_body_f16 in hifigan_forward.h.  Every layer of the generator runs in this mode: conv_pre,
 // the upsamplers, every ResBlock conv of every stage (wide and narrow) and conv_post read and write fp16 planes; the
 // waveform leaves conv_post's tanh in f32 (the reference casts its half output to float there, larynx/hifi_gan.py:160-166).
 // (one translation unit: included once by mi355tts.hip, after host_launch.h)
@@ -254,209 +254,4 @@ static HPlan plan_f16(const HConvW& c, HConvArgs a, int epi, int B, int n_max, d
   p.grid = dim3(p.gx, p.gy, B);
   p.flop = flop;
   return p;
-}
-
-// ------------------------------------------------------------------ the generator, conv_pre .. conv_post + tanh
-// planes: `buf[i]` are the worker's plane buffers (hifi_layout: B x `plane` floats each, 2 + 4 nk of them) — an fp16 plane of the
-// same channels and row stride takes half of one.  Leaves the f32 waveform rows in `wav` ([B][Nld]) and, when asked, the
-// |max| of every 256-sample tile in `peak` (voc_out.h's wave_out_kernel reads both).
-static int hifigan_body_f16(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355tts_mel* mel, float* const* buf, float* wav, size_t Nld,
-                            float* peak, long long peak_ld, int voc_host_len, hipStream_t s) {
-  const mi355tts_hifigan_hparams& h = hm->hp;
-  const int B = mel->B, F = mel->max_frames;
-  const int C0 = h.upsample_initial_channel, nk = h.num_kernels, nd = h.num_dilations;
-  const int* d_frames = mel->frames_dev;
-  auto plane = [&](int i) { return reinterpret_cast<uint4*>(buf[i]); };
-
-  // mel [B][M][ld] f32 -> octet planes (buf[1]: free until the first upsampler writes it)
-  const int M = mel->M, moct = (M + 7) / 8;
-  uint4* melh = plane(1);
-  {
-    ProfScope ps(ctx, w, KC_SMALL, 0, s);
-    kn_hit(ctx, KN_PACK_OCTETS);
-    hipLaunchKernelGGL(pack_octets_kernel, dim3((F + 255) / 256, moct, B), dim3(256), 0, s, mel->voc, (long long)mel->M * mel->ld, mel->ld, M, d_frames, 1,
-                       melh, (long long)moct * F, F);
-  }
-  uint4* cur[3] = {plane(0), nullptr, nullptr};
-  int ncur = 1;
-  float cur_div = 1.0f;
-  {  // conv_pre (models.py:187)
-    HConvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.x = melh;
-    a.x_bs = (long long)moct * F;
-    a.x_ld = F;
-    a.in_div = 1.0f;
-    a.dil = 1;
-    a.pad = 3;
-    a.in_slope = 1.0f;
-    a.out_slope = 1.0f;
-    a.y = cur[0];
-    a.y_bs = (long long)(C0 / 8) * F;
-    a.y_ld = F;
-    a.cout = C0;
-    h_set_lengths(a, B, d_frames, voc_host_len, 1, 1);
-    const HPlan p = plan_f16(hm->h_pre, a, EPI_LINEAR, B, F, 2.0 * C0 * M * 7 * (double)F * B);
-    CHECK(run_plan_f16(ctx, w, p, KC_VOC_IO, s));
-  }
-  uint4* xu = plane(1);
-  int mul = 1, Lin = F, ldin = F, ch = C0, flip = 0;
-  for (int i = 0; i < h.num_upsamples; ++i) {
-    const int u = h.upsample_rates[i];
-    const int cout = C0 >> (i + 1);
-    const int Lout = Lin * u, ldo = Lout;
-    {  // x = ups[i](leaky_relu(x, 0.1))  (models.py:189-190); the MRF average of the previous stage is taken on load
-      HConvArgs a;
-      std::memset(&a, 0, sizeof(a));
-      a.x = cur[0];
-      a.x2 = ncur > 1 ? cur[1] : nullptr;
-      a.x3 = ncur > 2 ? cur[2] : nullptr;
-      a.in_div = cur_div;
-      a.x_bs = (long long)(ch / 8) * ldin;
-      a.x_ld = ldin;
-      a.dil = 1;
-      a.pad = 1;
-      a.in_slope = 0.1f;
-      a.out_slope = 1.0f;
-      a.y = xu;
-      a.y_bs = (long long)(cout / 8) * ldo;
-      a.y_ld = ldo;
-      a.up = u;
-      a.up_pad = u / 2;
-      a.cout = cout;
-      h_set_lengths(a, B, d_frames, voc_host_len, mul, mul * u);
-      HPlan p = plan_f16(hm->h_ups[i], a, EPI_UPSAMPLE, B, Lin + 1, 2.0 * ch * cout * (2.0 * u) * (double)Lin * B);
-      p.mrf = ncur > 1;
-      CHECK(run_plan_f16(ctx, w, p, KC_UPSAMPLE, s));
-    }
-    mul *= u;
-    ch = cout;
-    const long long bs = (long long)(ch / 8) * ldo;
-    // per-chain planes: buf[2 + 4 j ..] = {t, ping, out (flip 0), out (flip 1)}; last stage's outputs are dead once the upsampler has read them
-    uint4 *tb[3], *pa[3], *pb[3], *dst_last[3];
-    const uint4* rin[3];
-    for (int j = 0; j < nk; ++j) {
-      tb[j] = plane(2 + 4 * j);
-      pa[j] = plane(2 + 4 * j + 1);
-      pb[j] = plane(2 + 4 * j + 2 + (flip ^ 1));
-      dst_last[j] = plane(2 + 4 * j + 2 + flip);
-      rin[j] = xu;
-    }
-    auto conv_args = [&](const uint4* x, uint4* y, const uint4* res, int K, int dil, float in_slope, float out_slope) {
-      HConvArgs a;
-      std::memset(&a, 0, sizeof(a));
-      a.x = x;
-      a.in_div = 1.0f;
-      a.x_bs = bs;
-      a.x_ld = ldo;
-      a.dil = dil;
-      a.pad = (K * dil - dil) / 2;
-      a.in_slope = in_slope;
-      a.out_slope = out_slope;
-      a.y = y;
-      a.y_bs = bs;
-      a.y_ld = ldo;
-      a.res = res;
-      a.cout = ch;
-      h_set_lengths(a, B, d_frames, voc_host_len, mul, mul);
-      return a;
-    };
-    // in this mode "mrf_group" and "rb_pair" select the grouped / fused launches (as the call saw them at its start)
-    const bool use_group = w->opt.mrf_group, use_pair = h.resblock_type == 1 && use_group && w->opt.rb_pair;
-    for (int d = 0; d < nd; ++d) {
-      HPlan c1[3], c2[3];
-      HPairPlan pp[3];
-      uint4* dst[3];
-      for (int j = 0; j < nk; ++j) {
-        const HResConv& rc = hm->h_rb[i][j][d];
-        const int K = h.resblock_kernel_sizes[j], dil = h.resblock_dilations[j][d];
-        const double flop = 2.0 * ch * ch * K * (double)Lout * B;
-        dst[j] = d == nd - 1 ? dst_last[j] : ((d & 1) ? pb[j] : pa[j]);
-        if (h.resblock_type == 1) {
-          // ResBlock1.forward (models.py:91-98): xt = c2(lrelu(c1(lrelu(x)))); x = xt + x.  conv1 stores lrelu(c1(.)) — its only
-          // consumer is conv2, which would apply it on load
-          c1[j] = plan_f16(rc.c1, conv_args(rin[j], tb[j], nullptr, K, dil, 0.1f, 0.1f), EPI_LINEAR, B, Lout, flop);
-          c2[j] = plan_f16(rc.c2, conv_args(tb[j], dst[j], rin[j], K, 1, 1.0f, 1.0f), EPI_LINEAR, B, Lout, flop);
-          HPairArgs& a = pp[j].a;
-          std::memset(&a, 0, sizeof(a));
-          a.x = rin[j];
-          a.y = dst[j];
-          a.bs = bs;
-          a.ld = ldo;
-          if (voc_host_len >= 0) {
-            a.len = nullptr;
-            a.len_const = voc_host_len * mul;
-          } else {
-            a.len = d_frames;
-          }
-          a.len_mul = mul;
-          a.w1 = rc.c1.w;
-          a.b1 = rc.c1.bias;
-          a.nslab1 = rc.c1.nslab;
-          a.w2 = rc.c2.w;
-          a.b2 = rc.c2.bias;
-          a.nslab2 = rc.c2.nslab;
-          a.C = ch;
-          a.dil = dil;
-          a.slope = 0.1f;
-          pp[j].K = K;
-          pp[j].flop = 2.0 * flop;
-        } else {
-          // ResBlock2.forward (models.py:136-141): x = c(lrelu(x)) + x
-          c1[j] = plan_f16(rc.c1, conv_args(rin[j], dst[j], rin[j], K, dil, 0.1f, 1.0f), EPI_LINEAR, B, Lout, flop);
-        }
-      }
-      int fused = 1;
-      if (use_pair) {
-        fused = run_pair_group_f16(ctx, w, pp, nk, ch, B, Lout, s);
-        if (fused < 0) return fused;
-      }
-      for (int pass = 0; fused != 0 && pass < (h.resblock_type == 1 ? 2 : 1); ++pass) {
-        const HPlan* pl = pass ? c2 : c1;
-        int rc = use_group ? run_group_f16(ctx, w, pl, nk, B, s) : 1;
-        if (rc < 0) return rc;
-        if (rc == 1)
-          for (int j = 0; j < nk; ++j) CHECK(run_plan_f16(ctx, w, pl[j], KC_RESBLOCK, s));
-      }
-      for (int j = 0; j < nk; ++j) rin[j] = dst[j];
-    }
-    for (int j = 0; j < nk; ++j) cur[j] = dst_last[j];
-    ncur = nk;
-    cur_div = (float)nk;
-    flip ^= 1;
-    Lin = Lout;
-    ldin = ldo;
-  }
-  {  // x = tanh(conv_post(leaky_relu(x)))  — default slope 0.01 (models.py:198-201)
-    HPostArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.x = cur[0];
-    a.x2 = ncur > 1 ? cur[1] : nullptr;
-    a.x3 = ncur > 2 ? cur[2] : nullptr;
-    a.in_div = cur_div;
-    a.slope = 0.01f;
-    a.x_bs = (long long)(ch / 8) * ldin;
-    a.x_ld = ldin;
-    if (voc_host_len >= 0) {
-      a.len = nullptr;
-      a.len_const = voc_host_len * mul;
-    } else {
-      a.len = d_frames;
-    }
-    a.len_mul = mul;
-    a.w = hm->arena + hm->post_w_off;
-    a.bias = hm->arena + hm->post_b_off;
-    a.C = ch;
-    a.y = wav;
-    a.y_bs = (long long)Nld;
-    a.peak = peak;
-    a.peak_ld = peak_ld;
-    ProfScope ps(ctx, w, KC_VOC_IO, 2.0 * (double)ch * 7 * (double)Lin * B, s);
-    kn_hit(ctx, KN_POST_F16);
-    const dim3 pg((Lin + HPOST_TW - 1) / HPOST_TW, B);
-    if (ncur > 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(post_f16_kernel<7, 3>), pg, dim3(256), 0, s, a);
-    else if (ncur > 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(post_f16_kernel<7, 2>), pg, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(post_f16_kernel<7, 1>), pg, dim3(256), 0, s, a);
-  }
-  return 0;
 }

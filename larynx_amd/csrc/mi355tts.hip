@@ -637,7 +637,7 @@ extern "C" int mi355tts_reserve(mi355tts_ctx* ctx, int workers, int glow, int vo
   if (hm) {
     const bool dn = denoiser != 0 && (long long)max_frames * hm->hop > DN_FFT;
     // both vocoder schedules (forked MRF chains / one stream) carve the same planes unless serial_branches is set
-    const HifiLayout a = hifi_layout(hm->hp, hm->hop, max_batch, max_frames, dn, true && hm->hp.num_kernels >= 2 && hm->hp.num_kernels <= 3, max_pad_samples);
+    const HifiLayout a = hifi_layout(hm->hp, hm->hop, max_batch, max_frames, dn, hifi_split_out(false, hm->hp), max_pad_samples);
     const HifiLayout b = hifi_layout(hm->hp, hm->hop, max_batch, max_frames, dn, false, max_pad_samples);
     need = std::max(need, std::max(a.total, b.total));
     M = std::max(M, (int)hm->hp.num_mels);

@@ -89,8 +89,53 @@ def check_output_tail_forms(eng, g, v, num_symbols, hop, lens=(13, 7, 21), devic
         mel.free()
 
 
+def _host_buffer(shape, dtype):
+    a = np.full(shape, 7, dtype)
+    return a.ctypes.data, lambda: a
+
+
+# kernels only the vocoder launches (a fused call's GlowTTS half shares conv_mfma_kernel with conv_pre)
+VOCODER_ONLY_KERNELS = ("post_conv_kernel", "wave_out_kernel", "post_f16_kernel", "pack_octets_kernel", "mrf_small_kernel",
+                        "resblock_pair_kernel", "pair_group_kernel", "rb_conv_kernel", "rb_group_kernel", "conv_group_kernel")
+
+
+def check_empty_vocoder_call(eng, g, v, num_symbols, num_mels, device_buffer=_host_buffer):
+    """A vocoder call whose rows all have 0 frames launches nothing and zeroes every element of every output row, the
+    pauses and the tail up to `wav_ld` included: B = 1 and B = 3, host and MI355TTS_OUT_DEVICE destinations, float and int16
+    rows together and each alone, buffers pre-filled with 7.  `device_buffer(shape, dtype)` gives (pointer, fetch) of a
+    device buffer filled with 7 (the emulator's device memory is the host's).  The fused call: all-zero `durations` give
+    0 frames on a voice with n_sqz = 2, which the tiny and the full-size voices are."""
+    pad_before, pad_after, wav_ld = 3, 6, 16
+    for B in (1, 3):
+        mel = eng.mel_from_numpy(np.zeros((B, num_mels, 4), np.float32), frames=np.zeros(B, np.int32))
+        assert mel.max_frames == 0 and not np.any(mel.frames)
+        for flags, buffer in ((0, _host_buffer), (ffi.OUT_DEVICE, device_buffer)):
+            for want_f, want_i in ((True, True), (True, False), (False, True)):
+                pf, get_f = buffer((B, wav_ld), np.float32) if want_f else (None, None)
+                pi, get_i = buffer((B, wav_ld), np.int16) if want_i else (None, None)
+                eng.profile_reset()
+                eng.hifigan_infer_raw(v, mel, pf, pi, wav_ld, flags=flags, pad_before=pad_before, pad_after=pad_after)
+                assert not any(eng.kernel_counts().values())
+                for get in (get_f, get_i):
+                    if get is not None:
+                        out = get()
+                        assert out.shape == (B, wav_ld) and np.all(out == 0)
+        mel.free()
+    ids = synthetic.synthetic_phoneme_ids(np.random.default_rng(47), 6, num_symbols)
+    eng.profile_reset()
+    frames, f32, i16 = eng.synthesize(g, v, ids, seed=2, durations=np.zeros(6, np.int32), pad_before=pad_before, pad_after=pad_after,
+                                      want_float=True)
+    names = eng.kernel_counts()
+    assert int(frames[0]) == 0 and not any(names[k] for k in VOCODER_ONLY_KERNELS)
+    assert f32.shape == i16.shape == (1, pad_before + pad_after) and np.all(f32 == 0) and np.all(i16 == 0)
+
+
 def test_output_tail_forms(emu_engine, tiny):
     check_output_tail_forms(emu_engine, tiny["g"], tiny["v"], HP.TINY_GLOW.num_symbols, HP.TINY_HIFIGAN.hop)
+
+
+def test_empty_vocoder_call(emu_engine, tiny):
+    check_empty_vocoder_call(emu_engine, tiny["g"], tiny["v"], HP.TINY_GLOW.num_symbols, HP.TINY_HIFIGAN.num_mels)
 
 
 def test_synthesize_equals_two_calls(emu_engine, tiny):

@@ -213,10 +213,19 @@ def test_device_noise_is_standard_normal(gpu_engine):
 def test_host_feature_checks_on_the_device(gpu_engine):
     """The emulator suite's host-runtime checks (fused call, pause padding, schedule
     invariance under load) on the real build at full model sizes."""
-    from tests.test_emu_host_features import check_schedule_invariance, check_synthesize_equals_two_calls
+    import torch
+
+    from tests.test_emu_host_features import check_empty_vocoder_call, check_schedule_invariance, check_synthesize_equals_two_calls
 
     (gsd, g), (vsd, v) = models(gpu_engine, HP.LJSPEECH, HP.HIFIGAN_MEDIUM)
     check_synthesize_equals_two_calls(gpu_engine, g, v, HP.LJSPEECH.num_symbols, HP.HIFIGAN_MEDIUM.hop, lens=(40, 17, 63))
+
+    def torch_buffer(shape, dtype):
+        t = torch.full(shape, 7, dtype=torch.float32 if dtype == np.float32 else torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        return t.data_ptr(), lambda: t.cpu().numpy()
+
+    check_empty_vocoder_call(gpu_engine, g, v, HP.LJSPEECH.num_symbols, HP.HIFIGAN_MEDIUM.num_mels, device_buffer=torch_buffer)
     _, (_, vh) = models(gpu_engine, HP.LJSPEECH, HP.HIFIGAN_HIGH)
     check_schedule_invariance(gpu_engine, vh, 80, frames=150, threads=6)
     from larynx_amd import ffi
