@@ -353,8 +353,8 @@ static void launch_attention(const GlowPass& p, const GlowLayer& L, const GlowEn
   const int H = h.hidden_channels, nh = h.n_heads, P = p.ld, Pmax = p.n_max;
   const long long bsH = (long long)H * P;
   ProfScope ps = p.small();
-  kn_hit(p.ctx, KN_ATTENTION);
   if (Pmax > ATTM_MAXP) {
+    kn_hit(p.ctx, KN_ATTENTION_VALU);
     hipLaunchKernelGGL(attention_kernel, dim3(att_rows / ATT_ROWS, nh, p.B), dim3(256), 0, p.s, v.qkv, 3 * bsH, P, p.d_len, H, nh,
                        h.window_size, p.A + L.ek, p.A + L.ev, v.t2, bsH, P, v.sc, P);
     return;
@@ -363,6 +363,7 @@ static void launch_attention(const GlowPass& p, const GlowLayer& L, const GlowEn
   const int dkh = H / nh;
   const int nk = dkh <= 32 ? 16 : dkh <= 64 ? 32 : dkh <= 96 ? 48 : 64;
   const bool small_lds = Pmax <= 256 && !p.w->opt.env.att_big_lds;  // (A/B runs)
+  kn_hit(p.ctx, small_lds ? KN_ATTENTION : KN_ATTENTION_P768);
   auto launch = [&](auto k, auto exact, auto pm) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(attention_mfma_kernel<decltype(k)::value, decltype(exact)::value != 0, decltype(pm)::value>), ag,
                        dim3(512), 0, p.s, v.qkv, 3 * bsH, P, p.d_len, H, nh, h.window_size, p.A + L.ek, p.A + L.ev, v.t2, bsH, P);

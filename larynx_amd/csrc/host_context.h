@@ -24,7 +24,7 @@ enum KName {
   KN_RB_PAIR_GROUP, KN_CONV_BF16, KN_CONV_BF16_GROUP, KN_PAIR_BF16, KN_PAIR_BF16_GROUP, KN_MRF_SMALL, KN_MRF8, KN_GATE16, KN_GATE16_WIDE, KN_LIN16,
   KN_LIN16_LN, KN_LIN16_WIDE, KN_GLOW_TAIL, KN_OPROJ_LN, KN_POST_CONV, KN_WAVE_OUT, KN_ATTENTION, KN_CONV_F16, KN_CONV_F16_GROUP, KN_POST_F16,
   KN_PACK_OCTETS, KN_PAIR_F16_GROUP, KN_WN_F16, KN_RB_GROUP_NB4, KN_GL_MAG, KN_GL_INIT, KN_GL_ITER, KN_GL_OUT, KN_GL_INT16, KN_GLOW_FWD, KN_ALIGN_SCORE,
-  KN_ALIGN_PATH, KN_MEL_ANALYSIS, KN_COUNT
+  KN_ALIGN_PATH, KN_MEL_ANALYSIS, KN_ATTENTION_P768, KN_ATTENTION_VALU, KN_COUNT
 };
 static const char* kname_name[KN_COUNT] = {
     "conv_mfma_kernel", "conv_mfma_kernel.m128", "conv_group_kernel", "rb_conv_kernel", "rb_group_kernel", "rb_group_kernel.snake",
@@ -33,7 +33,9 @@ static const char* kname_name[KN_COUNT] = {
     "glow_tail_kernel", "oproj_ln_kernel", "post_conv_kernel", "wave_out_kernel", "attention_mfma_kernel", "conv_f16_kernel", "conv_f16_group_kernel",
     "post_f16_kernel", "pack_octets_kernel", "pair_f16_group_kernel", "wn_f16_kernel", "rb_group_kernel.nb4",
     "griffin_lim_mag_kernel", "griffin_lim_init_kernel", "griffin_lim_iter_kernel", "griffin_lim_out_kernel", "griffin_lim_int16_kernel",
-    "glow_fwd_kernel", "align_score_kernel", "align_path_kernel", "mel_analysis_kernel"};
+    "glow_fwd_kernel", "align_score_kernel", "align_path_kernel", "mel_analysis_kernel",
+    // launch_attention's other two branches ("attention_mfma_kernel" is the 256-id LDS layout): the ATTM_MAXP layout, the VALU kernel
+    "attention_mfma_kernel.p768", "attention_kernel"};
 // the launch helpers without a context argument (launch_conv_k, launch_group_k) count through this: set by run_plan / run_group
 static thread_local std::atomic<long long>* g_kn = nullptr;
 // the kernel name (and launch sub-key: output rows / channels) of the launch inside the running ProfScope: the scope's

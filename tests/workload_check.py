@@ -5,7 +5,9 @@ micro-batched shard, mels and waveforms at the lengths where the vocoder's tile 
 Which kernels a vocoder call gets depends on the frame count, the batch and the load (csrc/host_launch.h: plan_conv,
 promote_group_plans, plan_pair, run_group), so the lengths compared here are chosen from the launch-rule transitions the
 library itself shows (`kernel_signature`) and from where a stage's last tile is full, one column or narrower than the halo
-(`edge_frames`)."""
+(`edge_frames`).  The acoustic model has the same kind of rules along the id count, the frame count, the batch and the precision
+(csrc/glow_forward.h: launch_attention; host_launch.h: run_gate16, run_lin16): "the GlowTTS sweep" below, shared by
+tests/test_gpu_glow_sweep.py and tests/test_emu_glow_sweep.py."""
 import threading
 import time
 
@@ -152,15 +154,24 @@ def vocoder_tiles(hp, precision="f32"):
     return sorted(set(out), key=lambda t: (t[1], t[2], t[0]))
 
 
-def edge_frames(hp, tiles, lo, hi):
-    """{F: [(label, stage, width, kind)]} for every F in [lo, hi] at which some stage's (length F * prod(u[:stage + 1])) last
-    tile of some width in `tiles` (vocoder_tiles) is exactly full ("full"), one column wide ("one") or narrower than that
-    kernel's halo ("halo")."""
+def vocoder_axis(hp):
+    """The axis length function of the vocoder's tiles: stage i runs on F * prod(upsample_rates[: i + 1]) columns."""
+    return lambda F, stage: F * int(np.prod(hp.upsample_rates[: stage + 1]))
+
+
+def edge_frames(hp, tiles, lo, hi, length=None):
+    """{F: [(label, stage, width, kind)]} for every F in [lo, hi] at which the last tile of some entry of `tiles` (vocoder_tiles,
+    glow_tiles) is exactly full ("full"), one column wide ("one") or narrower than that kernel's halo ("halo").
+    `length(F, stage)`: the columns the entry's kernel runs on at the scanned length F (default: the vocoder's stage length);
+    None = the kernel does not run at this F."""
+    length = length or vocoder_axis(hp)
     out = {}
     for F in range(max(1, lo), hi + 1):
         hits = []
         for label, stage, width, halo in tiles:
-            L = F * int(np.prod(hp.upsample_rates[: stage + 1]))
+            L = length(F, stage)
+            if L is None:
+                continue
             r = L % width
             kind = "full" if r == 0 else "one" if r == 1 else "halo" if r < halo else None
             if kind:
@@ -170,10 +181,13 @@ def edge_frames(hp, tiles, lo, hi):
     return out
 
 
-def cover_edges(edges, cap=None):
+def cover_edges(edges, cap=None, have=()):
     """A small set of frame counts that together hit every (stage, width, kind) edge in `edges` (edge_frames): greedy, the F
-    that hits the most edges not yet hit, the shorter F on a tie (the oracle's cost grows with F)."""
+    that hits the most edges not yet hit, the shorter F on a tie (the oracle's cost grows with F).  `have`: lengths compared
+    anyway: the edges they hit need no other length.  At most `cap` lengths."""
     left = {(s, w, k) for hits in edges.values() for (_, s, w, k) in hits}
+    for F in have:
+        left -= {(s, w, k) for (_, s, w, k) in edges.get(F, ())}
     chosen = []
     while left and (cap is None or len(chosen) < cap):
         F = max(edges, key=lambda f: (len(left & {(s, w, k) for (_, s, w, k) in edges[f]}), -f))
@@ -275,6 +289,330 @@ def check_lengths(eng, v, vsd, vhp, Fs, oracle, key, bounds=F32_SWEEP, label="",
         d = float(np.sqrt(np.mean((wav[b, :n].astype(np.float64) - solo[F][:n]) ** 2)))
         assert d <= solo_rms, (label, F, d)
     return ran
+
+
+# ---- the GlowTTS sweep --------------------------------------------------------------------------------------------------
+# Which kernels a GlowTTS call gets depends on the id count P, the frame count, the batch and the precision (csrc/glow_forward.h:
+# launch_attention; csrc/host_launch.h: run_gate16, run_lin16, plan_conv).  The column widths of its tiles, one entry per kernel
+# family: (label, precision ("any" = both), axis, width, per-side halo as a function of the hparams, (lo, hi) = the axis lengths
+# of a lone call at which the kernel runs, None = no bound).  Axes: "P" = phoneme ids (the encoder), "F2" = F / n_sqz (the
+# decoder's columns), "F" = mel frames.
+GLOW_TILE_WIDTHS = (
+    # small_kernels.h attention_mfma_kernel: i0 = blockIdx.x * 32 query rows, nkb = (P + 31) / 32 key blocks; the relative-position
+    # band reaches window_size keys across a seam.  glow_forward.h launch_attention: P <= ATTM_MAXP = 768
+    ("attention_mfma 32 rows / 32 keys", "any", "P", 32, lambda hp: hp.window_size, (1, 768)),
+    # small_kernels.h attention_mfma_kernel v_fetch / v_park: V staged in chunks of 64 keys
+    ("attention_mfma V chunk", "any", "P", 64, lambda hp: 0, (1, 768)),
+    # small_kernels.h ATT_ROWS = 4 query rows per workgroup, ATT_JCH = 64 keys per staged V chunk (attention_kernel, P > ATTM_MAXP)
+    ("attention ATT_ROWS", "any", "P", 4, lambda hp: 0, (769, None)),
+    ("attention ATT_JCH", "any", "P", 64, lambda hp: 0, (769, None)),
+    # host_launch.h run_lin16: TC = 16 * nblk, nblk = 2 below 16 channel groups (Cin 192 / 256: prenet k = 5, FFN conv_1, duration
+    # predictor k = 3, the 1 x 1 convs), 1 from 16 groups (the Cin = 768 FFN conv_2)
+    ("lin16 TC=32", "any", "P", 32, lambda hp: max(hp.prenet_kernel_size, hp.kernel_size) // 2, None),
+    ("lin16 TC=16", "any", "P", 16, lambda hp: hp.kernel_size // 2, None),
+    # coltile.h COL_T = 16 (oproj_ln_kernel)
+    ("oproj_ln COL_T", "any", "P", 16, lambda hp: 0, None),
+    # glow_forward.h launch_layernorm: layernorm16_kernel's grid (n_max + 15) / 16
+    ("layernorm16", "any", "P", 16, lambda hp: 0, None),
+    # glow_forward.h glow_encoder: embed_kernel's grid (Pmax + 63) / 64
+    ("embed", "any", "P", 64, lambda hp: 0, None),
+    # gate16.h gate16_kernel: 32 columns per workgroup (host_launch.h run_gate16: gx = (n_max + 31) / 32), halo of the k = 5 conv
+    ("gate16 32 columns", "f32", "F2", 32, lambda hp: (hp.kernel_size_dec - 1) // 2, None),
+    # host_launch.h run_lin16 on the res_skip 1 x 1 convs: TC = 32
+    ("lin16 TC=32", "any", "F2", 32, lambda hp: 0, None),
+    # coltile.h COL_T = 16 (glow_tail_kernel)
+    ("glow_tail COL_T", "any", "F2", 16, lambda hp: 0, None),
+    # wn_f16.h WN_W = 64 columns computed per workgroup, glow_forward.h run_wn_f16: margin = (kernel_size_dec - 1) / 2 * n_block_layers
+    # per side recomputed, WN_W - 2 * margin written (48 columns, halo 8 at the released shape)
+    ("wn_f16 WN_W - 2 margin", "f16", "F2", lambda hp: 64 - (hp.kernel_size_dec - 1) * hp.n_block_layers,
+     lambda hp: (hp.kernel_size_dec - 1) // 2 * hp.n_block_layers, None),
+    # glow_forward.h glow_decoder: expand_noise_squeeze_kernel's grid (Fmax + 255) / 256, mel_finalize_kernel's (Fld + 255) / 256
+    ("expand_noise_squeeze / mel_finalize", "any", "F", 256, lambda hp: 0, None),
+) + tuple(
+    # conv_mfma.h T_T = WN * NB * 32 of plan_conv's shapes (TILE_TINY 32, TILE_SMALL / TILE_M128 64, TILE_W128 128, TILE_NB2 256):
+    # the generic tile of whatever the 16-row kernels do not take, on both axes
+    (f"conv_mfma T_T={w}", "any", axis, w, (lambda hp: max(hp.prenet_kernel_size, hp.kernel_size) // 2) if axis == "P" else
+     (lambda hp: (hp.kernel_size_dec - 1) // 2), None)
+    for axis in ("P", "F2") for w in (32, 64, 128, 256)
+)
+
+
+def glow_tiles(hp, precision="f32"):
+    """The (label, stage, width, halo) tiles of the GlowTTS kernels in `precision`, for edge_frames / cover_edges.  stage =
+    (axis, lo, hi): the axis the tile runs along and the lengths at which its kernel runs (glow_axis reads it)."""
+    out = []
+    for label, prec, axis, width, halo, span in GLOW_TILE_WIDTHS:
+        if prec not in ("any", precision):
+            continue
+        lo, hi = span or (None, None)
+        out.append((label, (axis, lo, hi), width(hp) if callable(width) else width, halo(hp)))
+    return sorted(set(out), key=lambda t: (t[1][0], t[2], t[0], str(t[1])))
+
+
+def glow_axis(hp, scanned):
+    """The axis length function of a GlowTTS scan along `scanned`: "P" (P ids of 2 frames each: only the encoder's tiles count;
+    the decoder has the F2 scan) or "F2" (F = n_sqz * F2)."""
+    def length(n, stage):
+        axis, lo, hi = stage
+        L = {"P": {"P": n}, "F2": {"F2": n, "F": n * hp.n_sqz}}[scanned].get(axis)
+        if L is None or (lo is not None and L < lo) or (hi is not None and L > hi):
+            return None
+        return L
+    return length
+
+
+def glow_ids(hp, P, gsd=None, length_scale=1.0, tries=3):
+    """Ids seeded by P (seed 1000 + P); with `gsd`, the first of at most `tries` seeds whose oracle durations at `length_scale`
+    clear CEIL_MARGIN (chosen on the CPU from the oracle, never from the device)."""
+    from larynx_amd import synthetic
+
+    for t in range(tries):
+        ids = synthetic.synthetic_phoneme_ids(np.random.default_rng(1000 + P + t), P, hp.num_symbols)
+        if gsd is None or oracle_frames(gsd, hp, ids, length_scale)[1] >= CEIL_MARGIN:
+            return ids
+    raise AssertionError(f"no ids of length {P} clear the ceil margin in {tries} seeds")
+
+
+def glow_noise(hp, F, key):
+    """The standard-normal noise a sweep call injects, seeded by the compared length; 5 columns wider than the mel: its row stride
+    is not the mel's."""
+    return np.random.default_rng(2000 + key).standard_normal((hp.mel_channels, F + 5)).astype(F32)
+
+
+def forced_durations(hp, F2, P=8, odd_sum=False):
+    """P forced durations summing to n_sqz * F2 (+ 1 with `odd_sum`: the frame count is truncated to a multiple of n_sqz), split
+    unevenly, at least one of them odd wherever the sum allows it."""
+    total = hp.n_sqz * F2
+    w = np.array([1, 3, 2, 5, 1, 4, 2, 6][:P] + [1] * max(0, P - 8), np.int64)
+    d = total * w // int(w.sum())
+    d[3 % P] += total - int(d.sum())
+    if not np.any(d % 2) and P >= 2:
+        i = int(np.argmax(d))
+        d[i] -= 1
+        d[(i + 1) % P] += 1
+    if odd_sum:
+        d[P - 1] += 1
+    assert int(d.sum()) == total + int(odd_sum) and np.all(d >= 0)
+    return d.astype(np.int32)
+
+
+class GlowCase:
+    """One compared call: `n` = the scanned length (P or F2), its ids and forced durations, the frame count they give."""
+
+    def __init__(self, hp, axis, n, odd_sum=False):
+        from tests.test_emu_prosody import attn_durations
+
+        self.axis, self.n, self.odd = axis, int(n), bool(odd_sum)
+        self.key = self.n + (100000 if odd_sum else 0) + (200000 if axis == "F2" else 0)
+        self.ids = glow_ids(hp, self.n if axis == "P" else 8)
+        self.d = np.full(self.n, 2, np.int32) if axis == "P" else forced_durations(hp, self.n, 8, odd_sum)
+        self.exp_d, self.F = attn_durations(self.d, hp.n_sqz)  # what the call reports: the last id truncated with the frame count
+        self._hp, self._noise = hp, None
+
+    @property
+    def noise(self):
+        if self._noise is None:
+            self._noise = glow_noise(self._hp, self.F, self.key)
+        return self._noise
+
+    def __repr__(self):
+        return f"{self.axis}={self.n}{'+1 frame' if self.odd else ''}"
+
+
+def glow_call_signature(eng, g, case):
+    """kernel_signature of the case's lone call (the device's own noise: no value is read)."""
+    eng.profile_reset()
+    eng.glow_infer(g, case.ids, 0.667, 1.0, seed=case.key, durations=case.d).free()
+    return kernel_signature(eng)
+
+
+def scan_glow_signatures(eng, g, hp, axis, lo, hi, label="", only=None):
+    """{n: kernel_signature} of a lone call at every n in [lo, hi] (`only`: at these n) along `axis`: "P" = n ids forced to 2
+    frames each, "F2" = 8 ids with forced durations summing to n_sqz * n (forced_durations); prints each signature's range."""
+    ns = sorted(only) if only is not None else list(range(lo, hi + 1))
+    sigs = {n: glow_call_signature(eng, g, GlowCase(hp, axis, n)) for n in ns}
+    start = ns[0]
+    for a, b in zip(ns, ns[1:] + [None]):
+        if b is None or sigs[b] != sigs[a]:
+            print(f"{label} scan: {axis} {start}..{a}: {sorted(sigs[a])}")
+            start = b
+    return sigs
+
+
+class GlowOracle:
+    """The oracle's raw mel per compared case (text encoder -> expansion by the forced durations -> + noise -> the flows in
+    reverse: tests/test_emu_prosody.oracle_with_durations), computed once per (weights, case)."""
+
+    def __init__(self):
+        self._c = {}
+        self.seconds = 0.0
+
+    def __call__(self, gsd, hp, key, case):
+        from tests.test_emu_prosody import oracle_with_durations
+
+        k = (key, case.axis, case.key)
+        if k not in self._c:
+            t = time.perf_counter()
+            self._c[k] = oracle_with_durations(gsd, hp, case.ids, case.d, case.noise, 0.667)
+            self.seconds += time.perf_counter() - t
+        return self._c[k]
+
+
+def mel_plane(eng, mel):
+    """The whole raw plane [B, M, ld] of a mel, the padding columns max_frames .. ld included (`numpy` stops at max_frames)."""
+    ptr, ld = mel.plane("raw")
+    full = eng.mel_from_device(ptr, [ld] * mel.batch, mel.channels, ld)
+    out = full.numpy("raw")
+    full.free()
+    return out
+
+
+F32_MEL = dict(max=5e-5, rms=None)  # the project's bar: test_golden_reference_parity, check_mels
+
+
+def f16_mel_bounds(voice="ljspeech"):
+    """The bar of test_f16_acoustic_mode_against_the_reference over the committed goldens of `voice`: the largest deviation of the
+    reference's own decoder under .half() from its f32 mel (tests/golden/glow_half_reference.json)."""
+    from tests.golden_util import load_glow_half_reference
+
+    got = [v for k, v in load_glow_half_reference().items() if k.startswith(voice)]
+    assert got, voice
+    return dict(max=max(float(v["dec_half_max"]) for v in got), rms=max(float(v["dec_half_rms"]) for v in got))
+
+
+def compare_mel(raw, ref, F, bounds, label=""):
+    """One row of a raw plane [M, ld]: columns [0, F) against the oracle's mel (max |error| over every element, and RMS where the
+    bound has one), the rest of the row exactly 0.  Prints the worst element's column; returns the max |error|."""
+    assert ref.shape[1] == F and raw.shape[0] == ref.shape[0] and raw.shape[1] >= F, (label, ref.shape, raw.shape, F)
+    assert np.all(raw[:, F:] == 0), (label, "columns past the row's frames are not 0", np.argwhere(raw[:, F:] != 0)[:4].tolist())
+    if F == 0:
+        return 0.0
+    d = np.abs(raw[:, :F].astype(np.float64) - ref)
+    mx, rms = float(d.max()), float(np.sqrt(np.mean(d ** 2)))
+    ch, col = np.unravel_index(int(d.argmax()), d.shape)
+    print(f"{label}: F {F} max-abs {mx:.2e} (channel {ch}, column {col} of {F}) rms {rms:.2e}")
+    assert mx <= bounds["max"], (label, mx, int(ch), int(col), bounds)
+    assert bounds["rms"] is None or rms <= bounds["rms"], (label, rms, bounds)
+    return mx
+
+
+def check_glow_rows(eng, g, gsd, hp, cases, oracle, key, bounds=F32_MEL, label="", solo=None, solo_tol=1e-5, on_counts=None):
+    """`cases` as ONE call (a lone call, or a padded batch in the order given) against the oracle: frames exact, the durations
+    read back equal to the forced ones, every element of the raw mel within `bounds`, the plane's padding and every row's tail
+    exactly 0; with `solo` ({case key: the lone call's mel}) every row within `solo_tol` max-abs of its lone call.
+    `on_counts(kernel_counts, tag)`: the caller's assertions on the call's launches.  Returns (kernel names that ran, [each row's
+    mel [M, F]])."""
+    B = len(cases)
+    Fmax, Pmax = max(c.F for c in cases), max(len(c.ids) for c in cases)
+    noise = np.zeros((B, hp.mel_channels, Fmax + 5), F32)
+    for b, c in enumerate(cases):
+        noise[b, :, : c.noise.shape[1]] = c.noise
+    eng.profile_reset()
+    mel = eng.glow_infer(g, [c.ids for c in cases], 0.667, 1.0, noise=noise, durations=[c.d for c in cases])
+    counts = eng.kernel_counts()
+    ran = {k for k, n in counts.items() if n > 0}
+    if on_counts:
+        on_counts(counts, f"{label} {cases!r}")
+    frames, dur = [int(f) for f in mel.frames], mel.durations
+    plane = mel_plane(eng, mel) if Fmax else np.zeros((B, hp.mel_channels, 0), F32)
+    mel.free()
+    assert plane.shape[2] % 4 == 0 and Fmax <= plane.shape[2] < Fmax + 4, (label, plane.shape, Fmax)
+    assert dur.shape == (B, Pmax), (label, dur.shape)
+    rows = []
+    for b, c in enumerate(cases):
+        tag = f"{label} {c!r} " + ("B=1" if B == 1 else f"row {b} of B={B}")
+        assert frames[b] == c.F, (tag, frames[b], c.F)
+        assert np.array_equal(dur[b, : len(c.ids)], c.exp_d) and np.all(dur[b, len(c.ids):] == 0), (tag, dur[b].tolist(), c.exp_d.tolist())
+        compare_mel(plane[b], oracle(gsd, hp, key, c), c.F, bounds, tag)
+        rows.append(plane[b][:, : c.F].copy())
+        if solo is not None and c.F:
+            e = float(np.abs(rows[-1].astype(np.float64) - solo[c.key]).max())
+            assert e <= solo_tol, (tag, "against its lone call", e, solo_tol)
+    return ran, rows
+
+
+def check_glow_lengths(eng, g, gsd, hp, cases, oracle, key, bounds=F32_MEL, label="", batch=8, solo_tol=1e-5, on_counts=None,
+                       rows=None):
+    """Each case as a lone call, then the longest <= `batch` of them as one ragged padded batch in unsorted order (`rows`: this
+    batch, in this order, instead): every row against the oracle (check_glow_rows) and within `solo_tol` of its lone call.
+    Returns (kernel names that ran in the lone calls, kernel names that ran in the batch)."""
+    ran, solo = set(), {}
+    for c in cases:
+        r, got = check_glow_rows(eng, g, gsd, hp, [c], oracle, key, bounds, label, on_counts=on_counts)
+        ran |= r
+        solo[c.key] = got[0]
+    if rows is None:
+        rows = sorted(cases, key=lambda c: (-c.F, -len(c.ids), c.key))[:batch]  # the longest: the most tiles per row
+        rows = rows[::2] + rows[1::2][::-1]  # ragged, not sorted
+    ran_batch = set()
+    if len(rows) > 1:
+        ran_batch, _ = check_glow_rows(eng, g, gsd, hp, rows, oracle, key, bounds, label, solo=solo, solo_tol=solo_tol, on_counts=on_counts)
+    return ran, ran_batch
+
+
+def check_plain_durations(eng, g, gsd, hp, P, length_scale=1.0, label=""):
+    """One plain call (no forced durations) on glow_ids(P): the duration predictor and duration_kernel's ceil path.  The
+    durations equal ceil(exp(logw) * length_scale) of the oracle's logw with the last id truncated as attn_durations does."""
+    from tests.test_emu_prosody import attn_durations, oracle_logw, scaled_w
+
+    ids = glow_ids(hp, P, gsd, length_scale)
+    w = scaled_w(oracle_logw(gsd, hp, ids), length_scale)
+    exp_d, F = attn_durations(np.ceil(w).astype(np.int64), hp.n_sqz)
+    mel = eng.glow_infer(g, ids, 0.667, length_scale, seed=P, want_durations=True)
+    got, frames = mel.durations, int(mel.frames[0])
+    mel.free()
+    assert got.shape == (1, P) and frames == F == int(got.sum()), (label, P, frames, F)
+    assert np.array_equal(got[0], exp_d), (label, P, np.flatnonzero(got[0] != exp_d)[:8].tolist())
+
+
+def check_interior_columns_equal(eng, g, hp, F2, label=""):
+    """A bound-free seam check of the decoder: 8 ids of which ONE gets every frame, no noise -> every decoder column starts from the
+    same vector, and the flows are convolutions along time: away from the two ends (further than the decoder's receptive field,
+    n_blocks_dec * n_block_layers * (kernel_size_dec - 1) / 2 columns) every column goes through the same arithmetic in the same
+    order, whichever tile it falls in, so frames f and f + n_sqz are equal bit for bit.  A tile that recomputes too narrow a halo, or
+    reads a neighbour's column, breaks that at its seams.  Returns the number of interior columns."""
+    d = np.zeros(8, np.int32)
+    d[3] = hp.n_sqz * F2
+    mel = eng.glow_infer(g, glow_ids(hp, 8), 0.0, 1.0, durations=d)
+    F = int(mel.frames[0])
+    raw = mel.numpy("raw")[0]
+    mel.free()
+    assert F == hp.n_sqz * F2, (label, F)
+    reach = hp.n_blocks_dec * hp.n_block_layers * ((hp.kernel_size_dec - 1) // 2) * hp.n_sqz
+    a, b = raw[:, reach : F - reach - hp.n_sqz], raw[:, reach + hp.n_sqz : F - reach]
+    assert a.shape[1] > 0, (label, "F2 too short for an interior", F2, reach)
+    bad = np.flatnonzero(np.any(a != b, axis=0))
+    assert bad.size == 0, (label, "decoder columns differ in the interior: frames", (bad[:8] + reach).tolist(),
+                           float(np.abs(a - b).max()))
+    return a.shape[1] // hp.n_sqz
+
+
+def choose_glow_lengths(sigs, must=(), edges=None, cap=16, label=""):
+    """The lengths a GlowTTS case compares, at most `cap`: the first n of each signature and `must`; then the transitions (n and
+    n + 1 where the signature changes) by increasing n; then lengths that cover the tile edges `edges` (edge_frames) not hit yet.
+    Prints the choice with the edges each length covers, and whatever the cap left out."""
+    ns = sorted(sigs)
+    first = {}
+    for n in ns:
+        first.setdefault(sigs[n], n)
+    chosen = set(first.values()) | set(must)
+    assert len(chosen) <= cap, (label, "more signatures and fixed lengths than the cap", sorted(chosen))
+    trans = [m for a, b in zip(ns, ns[1:]) if sigs[a] != sigs[b] for m in (a, b)]
+    for m in trans:
+        if len(chosen) < cap:
+            chosen.add(m)
+    if set(trans) - chosen:
+        print(f"{label}: transitions without a length (cap {cap}): {sorted(set(trans) - chosen)}")
+    edges = edges or {}
+    chosen |= set(cover_edges(edges, cap - len(chosen), have=chosen))
+    left = {(s, w, k) for hits in edges.values() for (_, s, w, k) in hits}
+    for n in sorted(chosen):
+        hits = edges.get(n, ())
+        left -= {(s, w, k) for (_, s, w, k) in hits}
+        print(f"{label} length {n}: " + (", ".join(sorted({f'{lab} {kind}' for (lab, _, _, kind) in hits})) or "-"))
+    if left:
+        print(f"{label}: edges without a length (cap {cap}): {sorted((s[0], w, k) for (s, w, k) in left)}")
+    return sorted(chosen)
 
 
 # ---- BASELINE config 3 ---------------------------------------------------------------------------------------------------
