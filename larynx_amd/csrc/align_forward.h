@@ -51,7 +51,7 @@ static AlignLayout glow_align_layout(const mi355tts_glow_hparams& h, const GlowE
 static void launch_path(mi355tts_ctx* ctx, Worker* w, const AlignLayout& al, int B, const float* logp, long long lp_bs, const int* d_plen,
                         const int* d_frames, unsigned* bits, int* dur, float* score) {
   ProfScope ps(ctx, w, KC_SMALL, 0);
-  kn_hit(ctx, KN_ALIGN_PATH);
+  ps.kernel(KN_ALIGN_PATH);
   switch_const<1, 2, 4, 8, 16, 32>(al.CH, [&](auto ch) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(align_path_kernel<decltype(ch)::value>), dim3(B), dim3(64), 0, w->stream, logp, lp_bs, al.ldp, d_plen,
                        d_frames, bits, al.bits_bs, dur, al.dur_ld, score);
@@ -121,7 +121,7 @@ static int run_glow_fwd(const GlowPass& p, const GlowDecView& dv, const GlowBloc
   a.H = H; a.half = half;
   const double mac = (prev ? (double)H * H + 2.0 * half * H : 0.0) + (next ? (double)H * half : 0.0);
   ProfScope ps(p.ctx, p.w, p.cls, 2.0 * mac * (double)p.n_max * p.B);
-  kn_hit(p.ctx, KN_GLOW_FWD);
+  ps.kernel(KN_GLOW_FWD);
   const dim3 grid((p.n_max + COL_T - 1) / COL_T, p.B);
   if (prev) hipLaunchKernelGGL(glow_fwd_kernel<true>, grid, dim3(512), 0, p.s, a);
   else hipLaunchKernelGGL(glow_fwd_kernel<false>, grid, dim3(512), 0, p.s, a);
@@ -250,7 +250,7 @@ extern "C" int mi355tts_glow_align(mi355tts_ctx* ctx, int glow, const int64_t* i
   const long long lp_bs = (long long)Fmax * al.ldp;
   {
     ProfScope ps(ctx, w, KC_SMALL, 2.0 * M * (double)Pmax * Fmax * B);
-    kn_hit(ctx, KN_ALIGN_SCORE);
+    ps.kernel(KN_ALIGN_SCORE);
     const float c0 = (float)(-0.5 * M * std::log(2.0 * 3.14159265358979323846));
     hipLaunchKernelGGL(align_score_kernel, dim3(al.ldp / 64, (Fmax + SC_TJ - 1) / SC_TJ, B), dim3(256), 0, s, v.xm, (long long)M * r.el.P, r.el.P,
                        v.len, d_z, bsM, mel_ld, d_frames, M, c0, logp, lp_bs, al.ldp);

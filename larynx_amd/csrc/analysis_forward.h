@@ -152,7 +152,7 @@ extern "C" int mi355tts_mel_from_audio(mi355tts_ctx* ctx, int model, const float
     a.plain = audio ? 0 : 1;
     // the transform (5 N log2 N of the 512-point complex one + the unpack) and the filter bank's two triangles per bin
     ProfScope ps(ctx, w, KC_SMALL, (double)total * (5.0 * GL_HALF * 9 + 10.0 * GL_HALF + 4.0 * GL_BINS));
-    kn_hit(ctx, KN_MEL_ANALYSIS);
+    ps.kernel(KN_MEL_ANALYSIS);
     hipLaunchKernelGGL(mel_analysis_kernel, dim3(ld / MA_FRAMES, B), dim3(64 * MA_FRAMES), 0, s, a);
   }
   HIPCHECK(mi355_sync(s));

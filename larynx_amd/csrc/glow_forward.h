@@ -282,7 +282,7 @@ static int run_oproj_ln(const GlowPass& p, const GlowLayer& L, const float* att,
   a.w = p.A + L.o16.w_off; a.b = p.A + L.o16.b_off; a.gamma = p.A + L.g1; a.beta = p.A + L.b1;
   a.H = H; a.eps = 1e-4f;
   ProfScope ps(p.ctx, p.w, p.cls, 2.0 * (double)H * H * (double)p.n_max * p.B);
-  kn_hit(p.ctx, KN_OPROJ_LN);
+  ps.kernel(KN_OPROJ_LN);
   hipLaunchKernelGGL(oproj_ln_kernel, dim3((p.n_max + COL_T - 1) / COL_T, p.B), dim3(512), 0, p.s, a);
   return 0;
 }
@@ -308,7 +308,7 @@ static int run_glow_tail(const GlowPass& p, const GlowDecView& dv, const GlowBlo
   a.H = H; a.half = half;
   const double mac = (double)H * H + 2.0 * half * H + (next ? (double)H * half : 0.0);
   ProfScope ps(p.ctx, p.w, p.cls, 2.0 * mac * (double)p.n_max * p.B);
-  kn_hit(p.ctx, KN_GLOW_TAIL);
+  ps.kernel(KN_GLOW_TAIL);
   hipLaunchKernelGGL(glow_tail_kernel, dim3((p.n_max + COL_T - 1) / COL_T, p.B), dim3(512), 0, p.s, a);
   return 0;
 }
@@ -342,7 +342,7 @@ static int run_wn_f16(const GlowPass& p, const GlowDecView& dv, const GlowBlock&
     else
       hipLaunchKernelGGL((wn_f16_kernel<5, 4, 1, 6>), grid, dim3(256), 0, p.s, a);
   }
-  kn_hit(p.ctx, KN_WN_F16);
+  ps.kernel(KN_WN_F16);
   return 0;
 }
 
@@ -354,7 +354,7 @@ static void launch_attention(const GlowPass& p, const GlowLayer& L, const GlowEn
   const long long bsH = (long long)H * P;
   ProfScope ps = p.small();
   if (Pmax > ATTM_MAXP) {
-    kn_hit(p.ctx, KN_ATTENTION_VALU);
+    ps.kernel(KN_ATTENTION_VALU);
     hipLaunchKernelGGL(attention_kernel, dim3(att_rows / ATT_ROWS, nh, p.B), dim3(256), 0, p.s, v.qkv, 3 * bsH, P, p.d_len, H, nh,
                        h.window_size, p.A + L.ek, p.A + L.ev, v.t2, bsH, P, v.sc, P);
     return;
@@ -363,7 +363,7 @@ static void launch_attention(const GlowPass& p, const GlowLayer& L, const GlowEn
   const int dkh = H / nh;
   const int nk = dkh <= 32 ? 16 : dkh <= 64 ? 32 : dkh <= 96 ? 48 : 64;
   const bool small_lds = Pmax <= 256 && !p.w->opt.env.att_big_lds;  // (A/B runs)
-  kn_hit(p.ctx, small_lds ? KN_ATTENTION : KN_ATTENTION_P768);
+  ps.kernel(small_lds ? KN_ATTENTION : KN_ATTENTION_P768);
   auto launch = [&](auto k, auto exact, auto pm) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(attention_mfma_kernel<decltype(k)::value, decltype(exact)::value != 0, decltype(pm)::value>), ag,
                        dim3(512), 0, p.s, v.qkv, 3 * bsH, P, p.d_len, H, nh, h.window_size, p.A + L.ek, p.A + L.ev, v.t2, bsH, P);

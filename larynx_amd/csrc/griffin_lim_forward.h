@@ -115,19 +115,19 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
   const float* tab = ctx->gl_table;
   {
     ProfScope ps(ctx, w, KC_SMALL, 2.0 * gm->p.num_mels * GL_BINS * (double)T * B);
-    kn_hit(ctx, KN_GL_MAG);
+    ps.kernel(KN_GL_MAG);
     hipLaunchKernelGGL(griffin_lim_mag_kernel, dim3((T + GL_MAG_FRAMES - 1) / GL_MAG_FRAMES, B), dim3(256), 0, s, mel->voc,
                        (long long)mel->M * mel->ld, mel->ld, d_frames, mel->M, gm->basis, gm->p.mel_scaling, mag, T);
   }
   {
     ProfScope ps(ctx, w, KC_SMALL, 0);
-    kn_hit(ctx, KN_GL_INIT);
+    ps.kernel(KN_GL_INIT);
     hipLaunchKernelGGL(griffin_lim_init_kernel, dim3(T, B), dim3(64), 0, s, mag, d_frames, T, dph_in, dph_out, T, seed, tab, fb[0]);
   }
   int cur = 0;
   for (int it = 0; it < iters; ++it) {
     ProfScope ps(ctx, w, KC_SMALL, 0);
-    kn_hit(ctx, KN_GL_ITER);
+    ps.kernel(KN_GL_ITER);
     hipLaunchKernelGGL(griffin_lim_iter_kernel, dim3(T, B), dim3(64), 0, s, fb[cur], fb[cur ^ 1], mag, d_frames, T, tab);
     cur ^= 1;
   }
@@ -141,13 +141,13 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
   if (wav_f32 || wav_i16) {
     ProfScope ps(ctx, w, KC_SMALL, 0);
     if (wav_i16) HIPCHECK(hipMemsetAsync(peak, 0, sizeof(unsigned) * B, s));
-    kn_hit(ctx, KN_GL_OUT);
+    ps.kernel(KN_GL_OUT);
     hipLaunchKernelGGL(griffin_lim_out_kernel, dim3(128, B), dim3(256), 0, s, fb[cur], T, d_frames, wav, wbs, wld, wav_i16 ? peak : (unsigned*)nullptr);
   }
   short* i16 = (short*)(base + o_i16);
   if (wav_i16) {
     ProfScope ps(ctx, w, KC_SMALL, 0);
-    kn_hit(ctx, KN_GL_INT16);
+    ps.kernel(KN_GL_INT16);
     if (out_dev) hipLaunchKernelGGL(griffin_lim_int16_kernel, dim3(128, B), dim3(256), 0, s, wav, wbs, d_frames, peak, wav_i16, (long long)wav_ld, (long long)wav_ld);
     else hipLaunchKernelGGL(griffin_lim_int16_kernel, dim3(128, B), dim3(256), 0, s, wav, wbs, d_frames, peak, i16, (long long)Nld, (long long)Nld);
   }

@@ -140,8 +140,7 @@ static int launch_f16_k(const HPlan& p, hipStream_t s) {
 }
 static int run_plan_f16(mi355tts_ctx* ctx, Worker* w, const HPlan& p, int cls, hipStream_t s) {
   ProfScope ps(ctx, w, cls, p.flop, s);
-  kn_hit(ctx, KN_CONV_F16);
-  g_last_sub = p.a.rows;
+  ps.kernel(KN_CONV_F16, p.a.rows);
   if (p.epi == EPI_UPSAMPLE) return p.mrf ? launch_f16_k<2, EPI_UPSAMPLE, true>(p, s) : launch_f16_k<2, EPI_UPSAMPLE, false>(p, s);
   int rc = 0;
   if (!switch_const<3, 5, 7, 11>(p.K, [&](auto k) { rc = launch_f16_k<decltype(k)::value, EPI_LINEAR, false>(p, s); }))
@@ -169,8 +168,7 @@ static int run_group_f16(mi355tts_ctx* ctx, Worker* w, const HPlan* p, int n, in
   }
   std::copy(lay.off, lay.off + 4, g.off);
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
-  kn_hit(ctx, KN_CONV_F16_GROUP);
-  g_last_sub = p[0].a.rows;
+  ps.kernel(KN_CONV_F16_GROUP, p[0].a.rows);
   const dim3 grid(g.off[3], 1, B);
   int rc = 0;
   switch_taps(lay, [&](auto k0, auto k1, auto k2) {
@@ -219,8 +217,7 @@ static int run_pair_group_f16(mi355tts_ctx* ctx, Worker* w, const HPairPlan* p, 
   }
   std::copy(lay.off, lay.off + 4, g.off);
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
-  kn_hit(ctx, KN_PAIR_F16_GROUP);
-  g_last_sub = C;
+  ps.kernel(KN_PAIR_F16_GROUP, C);
   return h_tile_dispatch(tile, [&](auto ti) {
     constexpr HTileCfg t = H_TILES[decltype(ti)::value];
     hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_f16_group_kernel<11, 7, 3, t.MB, t.NB, t.WM, t.WN, ConvHalo<11>::v, ConvHalo<7>::v, ConvHalo<3>::v, H_CH, t.RING, t.PAIR_MINW>),

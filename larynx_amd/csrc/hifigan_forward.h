@@ -556,7 +556,7 @@ static int f32_post(VocPass& p, const StageCursor<float>& c) {  // x = tanh(conv
     a.peak_ld = p.peak_ld;
   }
   ProfScope ps(p.ctx, p.w, KC_VOC_IO, 2.0 * (double)c.ch * 7 * (double)c.Lin * p.B);
-  kn_hit(p.ctx, KN_POST_CONV);
+  ps.kernel(KN_POST_CONV);
   const dim3 pg((c.Lin + POST_TW - 1) / POST_TW, p.B);
   switch_const<1, 2, 3>(c.ncur, [&](auto n) { hipLaunchKernelGGL(HIP_KERNEL_NAME(post_conv_kernel<7, decltype(n)::value>), pg, dim3(256), 0, p.s, a); });
   return 0;
@@ -612,7 +612,7 @@ static int f16_pre(VocPass& p, StageCursor<uint4>& c) {
   uint4* melh = p.plane<uint4>(1);
   {
     ProfScope ps(p.ctx, p.w, KC_SMALL, 0, p.s);
-    kn_hit(p.ctx, KN_PACK_OCTETS);
+    ps.kernel(KN_PACK_OCTETS);
     hipLaunchKernelGGL(pack_octets_kernel, dim3((F + 255) / 256, moct, B), dim3(256), 0, p.s, mel->voc, (long long)mel->M * mel->ld, mel->ld, M, p.d_frames, 1,
                        melh, (long long)moct * F, F);
   }
@@ -724,7 +724,7 @@ static int f16_post(VocPass& p, const StageCursor<uint4>& c) {  // x = tanh(conv
   a.peak = p.peak;
   a.peak_ld = p.peak_ld;
   ProfScope ps(p.ctx, p.w, KC_VOC_IO, 2.0 * (double)c.ch * 7 * (double)c.Lin * p.B, p.s);
-  kn_hit(p.ctx, KN_POST_F16);
+  ps.kernel(KN_POST_F16);
   const dim3 pg((c.Lin + HPOST_TW - 1) / HPOST_TW, p.B);
   switch_const<1, 2, 3>(c.ncur, [&](auto n) { hipLaunchKernelGGL(HIP_KERNEL_NAME(post_f16_kernel<7, decltype(n)::value>), pg, dim3(256), 0, p.s, a); });
   return 0;
@@ -862,7 +862,7 @@ static int voc_tail_one_launch(VocPass& p, const VocCall& call, float* wav) {
     if (call.wav_i16) { o.i16 = p.i16; o.i_bs = (long long)p.ild; o.i_ld = (long long)p.ild; }
   }
   if (o.f32 || o.i16 || any_out) {
-    kn_hit(p.ctx, KN_WAVE_OUT);
+    ps.kernel(KN_WAVE_OUT);
     hipLaunchKernelGGL(wave_out_kernel, dim3(128, B), dim3(256), 0, p.s, o);
   }
   if (!out_dev && p.any_f32 && B > 1) hipLaunchKernelGGL(zero_tail_kernel, dim3(64, B), dim3(256), 0, p.s, wav, (long long)p.Nld, (long long)p.Nld, p.d_frames, p.hop);

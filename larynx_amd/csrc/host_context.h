@@ -2,50 +2,9 @@
 // (one translation unit: included once by mi355tts.hip, after the kernel headers)
 #pragma once
 
+#include "host_profile.h"
+
 // ------------------------------------------------------------------ context
-struct ProfEvent {
-  hipEvent_t a, b;
-  int cls;
-  double flop;
-  int kn, sub;  // kernel name (KName, -1 = a kernel without one) and a sub-key of the launch (its output rows / channels)
-};
-enum KClass { KC_RESBLOCK = 0, KC_UPSAMPLE, KC_VOC_IO, KC_GLOW_ENC_CONV, KC_GLOW_DEC_CONV, KC_SMALL, KC_MRF_NARROW, KC_COUNT };
-static const char* kclass_name[KC_COUNT] = {"conv_mfma.hifigan_resblock", "conv_mfma.hifigan_upsample",
-                                            "conv_mfma.hifigan_pre_post", "conv_mfma.glow_encoder",
-                                            "conv_mfma.glow_decoder",     "elementwise",
-                                            "mrf_small.hifigan_narrow_stage"};
-
-// Launches per kernel NAME since the last mi355tts_profile_reset (always counted: one relaxed atomic add per launch) —
-// mi355tts_kernel_counts_json.  The class counters above cannot tell a kernel from the fallback that would take its place
-// (rb_group_kernel -> conv_group_kernel, rb_pair_group_kernel -> pair_group_kernel:
-// same launch counts per class, same bits by design), so the device tests assert on these.
-enum KName {
-  KN_CONV_MFMA = 0, KN_CONV_M128, KN_CONV_GROUP, KN_RB_CONV, KN_RB_GROUP, KN_RB_GROUP_SNAKE, KN_PAIR, KN_PAIR_GROUP, KN_RB_PAIR,
-  KN_RB_PAIR_GROUP, KN_CONV_BF16, KN_CONV_BF16_GROUP, KN_PAIR_BF16, KN_PAIR_BF16_GROUP, KN_MRF_SMALL, KN_MRF8, KN_GATE16, KN_GATE16_WIDE, KN_LIN16,
-  KN_LIN16_LN, KN_LIN16_WIDE, KN_GLOW_TAIL, KN_OPROJ_LN, KN_POST_CONV, KN_WAVE_OUT, KN_ATTENTION, KN_CONV_F16, KN_CONV_F16_GROUP, KN_POST_F16,
-  KN_PACK_OCTETS, KN_PAIR_F16_GROUP, KN_WN_F16, KN_RB_GROUP_NB4, KN_GL_MAG, KN_GL_INIT, KN_GL_ITER, KN_GL_OUT, KN_GL_INT16, KN_GLOW_FWD, KN_ALIGN_SCORE,
-  KN_ALIGN_PATH, KN_MEL_ANALYSIS, KN_ATTENTION_P768, KN_ATTENTION_VALU, KN_COUNT
-};
-static const char* kname_name[KN_COUNT] = {
-    "conv_mfma_kernel", "conv_mfma_kernel.m128", "conv_group_kernel", "rb_conv_kernel", "rb_group_kernel", "rb_group_kernel.snake",
-    "resblock_pair_kernel", "pair_group_kernel", "rb_pair_kernel", "rb_pair_group_kernel", "conv_bf16_kernel", "conv_bf16_group_kernel",
-    "pair_bf16_kernel", "pair_bf16_group_kernel", "mrf_small_kernel", "mrf8_kernel", "gate16_kernel", "gate16_kernel.wide", "lin16_kernel", "lin16_kernel.ln", "lin16_kernel.wide",
-    "glow_tail_kernel", "oproj_ln_kernel", "post_conv_kernel", "wave_out_kernel", "attention_mfma_kernel", "conv_f16_kernel", "conv_f16_group_kernel",
-    "post_f16_kernel", "pack_octets_kernel", "pair_f16_group_kernel", "wn_f16_kernel", "rb_group_kernel.nb4",
-    "griffin_lim_mag_kernel", "griffin_lim_init_kernel", "griffin_lim_iter_kernel", "griffin_lim_out_kernel", "griffin_lim_int16_kernel",
-    "glow_fwd_kernel", "align_score_kernel", "align_path_kernel", "mel_analysis_kernel",
-    // launch_attention's other two branches ("attention_mfma_kernel" is the 256-id LDS layout): the ATTM_MAXP layout, the VALU kernel
-    "attention_mfma_kernel.p768", "attention_kernel"};
-// the launch helpers without a context argument (launch_conv_k, launch_group_k) count through this: set by run_plan / run_group
-static thread_local std::atomic<long long>* g_kn = nullptr;
-// the kernel name (and launch sub-key: output rows / channels) of the launch inside the running ProfScope: the scope's
-// destructor files its event pair under them (mi355tts_profile_kernels_json: durations per kernel NAME, not only per class)
-static thread_local int g_last_kn = -1, g_last_sub = 0;
-static inline void kn_add(int k) {
-  g_last_kn = k;
-  if (g_kn) g_kn[k].fetch_add(1, std::memory_order_relaxed);
-}
-
 // Host wait for a stream.  hipStreamSynchronize SPINS: a caller thread burns a core for the ~4 ms its kernels run (28 ms of CPU
 // per utterance with eight callers, measured), and the reference's calling pattern is a ThreadPoolExecutor of up to 32 such
 // threads per process (larynx/__init__.py:66-67, :146) — times 8 ranks on a node.  Default (mode 3, adaptive): poll
@@ -104,8 +63,7 @@ static hipError_t mi355_sync(hipStream_t s) {
   return hipStreamSynchronize(s);
 }
 
-struct Worker {
-  hipStream_t stream = nullptr;
+struct Worker : ProfLane {  // (its stream, event pairs, flop_scale and `quiet`: host_profile.h)
   char* arena = nullptr;
   size_t arena_bytes = 0;
   size_t arena_pos = 0;
@@ -113,16 +71,9 @@ struct Worker {
   size_t pinned_ints = 0;
   char* pinned_out = nullptr;  // pinned host staging for waveform outputs (grow-only)
   size_t pinned_out_bytes = 0;
-  std::vector<ProfEvent> events;
-  // profiled FLOP of the launches that follow = the padded-batch figure x this (sum of the rows' real lengths / (B x longest))
-  double flop_scale = 1.0;
-  // this worker's launches are neither profiled nor counted per kernel name (the dispatch self-check's own launches are not a
-  // caller's: a worker-local switch, so concurrent calls on the context keep their samples and counts)
-  bool quiet = false;
   // hardware-queue group of `stream` (streams of one group run their kernels one after the other): learnt by
   // probe_queue_groups at mi355tts_reserve, -1 = not probed (a worker created on demand)
   int qgroup = -1;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> event_pool;
   // side streams for the independent MRF branches of a HiFi-GAN stage
   hipStream_t aux[2] = {nullptr, nullptr};
   hipEvent_t ev_fork = nullptr;
@@ -130,7 +81,7 @@ struct Worker {
   CallOptions opt;  // what selects this call's kernels, tiles and schedule: filled when the worker is checked out (acquire_worker)
 };
 
-struct mi355tts_ctx {
+struct mi355tts_ctx : ProfSums {  // (the profiling switch, the launch sums and the name counters: host_profile.h)
   int device = 0;
   int ncu = 256;  // compute units (hipGetDeviceProperties at create): the dispatch-order logic of grouped launches
   std::mutex mu;
@@ -145,7 +96,6 @@ struct mi355tts_ctx {
   std::vector<Worker*> free_workers;
   std::vector<Worker*> all_workers;
   ContextOptions opts;  // mi355tts_set_option's (host_options.h); calls read them through Worker::opt
-  std::atomic<bool> profiling{false};
   // calls currently holding a worker; with "adaptive_schedule" on and more than one in flight the vocoder
   // launches the members of a grouped step one by one (and never forks its MRF chains)
   std::atomic<int> active_calls{0};
@@ -166,12 +116,6 @@ struct mi355tts_ctx {
   std::vector<std::pair<void*, size_t>> mel_pool;
   size_t mel_pool_cap = 256;  // raised by mi355tts_reserve to 3 x workers + slack
   std::map<void*, size_t> mel_sizes;  // true size of every block the pool has ever handed out
-  struct Acc {
-    long long launches = 0;
-    double ms = 0, flop = 0;
-  } prof[KC_COUNT];
-  std::map<std::pair<int, int>, Acc> prof_kn[KC_COUNT];  // per class: (kernel name, sub-key) -> the same sums
-  std::atomic<long long> kn[KN_COUNT] = {};  // launches per kernel name (KName)
 };
 
 struct mi355tts_mel {
@@ -189,11 +133,6 @@ struct mi355tts_mel {
   int dur_ld = 0;
   std::vector<int32_t> durations;
 };
-
-static inline void kn_hit(mi355tts_ctx* ctx, int k) {
-  g_last_kn = k;
-  ctx->kn[k].fetch_add(1, std::memory_order_relaxed);
-}
 
 static int acquire_worker(mi355tts_ctx* ctx, Worker** out) {
   {
@@ -251,28 +190,9 @@ static int acquire_worker(mi355tts_ctx* ctx, Worker** out) {
   return 0;
 }
 
-static void drain_profile(mi355tts_ctx* ctx, Worker* w) {
-  if (w->events.empty()) return;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  for (auto& ev : w->events) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) {
-      ctx->prof[ev.cls].launches++;
-      ctx->prof[ev.cls].ms += ms;
-      ctx->prof[ev.cls].flop += ev.flop;
-      mi355tts_ctx::Acc& k = ctx->prof_kn[ev.cls][std::make_pair(ev.kn, ev.sub)];
-      k.launches++;
-      k.ms += ms;
-      k.flop += ev.flop;
-    }
-    w->event_pool.emplace_back(ev.a, ev.b);
-  }
-  w->events.clear();
-}
-
 static void release_worker(mi355tts_ctx* ctx, Worker* w) {
   ctx->active_calls.fetch_sub(1, std::memory_order_relaxed);
-  drain_profile(ctx, w);
+  drain_profile(ctx, w, ctx->mu);
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (w->qgroup >= 0 && w->qgroup < (int)ctx->qgroup_busy.size() && ctx->qgroup_busy[w->qgroup] > 0) ctx->qgroup_busy[w->qgroup] -= 1;
   ctx->free_workers.push_back(w);

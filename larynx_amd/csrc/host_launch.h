@@ -1,42 +1,8 @@
-// mi355tts host runtime — profiling scopes and the conv / fused-pair launchers (tile-shape choice)
+// mi355tts host runtime — the row-length rule and the conv / fused-pair launchers (tile-shape choice)
 // (one translation unit: included once by mi355tts.hip, after the kernel headers)
 #pragma once
 
 // ------------------------------------------------------------------ launch helpers
-struct ProfScope {
-  mi355tts_ctx* ctx;
-  Worker* w;
-  bool on;
-  ProfEvent ev;
-  hipStream_t st;
-  ProfScope(mi355tts_ctx* c, Worker* wk, int cls, double flop, hipStream_t stream = nullptr)
-      : ctx(c), w(wk), on(c->profiling.load() && !wk->quiet), st(stream ? stream : wk->stream) {
-    if (!on) return;
-    if (!w->event_pool.empty()) {
-      ev.a = w->event_pool.back().first;
-      ev.b = w->event_pool.back().second;
-      w->event_pool.pop_back();
-    } else {
-      if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) {
-        on = false;
-        return;
-      }
-    }
-    ev.cls = cls;
-    ev.flop = flop * wk->flop_scale;
-    g_last_kn = -1;
-    g_last_sub = 0;
-    hipEventRecord(ev.a, st);
-  }
-  ~ProfScope() {
-    if (!on) return;
-    ev.kn = g_last_kn;
-    ev.sub = g_last_sub;
-    hipEventRecord(ev.b, st);
-    w->events.push_back(ev);
-  }
-};
-
 // The row-length rule of every launch: one row whose length the host knows takes it as a launch constant (no dependent load of
 // len[b] in every workgroup's prologue); a batch reads the device array (the kernels ignore len_const when len is non-null).
 struct RowLen {
@@ -52,8 +18,8 @@ static inline RowLen row_len(int B, int host_len, const int* dev_len, int mul = 
 }
 
 template <int K, int CI_C, int MB, int NB, int WN, int KS, int HALO, int EPI>
-static void launch_conv_inst(hipStream_t s, dim3 grid, const ConvArgs& a) {
-  kn_add(KN_CONV_MFMA);
+static void launch_conv_inst(ProfScope& ps, hipStream_t s, dim3 grid, const ConvArgs& a) {
+  ps.kernel(KN_CONV_MFMA, a.rows);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_mfma_kernel<K, CI_C, MB, NB, WN, KS, HALO, EPI>), grid, dim3(64 * WN * KS), 0, s, a);
 }
 
@@ -73,9 +39,10 @@ static void launch_conv_inst(hipStream_t s, dim3 grid, const ConvArgs& a) {
 //           128 x 128 form: +1.4 % on the class — finer granularity, four workgroups per CU.)
 enum TileShape { TILE_SMALL = 0, TILE_W128 = 1, TILE_NB2 = 2, TILE_TINY = 3, TILE_LAST = 3, TILE_M128 = 4 };
 
-// rb_conv: the call's option "rb_conv" and not MI355TTS_NO_RB_CONV (the upsamplers' continuous-stream tile)
+// rb_conv: the call's option "rb_conv" and not MI355TTS_NO_RB_CONV (the upsamplers' continuous-stream tile); ps: the caller's scope
+// (the launch is named, with its output rows as the sub-key, where its kernel is chosen)
 template <int K, int EPI>
-static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const ConvArgs& a, bool rb_conv) {
+static int launch_conv_k(ProfScope& ps, hipStream_t s, int MB, int shape, dim3 grid, const ConvArgs& a, bool rb_conv) {
   constexpr int HALO = conv_halo(K);
   constexpr int CI_SMALL = (K == 1) ? 64 : 32;
   constexpr bool PAIRED = (EPI == EPI_GATE || EPI == EPI_COUPLING);
@@ -84,7 +51,7 @@ static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const Conv
   if (a.x_ld % 4) return fail(MI355TTS_ERR_INVALID, "internal: activation row stride %d is not a multiple of 4", a.x_ld);
   if constexpr (EPI == EPI_LINEAR && K >= 3) {
     if (shape == TILE_M128) {
-      kn_add(KN_CONV_M128);
+      ps.kernel(KN_CONV_M128, a.rows);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_mfma_kernel<K, 16, 1, 2, 1, 1, HALO, EPI, 4>), grid, dim3(256), 0, s, a);
       return 0;
     }
@@ -97,29 +64,29 @@ static int launch_conv_k(hipStream_t s, int MB, int shape, dim3 grid, const Conv
           if (a.x2 && a.x3) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_conv_kernel<2, 4, EPI_UPSAMPLE, true>), grid, dim3(256), 0, s, a);
           else if (!a.x2) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_conv_kernel<2, 4, EPI_UPSAMPLE, false>), grid, dim3(256), 0, s, a);
           if ((a.x2 && a.x3) || !a.x2) {
-            kn_add(KN_RB_CONV);
+            ps.kernel(KN_RB_CONV, a.rows);
             return 0;
           }
         }
       }
-      kn_add(KN_CONV_M128);
+      ps.kernel(KN_CONV_M128, a.rows);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_mfma_kernel<K, 16, 1, 2, 1, 1, HALO, EPI, 4>), grid, dim3(256), 0, s, a);
       return 0;
     }
   }
   if (shape == TILE_M128) return fail(MI355TTS_ERR_INVALID, "internal: the 128-row tile is a ResBlock conv / upsampler shape");
   if (MB == 1) {
-    if (shape == TILE_TINY) launch_conv_inst<K, 64, 1, 1, 1, 8, HALO, EPI>(s, grid, a);
-    else if (shape == TILE_SMALL) launch_conv_inst<K, CI_SMALL, 1, 1, 2, 4, HALO, EPI>(s, grid, a);
-    else if (shape == TILE_W128) launch_conv_inst<K, 32, 1, 2, 2, 4, HALO, EPI>(s, grid, a);
-    else launch_conv_inst<K, 16, 1, 2, 4, 2, HALO, EPI>(s, grid, a);
+    if (shape == TILE_TINY) launch_conv_inst<K, 64, 1, 1, 1, 8, HALO, EPI>(ps, s, grid, a);
+    else if (shape == TILE_SMALL) launch_conv_inst<K, CI_SMALL, 1, 1, 2, 4, HALO, EPI>(ps, s, grid, a);
+    else if (shape == TILE_W128) launch_conv_inst<K, 32, 1, 2, 2, 4, HALO, EPI>(ps, s, grid, a);
+    else launch_conv_inst<K, 16, 1, 2, 4, 2, HALO, EPI>(ps, s, grid, a);
     return 0;
   }
   if constexpr (!PAIRED) {
-    if (shape == TILE_TINY) launch_conv_inst<K, 64, 2, 1, 1, 8, HALO, EPI>(s, grid, a);
-    else if (shape == TILE_SMALL) launch_conv_inst<K, CI_SMALL, 2, 1, 2, 4, HALO, EPI>(s, grid, a);
+    if (shape == TILE_TINY) launch_conv_inst<K, 64, 2, 1, 1, 8, HALO, EPI>(ps, s, grid, a);
+    else if (shape == TILE_SMALL) launch_conv_inst<K, CI_SMALL, 2, 1, 2, 4, HALO, EPI>(ps, s, grid, a);
     else if (shape == TILE_W128) return fail(MI355TTS_ERR_INVALID, "internal: the 128-column tile is one m-tile high");
-    else launch_conv_inst<K, 16, 2, 2, 4, 2, HALO, EPI>(s, grid, a);
+    else launch_conv_inst<K, 16, 2, 2, 4, 2, HALO, EPI>(ps, s, grid, a);
     return 0;
   }
   return fail(MI355TTS_ERR_INVALID, "paired epilogues run on 32-row tiles (MB == 1)");
@@ -308,9 +275,9 @@ static int plan_conv(const CallOptions& o, const DevConv& c, ConvArgs a, int epi
 
 // the f32 tile of plan `p` for one epilogue and the tap counts it is built for
 template <int EPI, int... Ks>
-static int launch_conv_taps(const ConvPlan& p, const char* unsupported, hipStream_t s, bool rb_conv) {
+static int launch_conv_taps(ProfScope& ps, const ConvPlan& p, const char* unsupported, hipStream_t s, bool rb_conv) {
   int rc = 0;
-  if (!switch_const<Ks...>(p.K, [&](auto k) { rc = launch_conv_k<decltype(k)::value, EPI>(s, p.MB, p.shape, p.grid, p.a, rb_conv); }))
+  if (!switch_const<Ks...>(p.K, [&](auto k) { rc = launch_conv_k<decltype(k)::value, EPI>(ps, s, p.MB, p.shape, p.grid, p.a, rb_conv); }))
     rc = fail(MI355TTS_ERR_INVALID, unsupported, p.K);
   return rc;
 }
@@ -318,11 +285,9 @@ static int run_plan(mi355tts_ctx* ctx, Worker* w, const ConvPlan& p, hipStream_t
   if (p.empty) return 0;
   hipStream_t s = stream ? stream : w->stream;
   ProfScope ps(ctx, w, p.cls, p.flop, s);
-  g_last_sub = p.a.rows;
   const bool rb_conv = w->opt.rb_conv && !w->opt.env.rb_conv_off;
-  g_kn = w->quiet ? nullptr : ctx->kn;
   if (p.bf16) {
-    kn_add(KN_CONV_BF16);
+    ps.kernel(KN_CONV_BF16, p.a.rows);
     if (p.epi == EPI_UPSAMPLE) {
       if (p.K != 2) return fail(MI355TTS_ERR_INVALID, "bf16 upsampler needs two taps");
       return launch_bf16_k<2, EPI_UPSAMPLE>(p.shape, p.bf16, p.grid, s, p.a);
@@ -332,10 +297,10 @@ static int run_plan(mi355tts_ctx* ctx, Worker* w, const ConvPlan& p, hipStream_t
       rc = fail(MI355TTS_ERR_INVALID, "unsupported conv kernel size %d in bf16 mode", p.K);
     return rc;
   }
-  if (p.epi == EPI_LINEAR) return launch_conv_taps<EPI_LINEAR, 1, 3, 5, 7, 11>(p, "unsupported conv kernel size %d", s, rb_conv);
-  if (p.epi == EPI_GATE) return launch_conv_taps<EPI_GATE, 3, 5>(p, "unsupported WaveNet kernel size %d", s, rb_conv);
-  if (p.epi == EPI_COUPLING) return launch_conv_taps<EPI_COUPLING, 1>(p, "coupling conv must be 1x1", s, rb_conv);
-  return launch_conv_taps<EPI_UPSAMPLE, 1, 2, 3>(p, "unsupported upsample taps %d", s, rb_conv);
+  if (p.epi == EPI_LINEAR) return launch_conv_taps<EPI_LINEAR, 1, 3, 5, 7, 11>(ps, p, "unsupported conv kernel size %d", s, rb_conv);
+  if (p.epi == EPI_GATE) return launch_conv_taps<EPI_GATE, 3, 5>(ps, p, "unsupported WaveNet kernel size %d", s, rb_conv);
+  if (p.epi == EPI_COUPLING) return launch_conv_taps<EPI_COUPLING, 1>(ps, p, "coupling conv must be 1x1", s, rb_conv);
+  return launch_conv_taps<EPI_UPSAMPLE, 1, 2, 3>(ps, p, "unsupported upsample taps %d", s, rb_conv);
 }
 
 static int launch_conv(mi355tts_ctx* ctx, Worker* w, const DevConv& c, ConvArgs a, int epi, int B, int n_max, int cls,
@@ -346,28 +311,30 @@ static int launch_conv(mi355tts_ctx* ctx, Worker* w, const DevConv& c, ConvArgs 
 }
 
 // ---- grouped launch: the same-geometry convs of the MRF chains of a stage in ONE launch
-template <int K0, int K1, int K2, int CI_C, int MB, int NB, int WN, int KS>
-static void launch_group_inst(hipStream_t s, dim3 grid, const ConvGroupArgs& g) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_group_kernel<K0, K1, K2, CI_C, MB, NB, WN, KS, conv_halo(K0), conv_halo(K1), conv_halo(K2)>),
-                     grid, dim3(64 * WN * KS), 0, s, g);
+// The f32 tiles that have a grouped kernel — the tile shapes the batch-1 ... batch-8 ResBlock launches of the shipped vocoders
+// use — with conv_group_kernel's template arguments; 64 x WM x WN x KS threads.  (MB 0: the 128-row tile, whatever the plan's
+// MB says: 16-channel chunks, one time-wave: <= 128 VGPRs, four 4-wave workgroups per CU.  The compiler emits the kernels in the
+// reverse of this order.)
+struct GroupTile {
+  int shape, MB, CI_C, MBT, NB, WN, KS, WM;
+};
+constexpr GroupTile GROUP_TILES[6] = {{TILE_M128, 0, 16, 1, 2, 1, 1, 4}, {TILE_NB2, 2, 16, 2, 2, 4, 2, 1},  {TILE_W128, 1, 32, 1, 2, 2, 4, 1},
+                                      {TILE_SMALL, 2, 32, 2, 1, 2, 4, 1}, {TILE_TINY, 1, 64, 1, 1, 1, 8, 1}, {TILE_TINY, 2, 64, 2, 1, 1, 8, 1}};
+// index into GROUP_TILES of a plan's (shape, MB), -1 = this tile has no grouped kernel
+static int group_tile(int shape, int MB) {
+  for (int i = 0; i < 6; ++i)
+    if (GROUP_TILES[i].shape == shape && (GROUP_TILES[i].MB == MB || GROUP_TILES[i].MB == 0)) return i;
+  return -1;
 }
+// tile: a GROUP_TILES index (run_group has checked that there is one)
 template <int K0, int K1, int K2>
-static int launch_group_k(hipStream_t s, int MB, int shape, dim3 grid, const ConvGroupArgs& g) {
-  kn_add(KN_CONV_GROUP);
-  // the tile shapes the batch-1 ... batch-8 ResBlock launches of the shipped vocoders use
-  if (shape == TILE_TINY && MB == 2) launch_group_inst<K0, K1, K2, 64, 2, 1, 1, 8>(s, grid, g);
-  else if (shape == TILE_TINY && MB == 1) launch_group_inst<K0, K1, K2, 64, 1, 1, 1, 8>(s, grid, g);
-  else if (shape == TILE_SMALL && MB == 2) launch_group_inst<K0, K1, K2, 32, 2, 1, 2, 4>(s, grid, g);
-  else if (shape == TILE_W128 && MB == 1) launch_group_inst<K0, K1, K2, 32, 1, 2, 2, 4>(s, grid, g);
-  else if (shape == TILE_NB2 && MB == 2) launch_group_inst<K0, K1, K2, 16, 2, 2, 4, 2>(s, grid, g);
-  else if (shape == TILE_M128)  // 16-channel chunks, one time-wave: <= 128 VGPRs, four 4-wave workgroups per CU
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_group_kernel<K0, K1, K2, 16, 1, 2, 1, 1, conv_halo(K0), conv_halo(K1), conv_halo(K2), 4>),
-                       grid, dim3(256), 0, s, g);
-  else {
-    if (g_kn) g_kn[KN_CONV_GROUP].fetch_sub(1, std::memory_order_relaxed);
-    return 1;
-  }
-  return 0;
+static void launch_group_k(ProfScope& ps, hipStream_t s, int tile, dim3 grid, const ConvGroupArgs& g) {
+  ps.kernel(KN_CONV_GROUP, g.c[0].rows);
+  switch_const<0, 1, 2, 3, 4, 5>(tile, [&](auto i) {
+    constexpr GroupTile t = GROUP_TILES[decltype(i)::value];
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_group_kernel<K0, K1, K2, t.CI_C, t.MBT, t.NB, t.WN, t.KS, conv_halo(K0), conv_halo(K1), conv_halo(K2), t.WM>),
+                       grid, dim3(64 * t.WM * t.WN * t.KS), 0, s, g);
+  });
 }
 // Returns 0 = launched as one group, 1 = not groupable (caller launches the members one by one), < 0 = error.
 // a member of a grouped launch the continuous-stream tile (rb_conv.h) covers: a plain ResBlock conv — bias, optional residual
@@ -452,12 +419,10 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* const* plans,
   std::copy(lay.off, lay.off + 4, g.off);
   const dim3 grid(g.off[3], 1, p0.grid.z);
   const bool taps_ok = lay.k1173 || lay.k753;
-  g_kn = w->quiet ? nullptr : ctx->kn;
   if (p0.bf16) {
     if (!taps_ok) return 1;
     ProfScope ps(ctx, w, p0.cls, flop, s);
-    g_last_sub = p0.a.rows;
-    kn_add(KN_CONV_BF16_GROUP);
+    ps.kernel(KN_CONV_BF16_GROUP, p0.a.rows);
     bool known = false;
     switch_taps(lay, [&](auto k0, auto k1, auto k2) {
       constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value, K2 = decltype(k2)::value;
@@ -470,11 +435,9 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* const* plans,
     });
     return known ? 0 : fail(MI355TTS_ERR_INVALID, "internal: bf16 tile %d", p0.shape);
   }
-  const bool shape_ok = (p0.shape == TILE_TINY) || (p0.shape == TILE_SMALL && p0.MB == 2) || (p0.shape == TILE_W128 && p0.MB == 1) ||
-                        (p0.shape == TILE_NB2 && p0.MB == 2) || p0.shape == TILE_M128;
-  if (!shape_ok || !taps_ok) return 1;
+  const int tile = group_tile(p0.shape, p0.MB);
+  if (tile < 0 || !taps_ok) return 1;
   ProfScope ps(ctx, w, p0.cls, flop, s);
-  g_last_sub = p0.a.rows;
   // The 128-row tile with the continuous matrix stream (rb_conv.h; same bits as the chunked tile) where the launch is
   // what it was written for: plain ResBlock convs (bias, optional residual), taps 11 / 7 / 3, dilation within its halos.
   if (p0.shape == TILE_M128 && lay.k1173 && !o.env.rb_conv_off && o.rb_conv) {
@@ -499,22 +462,21 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* const* plans,
           group_offsets(tiles4, g.off);
           const dim3 grid4(g.off[3], 1, 1);
           if (snake) group_snake_order(g, ncu, 3 * ncu);
-          kn_add(KN_RB_GROUP_NB4);
+          ps.kernel(KN_RB_GROUP_NB4, p0.a.rows);
           hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3, 4>), grid4, dim3(256), 0, s, g);
           return 0;
         }
       }
       if (grid.z == 1 && snake) group_snake_order(g, ncu, 4 * ncu);  // four of these workgroups fit a CU (32 KB, <= 128 VGPRs)
-      kn_add(g.nseg ? KN_RB_GROUP_SNAKE : KN_RB_GROUP);
+      ps.kernel(g.nseg ? KN_RB_GROUP_SNAKE : KN_RB_GROUP, p0.a.rows);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3>), grid, dim3(256), 0, s, g);
       return 0;
     }
   }
-  int rc = 1;
   switch_taps(lay, [&](auto k0, auto k1, auto k2) {
-    rc = launch_group_k<decltype(k0)::value, decltype(k1)::value, decltype(k2)::value>(s, p0.MB, p0.shape, grid, g);
+    launch_group_k<decltype(k0)::value, decltype(k1)::value, decltype(k2)::value>(ps, s, tile, grid, g);
   });
-  return rc;
+  return 0;
 }
 
 // Tiles of the fused pair kernels by channel count (32, 64): CB 32-channel row blocks; f32 (resblock_pair.h) NB column blocks
@@ -591,12 +553,10 @@ static void plan_pair(const CallOptions& o, const DevConv& c1, const DevConv& c2
 }
 static int run_pair(mi355tts_ctx* ctx, Worker* w, const PairPlan& p, hipStream_t s) {
   ProfScope ps(ctx, w, KC_RESBLOCK, p.flop, s);
-  g_last_sub = p.C;
   const PairArgs& a = p.a;
   const dim3 grid = p.grid;
-  g_kn = w->quiet ? nullptr : ctx->kn;
   const bool rb = w->opt.rb_pair && p.rb;  // the 4-wave tile without a k-split (rb_pair.h): same tiles and arguments
-  kn_add(p.bf16 ? KN_PAIR_BF16 : rb ? KN_RB_PAIR : KN_PAIR);
+  ps.kernel(p.bf16 ? KN_PAIR_BF16 : rb ? KN_RB_PAIR : KN_PAIR, p.C);
   const bool known = switch_const<3, 7, 11>(p.K, [&](auto k) {
     pair_tile_dispatch(p.C, [&](auto c) {
       constexpr int K = decltype(k)::value;
@@ -630,10 +590,8 @@ static int run_pair_group(mi355tts_ctx* ctx, Worker* w, const PairPlan* const* p
   std::copy(lay.off, lay.off + 4, g.off);
   const dim3 grid(g.off[3], 1, p0.grid.z);
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
-  g_last_sub = p0.C;
-  g_kn = w->quiet ? nullptr : ctx->kn;
   const bool rb = w->opt.rb_pair && p0.rb;
-  kn_add(p0.bf16 ? KN_PAIR_BF16_GROUP : rb ? KN_RB_PAIR_GROUP : KN_PAIR_GROUP);
+  ps.kernel(p0.bf16 ? KN_PAIR_BF16_GROUP : rb ? KN_RB_PAIR_GROUP : KN_PAIR_GROUP, p0.C);
   pair_tile_dispatch(p0.C, [&](auto c) {
     constexpr PairTile t = PAIR_TILES[decltype(c)::value];
     if (p0.bf16 == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, t.CB, t.WN16, t.NB16, 3>), grid, dim3(64 * t.CB * t.WN16), 0, s, g);
@@ -671,16 +629,16 @@ static int run_mrf_small(mi355tts_ctx* ctx, Worker* w, const MrfStage& ms, const
   const dim3 grid(2 * ((Lmax + T - 1) / T), 1, B);  // two workgroups per tile
   ProfScope ps(ctx, w, KC_MRF_NARROW, 2.0 * ms.mac_per_col * (double)Lmax * B, s);
   if (ms.C == 16) {
-    kn_hit(ctx, KN_MRF_SMALL);
+    ps.kernel(KN_MRF_SMALL);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(mrf_small_kernel<16, T, 4, 3, 7, 11>), grid, dim3(256), 0, s, a);
   } else if (!w->opt.env.mrf8_off) {
     // 8 channels: the 4x4x1 16-block MFMA (no padding rows), its own fragment packing; two waves per tile
     a.w = arena + ms.w8_off;
     a.tab = reinterpret_cast<const int*>(arena + ms.t8_off);
-    kn_hit(ctx, KN_MRF8);
+    ps.kernel(KN_MRF8);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(mrf8_kernel<T, 3, 7, 11>), grid, dim3(128), 0, s, a);
   } else {
-    kn_hit(ctx, KN_MRF_SMALL);
+    ps.kernel(KN_MRF_SMALL);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(mrf_small_kernel<8, T, 4, 3, 7, 11>), grid, dim3(256), 0, s, a);
   }
   return 0;
@@ -723,7 +681,7 @@ static int run_gate16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const Conv
     known = switch_const<1, 2, 3, 4, 6, 8>(c.g16_J, [&](auto j) { gate16_launch<decltype(k)::value, decltype(j)::value>(wide, grid, s, g); });
   });
   if (!known) return 1;
-  kn_hit(ctx, wide ? KN_GATE16_WIDE : KN_GATE16);
+  ps.kernel(wide ? KN_GATE16_WIDE : KN_GATE16);
   return 0;
 }
 
@@ -793,7 +751,7 @@ static int run_lin16(mi355tts_ctx* ctx, Worker* w, const DevConv& c, const ConvA
     constexpr Lin16Shape t = LIN16_SHAPES[decltype(i)::value];
     hipLaunchKernelGGL(HIP_KERNEL_NAME(lin16_kernel<t.K, t.J, t.NBLK, t.LN, t.RTW>), grid, dim3(512), 0, w->stream, g);
   });
-  kn_hit(ctx, wide ? KN_LIN16_WIDE : ln ? KN_LIN16_LN : KN_LIN16);
+  ps.kernel(wide ? KN_LIN16_WIDE : ln ? KN_LIN16_LN : KN_LIN16);
   return 0;
 }
 

@@ -1020,96 +1020,25 @@ extern "C" int mi355tts_coalesce_stats(mi355tts_ctx* ctx, int64_t* passes, int64
 extern "C" int mi355tts_profile_reset(mi355tts_ctx* ctx) {
   if (!ctx) return fail(MI355TTS_ERR_INVALID, "ctx null");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  for (auto& a : ctx->prof) a = mi355tts_ctx::Acc();
-  for (auto& m : ctx->prof_kn) m.clear();
-  for (auto& k : ctx->kn) k.store(0, std::memory_order_relaxed);
+  profile_reset(*ctx);
   return 0;
 }
-// {"kernel name": launches, ...} since the last mi355tts_profile_reset — counted whether profiling is on or not
+// the three renderings of the launch accounting and the event-overhead probe: host_profile.h
 extern "C" int mi355tts_kernel_counts_json(mi355tts_ctx* ctx, char* buf, int cap) {
   if (!ctx || !buf || cap <= 2) return fail(MI355TTS_ERR_INVALID, "bad argument");
-  std::string s = "{";
-  for (int i = 0; i < KN_COUNT; ++i) {
-    char tmp[128];
-    std::snprintf(tmp, sizeof(tmp), "%s\"%s\": %lld", i ? ", " : "", kname_name[i], ctx->kn[i].load(std::memory_order_relaxed));
-    s += tmp;
-  }
-  s += "}";
-  if ((int)s.size() + 1 > cap) return fail(MI355TTS_ERR_TOO_SMALL, "kernel-count buffer too small");
-  std::memcpy(buf, s.c_str(), s.size() + 1);
-  return 0;
+  return copy_json(kernel_counts_json(*ctx), buf, cap, "kernel-count buffer too small");
 }
-// What the two event records of a ProfScope cost by themselves: `pairs` empty pairs (hipEventRecord a, hipEventRecord b,
-// nothing between) on an idle stream of this context's device, median elapsed in microseconds.  A profiled launch's event time
-// is its kernel's duration plus at least this (4.5 us on MI355X; rocprofv3's kernel durations do not contain it), so bench.py
-// reports its event-timed launch durations with and without it.
 extern "C" int mi355tts_profile_event_overhead(mi355tts_ctx* ctx, int pairs, double* us_out) {
   if (!ctx || !us_out || pairs < 1 || pairs > 4096) return fail(MI355TTS_ERR_INVALID, "bad argument");
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipStream_t st = nullptr;
-  HIPCHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  std::vector<float> el;
-  hipEvent_t a = nullptr, b = nullptr;
-  hipError_t e = hipEventCreate(&a);
-  if (e == hipSuccess) e = hipEventCreate(&b);
-  for (int i = 0; i < pairs + 3 && e == hipSuccess; ++i) {
-    hipEventRecord(a, st);
-    hipEventRecord(b, st);
-    e = hipStreamSynchronize(st);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-    if (i >= 3) el.push_back(ms);  // (the first records of a new stream are slower)
-  }
-  if (a) hipEventDestroy(a);
-  if (b) hipEventDestroy(b);
-  hipStreamDestroy(st);
-  if (e != hipSuccess) return fail(MI355TTS_ERR_HIP, "event overhead: %s", hipGetErrorString(e));
-  std::sort(el.begin(), el.end());
-  *us_out = 1000.0 * (double)el[el.size() / 2];
-  return 0;
+  return profile_event_overhead(ctx->device, pairs, us_out);
 }
-// The same sums per kernel NAME and launch sub-key (output rows of a conv launch / channels of a fused pair): {"class": {"name/sub":
-// {"launches": n, "ms": t, "flop": f}, ...}, ...}; launches of kernels without a counted name are filed under "-".  bench.py's
-// `roofline.by_kernel` (a driver record on an unknown box can then be compared with the builder's kernel by kernel).
 extern "C" int mi355tts_profile_kernels_json(mi355tts_ctx* ctx, char* buf, int cap) {
   if (!ctx || !buf || cap <= 2) return fail(MI355TTS_ERR_INVALID, "bad argument");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  std::string s = "{";
-  bool first_cls = true;
-  for (int i = 0; i < KC_COUNT; ++i) {
-    if (ctx->prof_kn[i].empty()) continue;
-    s += first_cls ? "\"" : ", \"";
-    first_cls = false;
-    s += kclass_name[i];
-    s += "\": {";
-    bool first = true;
-    for (const auto& kv : ctx->prof_kn[i]) {
-      char tmp[256];
-      const int kn = kv.first.first;
-      std::snprintf(tmp, sizeof(tmp), "%s\"%s/%d\": {\"launches\": %lld, \"ms\": %.6f, \"flop\": %.6e}", first ? "" : ", ",
-                    kn >= 0 && kn < KN_COUNT ? kname_name[kn] : "-", kv.first.second, kv.second.launches, kv.second.ms, kv.second.flop);
-      s += tmp;
-      first = false;
-    }
-    s += "}";
-  }
-  s += "}";
-  if ((int)s.size() + 1 > cap) return fail(MI355TTS_ERR_TOO_SMALL, "profile buffer too small");
-  std::memcpy(buf, s.c_str(), s.size() + 1);
-  return 0;
+  return copy_json(profile_kernels_json(*ctx), buf, cap, "profile buffer too small");
 }
 extern "C" int mi355tts_profile_json(mi355tts_ctx* ctx, char* buf, int cap) {
   if (!ctx || !buf || cap <= 2) return fail(MI355TTS_ERR_INVALID, "bad argument");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  std::string s = "{";
-  for (int i = 0; i < KC_COUNT; ++i) {
-    char tmp[256];
-    std::snprintf(tmp, sizeof(tmp), "%s\"%s\": {\"launches\": %lld, \"ms\": %.6f, \"flop\": %.6e}", i ? ", " : "",
-                  kclass_name[i], ctx->prof[i].launches, ctx->prof[i].ms, ctx->prof[i].flop);
-    s += tmp;
-  }
-  s += "}";
-  if ((int)s.size() + 1 > cap) return fail(MI355TTS_ERR_TOO_SMALL, "profile buffer too small");
-  std::memcpy(buf, s.c_str(), s.size() + 1);
-  return 0;
+  return copy_json(profile_json(*ctx), buf, cap, "profile buffer too small");
 }

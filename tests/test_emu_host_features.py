@@ -782,3 +782,110 @@ def test_four_wave_pair_kernel_against_the_k_split_one(emu_engine, monkeypatch):
                 assert np.all(new[b, f * hp.hop:] == 0)
     finally:
         emu_engine.unload(v)
+
+
+# `mi355tts_kernel_counts_json`'s keys in its order (the device tests and bench.py's `roofline.by_kernel` index by these strings)
+KERNEL_NAMES = [
+    "conv_mfma_kernel", "conv_mfma_kernel.m128", "conv_group_kernel", "rb_conv_kernel", "rb_group_kernel", "rb_group_kernel.snake",
+    "resblock_pair_kernel", "pair_group_kernel", "rb_pair_kernel", "rb_pair_group_kernel", "conv_bf16_kernel", "conv_bf16_group_kernel",
+    "pair_bf16_kernel", "pair_bf16_group_kernel", "mrf_small_kernel", "mrf8_kernel", "gate16_kernel", "gate16_kernel.wide", "lin16_kernel",
+    "lin16_kernel.ln", "lin16_kernel.wide", "glow_tail_kernel", "oproj_ln_kernel", "post_conv_kernel", "wave_out_kernel",
+    "attention_mfma_kernel", "conv_f16_kernel", "conv_f16_group_kernel", "post_f16_kernel", "pack_octets_kernel", "pair_f16_group_kernel",
+    "wn_f16_kernel", "rb_group_kernel.nb4", "griffin_lim_mag_kernel", "griffin_lim_init_kernel", "griffin_lim_iter_kernel",
+    "griffin_lim_out_kernel", "griffin_lim_int16_kernel", "glow_fwd_kernel", "align_score_kernel", "align_path_kernel",
+    "mel_analysis_kernel", "attention_mfma_kernel.p768", "attention_kernel",
+]
+
+
+def test_kernel_name_table_is_pinned(emu_engine):
+    assert len(KERNEL_NAMES) == 44 and list(emu_engine.kernel_counts().keys()) == KERNEL_NAMES
+
+
+def counted_and_timed(eng, call):
+    """`call()` with profiling on, behind a reset: (kernel_counts, launches per name summed over the classes and sub-keys of
+    profile_kernels).  Per class, the entries of profile_kernels add up to profile()'s launches (kernels without a counted
+    name are filed under "-": timed in their class, no name to count)."""
+    eng.set_profiling(True)
+    try:
+        eng.profile_reset()
+        call()
+        prof, kern, names = eng.profile(), eng.profile_kernels(), eng.kernel_counts()
+    finally:
+        eng.set_profiling(False)
+    timed = {}
+    for cls, acc in prof.items():
+        entries = kern.get(cls, {})
+        assert sum(e["launches"] for e in entries.values()) == acc["launches"], (cls, acc, entries)
+        for key, e in entries.items():
+            name = key.rsplit("/", 1)[0]
+            if name != "-":
+                timed[name] = timed.get(name, 0) + e["launches"]
+    assert set(kern) <= set(prof)
+    return names, timed
+
+
+def check_counted_means_timed(eng, g, v, num_symbols, num_mels, lens=(15, 13, 7, 21), frames=33):
+    """A launch that `kernel_counts` counts is the launch `profile_kernels` times, under the same name: a batch-1 fused call
+    (lens[0] ids), a ragged batch (lens[1:]), a vocoder call with both output tails (option `voc_out`).  Then the batch-1 call
+    with profiling off: the same launches counted, none timed."""
+    rng = np.random.default_rng(53)
+    rows = [synthetic.synthetic_phoneme_ids(rng, n, num_symbols) for n in lens]
+    mel = eng.mel_from_numpy((0.5 + 0.1 * rng.standard_normal((1, num_mels, frames))).astype(np.float32))
+    one = lambda: eng.synthesize(g, v, rows[0], 0.667, 1.0, seed=3)  # noqa: E731
+    calls = [one, lambda: eng.synthesize(g, v, rows[1:], 0.667, 1.0, seed=3), lambda: eng.hifigan_infer(v, mel)]
+    totals = []
+    try:
+        for form in (1, 0):
+            eng.set_option("voc_out", form)
+            for call in calls if form else calls[2:]:
+                names, timed = counted_and_timed(eng, call)
+                assert timed and timed == {k: n for k, n in names.items() if n}, (form, names, timed)
+                assert names["post_conv_kernel"] == form and names["wave_out_kernel"] == form
+                totals.append(sum(names.values()))
+    finally:
+        eng.set_option("voc_out", 1)
+    eng.profile_reset()
+    one()
+    assert sum(eng.kernel_counts().values()) == totals[0]
+    assert all(acc["launches"] == 0 for acc in eng.profile().values()) and eng.profile_kernels() == {}
+    mel.free()
+
+
+def test_counted_means_timed_under_the_same_name(emu_engine, tiny):
+    check_counted_means_timed(emu_engine, tiny["g"], tiny["v"], HP.TINY_GLOW.num_symbols, HP.TINY_HIFIGAN.num_mels)
+
+
+def test_counts_of_two_contexts_on_one_thread(emu_library):
+    """Engine A runs grouped vocoder launches (run_group, run_pair_group: helpers that count without a context argument) and is
+    destroyed; the same call on engine B, on the same thread, counts what it counts on a fresh engine, and times nothing."""
+    from larynx_amd.engine import Engine
+
+    hp = HP.HifiGanHParams(upsample_rates=(2, 2), upsample_kernel_sizes=(4, 4), upsample_initial_channel=256,
+                           resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3), (1, 3), (1, 5)), num_mels=16)
+    sd = synthetic.make_hifigan_state_dict(hp, seed=71)
+    melin = (np.random.default_rng(72).standard_normal((1, hp.num_mels, 23)) * 2).astype(np.float32)
+
+    def run(eng):
+        v = eng.load_hifigan(hp, sd)
+        eng.profile_reset()
+        wav, _ = eng.hifigan_infer(v, eng.mel_from_numpy(melin))
+        return wav, eng.kernel_counts(), eng.profile(), eng.profile_kernels()
+
+    a, b = Engine(device=0, library_path=emu_library), Engine(device=0, library_path=emu_library)
+    try:
+        wav_a, counts_a, _, _ = run(a)
+        assert counts_a["conv_group_kernel"] > 0 and counts_a["pair_group_kernel"] > 0, counts_a
+        assert not any(b.kernel_counts().values())
+        a.close()
+        wav_b, counts_b, prof_b, kern_b = run(b)
+    finally:
+        a.close()
+        b.close()
+    fresh = Engine(device=0, library_path=emu_library)
+    try:
+        wav_f, counts_f, prof_f, kern_f = run(fresh)
+    finally:
+        fresh.close()
+    assert counts_b == counts_f == counts_a
+    assert prof_b == prof_f and all(acc["launches"] == 0 for acc in prof_b.values()) and kern_b == kern_f == {}
+    assert np.array_equal(wav_b, wav_f) and np.array_equal(wav_b, wav_a)

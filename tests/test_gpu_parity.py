@@ -238,6 +238,39 @@ def test_host_feature_checks_on_the_device(gpu_engine):
     gpu_engine.reserve(4, g, vh, max_batch=1, max_ids=128, max_frames=1024, denoiser=True, max_pad_samples=22050)
 
 
+def test_counted_launches_are_timed_under_the_same_name_on_the_device(gpu_engine):
+    """`kernel_counts` and `profile_kernels` agree name for name on the real build (the emulator suite's check): the fused call
+    and the vocoder at `test_host_feature_checks_on_the_device`'s shapes, then 'high' at 150 frames — the smallest input of
+    this file that reaches the grouped and the fused-pair runners."""
+    from tests.test_emu_host_features import check_counted_means_timed
+
+    (_, g), (_, v) = models(gpu_engine, HP.LJSPEECH, HP.HIFIGAN_MEDIUM)
+    check_counted_means_timed(gpu_engine, g, v, HP.LJSPEECH.num_symbols, HP.HIFIGAN_MEDIUM.num_mels, lens=(40, 40, 17, 63), frames=150)
+    _, (_, vh) = models(gpu_engine, HP.LJSPEECH, HP.HIFIGAN_HIGH)
+    check_counted_means_timed(gpu_engine, g, vh, HP.LJSPEECH.num_symbols, HP.HIFIGAN_HIGH.num_mels, lens=(40, 40, 17, 63), frames=150)
+    names = gpu_engine.kernel_counts()  # (the last call of the check: the batch-1 fused call, profiling off)
+    assert names["rb_group_kernel"] + names["rb_group_kernel.snake"] + names["conv_group_kernel"] > 0, names
+    assert names["rb_pair_group_kernel"] + names["pair_group_kernel"] > 0, names
+
+
+def test_dispatch_selfcheck_is_neither_counted_nor_timed():
+    """The self-check's own grouped launches (a `quiet` worker) on a context that profiles: the check runs with the first
+    'high'-class load, and no kernel name is counted and no class has a timed launch afterwards."""
+    from larynx_amd.engine import Engine
+
+    eng = Engine(device=0)
+    try:
+        eng.set_profiling(True)
+        eng.profile_reset()
+        eng.load_hifigan(HP.HIFIGAN_HIGH, synthetic.make_hifigan_state_dict(HP.HIFIGAN_HIGH, seed=1234))
+        r = eng.dispatch_selfcheck()
+        assert r["state"] in ("snake order kept", "snake order switched off"), r
+        assert not any(eng.kernel_counts().values()), eng.kernel_counts()
+        assert all(acc["launches"] == 0 for acc in eng.profile().values()) and eng.profile_kernels() == {}
+    finally:
+        eng.close()
+
+
 def test_standard_utterance_properties(gpu_engine):
     """BASELINE config 2 at full size (P=120): size-independent checks — frame
     count equals the duration sum, bounded tanh output, int16 peak-normalised,
