@@ -353,6 +353,56 @@ int mi355tts_mel_from_audio(mi355tts_ctx* ctx, int model, const float* wav_f32, 
  * mel can feed mi355tts_glow_align with MI355TTS_IN_DEVICE without a host round trip. */
 int mi355tts_mel_plane(const mi355tts_mel* mel, int which, const float** device_ptr, int* ld);
 
+/* ---- resampling: the delivered rows at another sample rate --------------------
+ * Every voice produces 22 050 Hz audio; this delivers 8 / 16 / 24 / 44.1 / 48 kHz (or any other rational ratio) where the samples
+ * already are: ONE launch behind the vocoder, TWO with MI355TTS_PCM_NORMALIZE (csrc/resample.h).  The reference has no such
+ * step (larynx/server.py:211-217 writes whatever AudioSettings.sample_rate says).
+ * Rational resampling by up / down (coprime) with a caller-supplied symmetric prototype filter: only up, down and the
+ * prototype's half-length are parameters, the design is the caller's (larynx_amd.resample.design_lowpass: a Kaiser-windowed
+ * sinc) and the taps are passed in like any other table.
+ *   Prototype:     host array taps[2 H + 1], centre H (= half_len), given at the up-sampled rate.
+ *   Output length: a row of N input samples gives N_out = ceil(N * up / down) outputs; N = 0 gives 0.
+ *   Definition:    with c = n * down + H,
+ *                    y[n] = sum over i in [0, N) with 0 <= c - i * up <= 2 H of x[i] * taps[c - i * up].
+ *                  Samples outside [0, N) are zero: each row starts and ends from silence, with no state across calls.  Output n
+ *                  sits at input time n * down / up: zero delay, y[0] is aligned with x[0].  This is
+ *                  scipy.signal.resample_poly(x, up, down, window=taps / up).
+ *   Arithmetic:    all f32, one fma per term, one accumulator per output, starting from +0.  Term order: i DESCENDING from
+ *                  c div up, i.e. prototype index c mod up + t * up for t = 0, 1, .. ascending (the polyphase row of phase
+ *                  c mod up, T = ceil((2 H + 1) / up) taps, walked from its first entry).  Terms outside the row or the
+ *                  prototype add exact zeros.  Row b of a batch is bit-identical to its own batch-1 call; int16 input is
+ *                  converted as s * 2^-15 (exact) inside the launch and gives the bits of the equal f32 input; host and device
+ *                  pointers give the same bits.
+ * mi355tts_load_resampler: lays the prototype out as the polyphase table [phase][t] on the device; mi355tts_unload frees the model.
+ * mi355tts_resample_length: ceil(samples * up / down) for 0 <= samples <= 2^24; a negative status on error.
+ * mi355tts_resample: exactly one of in_f32 / in_i16 [B][in_ld] (host, or device with MI355TTS_IN_DEVICE) and at least one of
+ * out_f32 / out_i16 [B][out_ld] (host, or device with MI355TTS_OUT_DEVICE), as in mi355tts_mel_from_audio and
+ * mi355tts_griffin_lim_infer.  Row b holds samples[b] <= in_ld input samples (host array); every output row is zero-filled from
+ * its N_out up to out_ld; samples_out (host [B], or NULL) receives the rows' N_out.  The workspace grows on demand
+ * (mi355tts_reserve does not cover this call).
+ * int16 output (pcm_mode):
+ *   MI355TTS_PCM_SATURATE (0)   clamp(rintf(y * 32768), -32768, 32767).  The filter overshoots: a full-scale input saturates,
+ *                               so a delivered int16 stream (whose peak sits at 32767) re-sampled in this mode MAY CLIP.
+ *   MI355TTS_PCM_NORMALIZE (1)  the reference's audio_float_to_int16 (larynx/audio.py:118-125) applied to the row's N_out resampled
+ *                               samples: scale 32767 / max(0.01, max|y|), clip to +-32767, truncate toward zero — the rule and
+ *                               rounding the vocoder's own int16 rows get.  The mode of the sentence path: resample the FLOAT
+ *                               signal, then normalise; the peak lands on 32767 at the new rate and nothing clips.
+ * MI355TTS_ERR_INVALID with the reason (MI355TTS_ERR_NO_MODEL for an unknown id): null pointers; both inputs or neither; no
+ * output; up or down outside [1, 1024], or not coprime; half_len < 0; more than 128 taps per phase (ceil((2 H + 1) / up)); a
+ * non-finite tap; samples[b] outside [0, in_ld] or above 2^24; out_ld below the longest row's N_out; an unknown pcm_mode.
+ * Added in ABI version 2 (additive: the version number is unchanged). */
+typedef struct {
+  int32_t up, down; /* 1 .. 1024, coprime */
+  int32_t half_len; /* H >= 0: the prototype has 2 H + 1 taps, at most 128 per phase */
+} mi355tts_resampler_params;
+int mi355tts_load_resampler(mi355tts_ctx* ctx, const mi355tts_resampler_params* params, const float* taps, int* model_out);
+int64_t mi355tts_resample_length(mi355tts_ctx* ctx, int model, int64_t samples);
+#define MI355TTS_PCM_SATURATE 0
+#define MI355TTS_PCM_NORMALIZE 1
+int mi355tts_resample(mi355tts_ctx* ctx, int model, const float* in_f32, const int16_t* in_i16, const int64_t* samples, int B,
+                      int64_t in_ld, float* out_f32, int16_t* out_i16, int64_t out_ld, int pcm_mode, int64_t* samples_out,
+                      uint32_t flags);
+
 /* ---- fused call: replaces the model half of _sentence_task -------------------
  * (larynx/__init__.py:229-283: phonemes_to_mels -> mel transforms -> mels_to_audio -> pause
  * padding) with ONE call on one stream: arguments as in mi355tts_glow_infer +

@@ -7,6 +7,7 @@ HTTP server stay in Larynx; see INTEGRATION.md for the two edit points.
 """
 from __future__ import annotations
 
+import functools
 import logging
 import time
 import typing
@@ -33,7 +34,7 @@ _LOGGER = logging.getLogger("larynx_amd")
 
 __all__ = [
     "AudioSettings", "InferenceBackend", "TextToSpeechResult", "load_tts_model", "load_vocoder_model",
-    "sentence_task", "sentence_task_aligned", "phonemes_to_speech",
+    "sentence_task", "sentence_task_aligned", "sentence_task_at_rate", "phonemes_to_speech",
 ]
 
 
@@ -76,29 +77,66 @@ def sentence_task(text: str, phoneme_ids, audio_settings, tts_model, tts_setting
                      pause_before_ms, pause_after_ms)[0]
 
 
+def sentence_task_at_rate(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                          pause_before_ms: int = 0, pause_after_ms: int = 0, sample_rate: typing.Optional[int] = None) -> np.ndarray:
+    """`sentence_task` delivered at `sample_rate` Hz: the vocoder's FLOAT row, SSML pauses included, is resampled on the
+    device and normalised to int16 afterwards (`larynx_amd.resample`; the peak lands on 32767 at the new rate), n samples
+    becoming ceil(n * up / down).  `None`, or the voice's own rate, is `sentence_task`."""
+    return _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                     pause_before_ms, pause_after_ms, sample_rate)[0]
+
+
 def sentence_task_aligned(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
-                          pause_before_ms: int = 0, pause_after_ms: int = 0) -> typing.Tuple[np.ndarray, np.ndarray]:
+                          pause_before_ms: int = 0, pause_after_ms: int = 0,
+                          sample_rate: typing.Optional[int] = None) -> typing.Tuple[np.ndarray, np.ndarray]:
     """`sentence_task` that also returns where every phoneme id sounds: `(audio, spans)`, spans int64 [P, 2] in samples
     of `audio`, leading pause included (`larynx_amd.alignment.phoneme_spans`).  The TTS model must be one whose mels
     carry durations (`HipGlowTextToSpeech`); the audio is what `sentence_task` gives for the same settings.  With a
-    Griffin-Lim vocoder the spans are nominal frame positions (hop 256), see `phoneme_spans`."""
+    Griffin-Lim vocoder the spans are nominal frame positions (hop 256), see `phoneme_spans`.  With `sample_rate` (see
+    `sentence_task_at_rate`) the spans are positions in the delivered audio: both ends scaled by (s * up) // down."""
     settings = dict(tts_settings or {})
     settings["alignment"] = True
-    audio, mels, before = _sentence(text, phoneme_ids, audio_settings, tts_model, settings, vocoder_model, vocoder_settings,
-                                    pause_before_ms, pause_after_ms)
-    from .alignment import phoneme_spans
+    audio, mels, before, resampler = _sentence(text, phoneme_ids, audio_settings, tts_model, settings, vocoder_model,
+                                               vocoder_settings, pause_before_ms, pause_after_ms, sample_rate)
+    from .alignment import phoneme_spans, scale_spans
 
     durations = getattr(mels, "durations", None)
     if durations is None:
         raise ValueError("the text-to-speech model's mels carry no per-phoneme durations")
     hparams = getattr(vocoder_model, "hparams", None)
     hop = int(hparams.hop) if hparams is not None else 256  # Griffin-Lim: hard-wired 256 (larynx/audio.py:284,297)
-    return audio, phoneme_spans(durations[0], hop, pad_before=before)
+    spans = phoneme_spans(durations[0], hop, pad_before=before)
+    return audio, (spans if resampler is None else scale_spans(spans, resampler.up, resampler.down))
+
+
+def _resampler_for(vocoder_model, audio_settings, sample_rate):
+    """The cached `Resampler` from the voice's rate to `sample_rate`, or None where the voice's own rate is delivered."""
+    voice_rate = audio_settings.sample_rate if audio_settings is not None else 22050
+    if sample_rate is None or int(sample_rate) == int(voice_rate):
+        return None
+    engine = getattr(vocoder_model, "engine", None)
+    if engine is None:
+        raise ValueError("sample_rate: the vocoder has no HIP engine to resample on")
+    from .resample import get_resampler
+
+    return get_resampler(engine, voice_rate, sample_rate)
+
+
+def _float_row(vocoder_model, mels, vocoder_settings, before, after) -> np.ndarray:
+    """The vocoder's float signal with the SSML pauses in it: what is resampled BEFORE the int16 normalisation."""
+    padded = getattr(vocoder_model, "mels_to_float_padded", None)
+    if padded is not None:
+        return padded(mels, vocoder_settings, before, after)
+    audio = np.asarray(vocoder_model.mels_to_audio(mels, settings=vocoder_settings))
+    if audio.dtype.kind != "f":
+        raise ValueError("sample_rate: the vocoder delivers no float signal to resample")
+    return np.pad(audio.astype(np.float32, copy=False), pad_width=(before, after), constant_values=0)
 
 
 def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
-              pause_after_ms):
-    """-> (audio, the mels the vocoder consumed, leading pause in samples)"""
+              pause_after_ms, deliver_rate=None):
+    """-> (audio, the mels the vocoder consumed, leading pause in samples at the voice's rate, the `Resampler` the audio went
+    through or None)"""
     t0 = time.perf_counter()
     mels = tts_model.phonemes_to_mels(phoneme_ids, settings=tts_settings)
     tts_mels = mels
@@ -116,8 +154,14 @@ def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocode
     after = max(0, (pause_after_ms * sample_rate) // 1000)
     lead = before
     t2 = time.perf_counter()
+    resampler = _resampler_for(vocoder_model, audio_settings, deliver_rate)
     padded = getattr(vocoder_model, "mels_to_audio_padded", None)
-    if padded is not None and (before or after):
+    if resampler is not None:
+        # another rate: the float row, pauses included, resampled on the device and normalised to int16 there
+        audio = resampler.resample(_float_row(vocoder_model, mels, vocoder_settings, before, after), normalize=True)
+        sample_rate = resampler.rate_out
+        before = after = 0
+    elif padded is not None and (before or after):
         # SSML pauses written by the device's int16 kernel instead of np.pad (same samples)
         audio = padded(mels, vocoder_settings, before, after)
         before = after = 0
@@ -129,7 +173,7 @@ def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocode
     _LOGGER.debug("Real-time factor: %0.2f (infer=%0.2f sec, audio=%0.2f sec)", (t3 - t0) / dur if dur > 0 else 0.0, t3 - t0, dur)
     if before or after:
         audio = np.pad(audio, pad_width=(before, after), constant_values=0)
-    return audio, tts_mels, lead
+    return audio, tts_mels, lead, resampler
 
 
 def _ensure_pool_workers(executor, *models):
@@ -147,22 +191,29 @@ def _ensure_pool_workers(executor, *models):
 def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Sequence[int]]], tts_model, vocoder_model,
                        tts_settings: typing.Optional[SettingsType] = None,
                        vocoder_settings: typing.Optional[SettingsType] = None,
-                       executor: typing.Optional[Executor] = None, alignment: bool = False) -> typing.Iterable[TextToSpeechResult]:
+                       executor: typing.Optional[Executor] = None, alignment: bool = False,
+                       sample_rate: typing.Optional[int] = None) -> typing.Iterable[TextToSpeechResult]:
     """`text_to_speech` (`larynx/__init__.py:47-190`) from the point where gruut /
     phonemes2ids have produced ids: one task per sentence on an executor, results
     yielded in submission order.  `alignment`: every result also carries `phoneme_spans`, the start and end sample
-    of each phoneme id in its audio (`sentence_task_aligned`); the audio is the same either way."""
+    of each phoneme id in its audio (`sentence_task_aligned`); the audio is the same either way.  `sample_rate`: deliver
+    the audio at that rate instead of the voice's own (`sentence_task_at_rate`: resampled on the device, int16 of
+    ceil(n * up / down) samples, spans scaled to match); `None` or the voice's rate changes nothing."""
     own = executor is None
     executor = executor or ThreadPoolExecutor()
     _ensure_pool_workers(executor, tts_model, vocoder_model)
     try:
         audio_settings = getattr(tts_model, "audio_settings", None)
+        sr = audio_settings.sample_rate if audio_settings is not None else 22050
+        task = sentence_task_aligned if alignment else sentence_task
+        if _resampler_for(vocoder_model, audio_settings, sample_rate) is not None:  # (made here, once, before the pool needs it)
+            sr = int(sample_rate)
+            task = functools.partial(sentence_task_aligned if alignment else sentence_task_at_rate, sample_rate=sr)
         futures = []
         for text, ids in sentences:
-            fut = executor.submit(sentence_task_aligned if alignment else sentence_task, text, np.asarray(ids, np.int64), audio_settings, tts_model, tts_settings,
+            fut = executor.submit(task, text, np.asarray(ids, np.int64), audio_settings, tts_model, tts_settings,
                                   vocoder_model, vocoder_settings)
             futures.append((text, fut))
-        sr = audio_settings.sample_rate if audio_settings is not None else 22050
         for text, fut in futures:
             audio, spans = fut.result() if alignment else (fut.result(), None)
             yield TextToSpeechResult(text=text, audio=audio, sample_rate=sr, phoneme_spans=spans)

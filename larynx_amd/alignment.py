@@ -1,6 +1,7 @@
 """Phoneme timings: from the frames every phoneme id occupies (`MelBatch.durations`, the reference's
 `attn.sum(-1)`, glow_tts/models.py:350-354) to sample positions in the delivered audio; `align_spans` does the same for a
-mel that already exists (forced alignment, `HipGlowTextToSpeech.align`), `align_audio_spans` for a recording."""
+mel that already exists (forced alignment, `HipGlowTextToSpeech.align`), `align_audio_spans` for a recording, `scale_spans`
+moves spans to another sample rate."""
 from __future__ import annotations
 
 import numpy as np
@@ -35,3 +36,10 @@ def align_audio_spans(tts_model, phoneme_ids, audio, hop: int = 256, pad_before:
     sample positions in `audio`.  Under the "hifigan" framing frame j is centred on samples [j * hop, (j + 1) * hop), the
     relation `phoneme_spans` relies on; under "reference" frame j covers [j * hop, j * hop + 1024)."""
     return phoneme_spans(tts_model.align_audio(phoneme_ids, audio, settings, framing), hop, pad_before)
+
+
+def scale_spans(spans, up: int, down: int) -> np.ndarray:
+    """Sample positions at the voice's rate -> positions in audio resampled by `up / down` (`larynx_amd.resample`): both ends
+    of every span become (s * up) // down, so contiguous spans stay contiguous and no end lies past the ceil(n * up / down)
+    delivered samples."""
+    return (np.asarray(spans, np.int64) * int(up)) // int(down)

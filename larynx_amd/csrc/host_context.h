@@ -89,6 +89,7 @@ struct mi355tts_ctx : ProfSums {  // (the profiling switch, the launch sums and 
   std::map<int, std::shared_ptr<HifiModel>> hifi;
   std::map<int, std::shared_ptr<GriffinLimModel>> griffin;
   std::map<int, std::shared_ptr<AnalysisModel>> analysis;
+  std::map<int, std::shared_ptr<ResamplerModel>> resampler;
   // window + twiddles of the Griffin-Lim kernels (griffin_lim.h), built by the first load of a Griffin-Lim or analysis model
   float* gl_table = nullptr;
   float* hann_periodic = nullptr;  // the HiFi-GAN framing's window (mel_analysis.h), built by the first analysis load

@@ -404,6 +404,19 @@ struct AnalysisModel {
   }
 };
 
+// A resampler (resample.h) is its polyphase table: the caller's prototype laid out [phase p][t] = taps[p + t * up], rows of Tp
+// floats (T = ceil((2 H + 1) / up) rounded up to 4, zero-filled), made at load time
+struct ResamplerModel {
+  mi355tts_resampler_params p;
+  int device = 0;
+  int T = 0, Tp = 0;
+  float* table = nullptr;
+  ~ResamplerModel() {
+    DeviceScope ds(device);
+    if (table) hipFree(table);
+  }
+};
+
 static std::vector<std::pair<std::string, int64_t>> glow_manifest(const mi355tts_glow_hparams& h) {
   std::vector<std::pair<std::string, int64_t>> m;
   auto add = [&](const std::string& n, int64_t e) { m.emplace_back(n, e); };

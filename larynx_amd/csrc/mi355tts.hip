@@ -42,6 +42,7 @@
 #include "small_kernels.h"
 #include "griffin_lim.h"
 #include "mel_analysis.h"
+#include "resample.h"
 #include "align.h"
 #include "conv_f16.h"
 #include "pair_f16.h"
@@ -213,11 +214,13 @@ extern "C" int mi355tts_unload(mi355tts_ctx* ctx, int model) {
   std::shared_ptr<HifiModel> v;
   std::shared_ptr<GriffinLimModel> gl;
   std::shared_ptr<AnalysisModel> an;
+  std::shared_ptr<ResamplerModel> rs;
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
     auto gi = ctx->glow.find(model);
     auto li = ctx->griffin.find(model);
     auto ai = ctx->analysis.find(model);
+    auto ri = ctx->resampler.find(model);
     if (gi != ctx->glow.end()) {
       g = std::move(gi->second);
       ctx->glow.erase(gi);
@@ -227,6 +230,9 @@ extern "C" int mi355tts_unload(mi355tts_ctx* ctx, int model) {
     } else if (ai != ctx->analysis.end()) {
       an = std::move(ai->second);
       ctx->analysis.erase(ai);
+    } else if (ri != ctx->resampler.end()) {
+      rs = std::move(ri->second);
+      ctx->resampler.erase(ri);
     } else {
       auto vi = ctx->hifi.find(model);
       if (vi == ctx->hifi.end()) return fail(MI355TTS_ERR_NO_MODEL, "no model %d", model);
@@ -234,7 +240,7 @@ extern "C" int mi355tts_unload(mi355tts_ctx* ctx, int model) {
       ctx->hifi.erase(vi);
     }
   }
-  return 0;  // g / v / gl / an released outside the lock (hipFree synchronises the device)
+  return 0;  // g / v / gl / an / rs released outside the lock (hipFree synchronises the device)
 }
 
 // §8(e): the one collective of the path.  The library does not link RCCL: the entry point is resolved from the
@@ -451,6 +457,7 @@ extern "C" int mi355tts_mel_from_buffer(mi355tts_ctx* ctx, const float* mel, con
 #include "griffin_lim_forward.h"
 #include "align_forward.h"
 #include "analysis_forward.h"
+#include "resample_forward.h"
 
 // ------------------------------------------------------------------ fused call + reservation
 // ids -> int16/f32 waveform in ONE call on ONE worker: GlowTTS and the vocoder are queued

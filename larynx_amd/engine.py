@@ -627,6 +627,67 @@ class Engine:
         )
         return MelBatch(self, out.value)
 
+    # ---- resampling ----------------------------------------------------------------
+    def load_resampler(self, taps: np.ndarray, up: int, down: int) -> int:
+        """`mi355tts_load_resampler`: rational resampling by `up / down` (coprime) with the symmetric prototype `taps`
+        [2 H + 1] given at the up-sampled rate (`larynx_amd.resample.design_lowpass`).  `unload` frees it."""
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        if len(taps) % 2 != 1:
+            raise ValueError(f"taps must be [2 H + 1] (a symmetric prototype around its centre), got {len(taps)}")
+        p = ffi.ResamplerParamsC(int(up), int(down), len(taps) // 2)
+        model = C.c_int()
+        ffi.check(self.lib, self.lib.mi355tts_load_resampler(self._ctx, C.byref(p), taps.ctypes.data, C.byref(model)))
+        return int(model.value)
+
+    def resample_length(self, model: int, samples: int) -> int:
+        """`mi355tts_resample_length`: ceil(samples * up / down)."""
+        return int(ffi.check(self.lib, self.lib.mi355tts_resample_length(self._ctx, int(model), int(samples))))
+
+    def resample(self, model: int, audio: np.ndarray, samples=None, want_float: bool = True, want_int16: bool = False,
+                 normalize: bool = False):
+        """`audio`: float32 or int16 (read as s / 32768), [N] or [B, N], row b valid for `samples[b]` entries (default: all) ->
+        (f32 or None, i16 or None, samples_out int64 [B]); outputs are [B, max N_out] ([N_out] for a 1-D input), rows
+        zero-filled behind their N_out = ceil(N * up / down).  int16: `normalize=False` saturates
+        clamp(rint(y * 32768)); `normalize=True` is the reference's `audio_float_to_int16` on each resampled row."""
+        audio = np.asarray(audio)
+        if audio.dtype != np.int16:
+            audio = audio.astype(np.float32, copy=False)
+        audio = np.ascontiguousarray(audio)
+        flat = audio.ndim == 1
+        if flat:
+            audio = audio[None]
+        if audio.ndim != 2:
+            raise ValueError("audio: [N] or [B, N]")
+        if not (want_float or want_int16):
+            raise ValueError("nothing asked for: want_float and / or want_int16")
+        B, N = audio.shape
+        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        if n.shape != (B,):
+            raise ValueError("samples: one count per row")
+        ld = max([self.resample_length(model, int(v)) for v in n if 0 <= v <= N] or [0])
+        f32 = np.empty((B, ld), np.float32) if want_float else None
+        i16 = np.empty((B, ld), np.int16) if want_int16 else None
+        f_in, i_in = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
+        out = self.resample_raw(model, f_in, i_in, n, N, ffi.ptr(f32), ffi.ptr(i16), ld,
+                                ffi.PCM_NORMALIZE if normalize else ffi.PCM_SATURATE)
+        if flat:
+            f32, i16 = (None if f32 is None else f32[0]), (None if i16 is None else i16[0])
+        return f32, i16, out
+
+    def resample_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, out_f32_ptr, out_i16_ptr, out_ld: int,
+                     pcm_mode: int = 0, flags: int = 0) -> np.ndarray:
+        """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE), at least one output
+        pointer [B][out_ld] (device memory with ffi.OUT_DEVICE); returns the rows' output lengths, int64 [B]."""
+        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        out = np.zeros(len(n), np.int64)
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_resample(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+                                       out_f32_ptr, out_i16_ptr, int(out_ld), int(pcm_mode),
+                                       out.ctypes.data_as(C.POINTER(C.c_int64)), int(flags)),
+        )
+        return out
+
     # ---- single operators ------------------------------------------------------
     def conv1d(self, x, w, bias=None, dilation=1, in_slope=1.0, out_act=0, lens=None) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

@@ -85,6 +85,14 @@ FRAMING_REFERENCE = 1
 FRAMINGS = {"hifigan": FRAMING_HIFIGAN, "reference": FRAMING_REFERENCE}
 
 
+class ResamplerParamsC(C.Structure):
+    _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("half_len", C.c_int32)]
+
+
+PCM_SATURATE = 0  # MI355TTS_PCM_*: clamp(rint(y * 32768)) / the reference's audio_float_to_int16 on the resampled row
+PCM_NORMALIZE = 1
+
+
 class ProsodyC(C.Structure):
     """`mi355tts_prosody`: host arrays [B][ld] (or NULL): a rate per id, durations in, durations out."""
 
@@ -164,6 +172,12 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
         [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, C.POINTER(AudioSettingsC), C.c_uint32, C.POINTER(_VP)],
     ),
     "mi355tts_mel_plane": (C.c_int, [_VP, C.c_int, C.POINTER(_VP), C.POINTER(C.c_int)]),
+    "mi355tts_load_resampler": (C.c_int, [_VP, C.POINTER(ResamplerParamsC), _VP, C.POINTER(C.c_int)]),
+    "mi355tts_resample_length": (C.c_int64, [_VP, C.c_int, C.c_int64]),
+    "mi355tts_resample": (
+        C.c_int,
+        [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, _VP, _VP, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_uint32],
+    ),
     "mi355tts_synthesize": (
         C.c_int,
         [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,

@@ -82,3 +82,16 @@ class HipHiFiGanVocoder(VocoderModel):
         f32, _ = self.engine.hifigan_infer(self.model_id, batch, want_float=True, want_int16=False,
                                            denoiser_strength=denoiser_strength)
         return f32
+
+    def mels_to_float_padded(self, mels: ARRAY_OR_TENSOR, settings: typing.Optional[SettingsType] = None,
+                             pad_before: int = 0, pad_after: int = 0) -> np.ndarray:
+        """`mels_to_audio_padded` before `audio_float_to_int16`: the float row with its SSML pauses, what the sentence path
+        resamples when another sample rate is asked for (`larynx_amd.resample`)."""
+        strength = self.denoiser_strength
+        if settings:
+            strength = float(settings.get("denoiser_strength", strength))
+        batch = mels if isinstance(mels, MelBatch) else self.engine.mel_from_numpy(np.asarray(mels, np.float32))
+        f32, _ = self.engine.hifigan_infer(self.model_id, batch, want_float=True, want_int16=False,
+                                           denoiser_strength=max(strength, 0.0), pad_before=pad_before, pad_after=pad_after)
+        n = int(batch.frames[0]) * self.engine.hop(self.model_id) + int(pad_before) + int(pad_after)
+        return f32[0, :n] if batch.batch == 1 else f32
