@@ -1,7 +1,7 @@
 // mi355tts host runtime — forced alignment: mi355tts_glow_align (encoder as in a synthesis call, the decoder's flows FORWARDS,
 // mel -> z: glow_tts/models.py:191-209 with reverse=False, the scores, the best monotonic path: glow_tts/utils.py:59-96) and
 // the single operator mi355tts_op_maximum_path.  Kernels: align.h, glow_fwd_kernel (coltile.h).
-// (one translation unit: included once by mi355tts.hip, after glow_forward.h)
+// (one translation unit: included once by mi355tts.hip, after glow_forward.h; the call frame and the model table: host_call.h)
 #pragma once
 
 // ids per lane of the path kernel's one wave: the smallest of 1, 2, 4, .. 32 that covers P
@@ -59,15 +59,14 @@ static void launch_path(mi355tts_ctx* ctx, Worker* w, const AlignLayout& al, int
 }
 
 // durations and scores: device -> pinned staging (behind whatever the caller queued there first) -> the caller's arrays
-static int align_results(Worker* w, const AlignLayout& al, const int32_t* id_lens, int B, const int* d_dur, const float* d_score,
+static int align_results(CallFrame& f, const AlignLayout& al, const int32_t* id_lens, int B, const int* d_dur, const float* d_score,
                          size_t staged, int32_t* durations_out, int dur_ld, float* score_out) {
   const size_t dur_b = sizeof(int) * (size_t)B * al.dur_ld;
-  char* pd = w->pinned_out + staged;
+  char* pd = f.w->pinned_out + staged;
   char* psc = pd + dur_b;
-  HIPCHECK(hipMemcpyAsync(pd, d_dur, dur_b, hipMemcpyDeviceToHost, w->stream));
-  HIPCHECK(hipMemcpyAsync(psc, d_score, sizeof(float) * B, hipMemcpyDeviceToHost, w->stream));
-  HIPCHECK(mi355_sync(w->stream));
-  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(pd, d_dur, dur_b, hipMemcpyDeviceToHost, f.s));
+  HIPCHECK(hipMemcpyAsync(psc, d_score, sizeof(float) * B, hipMemcpyDeviceToHost, f.s));
+  CHECK(f.finish());
   for (int b = 0; b < B; ++b) {
     int32_t* dst = durations_out + (size_t)b * dur_ld;
     std::memset(dst, 0, sizeof(int32_t) * (size_t)dur_ld);
@@ -172,7 +171,7 @@ extern "C" int mi355tts_glow_align(mi355tts_ctx* ctx, int glow, const int64_t* i
                                    int32_t* durations_out, int dur_ld, float* score_out, float* z_out) {
   if (!ctx || !mel || !frames || !durations_out) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GlowModel> gpin;
-  CHECK(find_glow(ctx, glow, &gpin));
+  CHECK(find_model(ctx, glow, &gpin));
   const GlowModel* gm = gpin.get();
   const mi355tts_glow_hparams& h = gm->hp;
   GlowCall call = glow_call(ids, id_lens, B, ids_ld, 0.f, 1.f, nullptr, 0, 0, nullptr, 0);
@@ -189,20 +188,18 @@ extern "C" int mi355tts_glow_align(mi355tts_ctx* ctx, int glow, const int64_t* i
   }
   CHECK(path_precheck(id_lens, F.data(), B, dur_ld, &Pmax, &Fmax));
   const bool in_dev = (flags & MI355TTS_IN_DEVICE) != 0, out_dev = (flags & MI355TTS_OUT_DEVICE) != 0;
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  hipStream_t s = w->stream;
+  CallFrame f(ctx);
+  CHECK(f.open());
+  Worker* w = f.w;
+  hipStream_t s = f.s;
   const int glow_tiles = w->opt.env.glow_tiles > 0 ? w->opt.env.glow_tiles : 1024;
   GlowRun r{ctx, w, gm, call, Pmax, glow_tiles, glow_enc_layout(h, B, ids_ld, Pmax), {}, nullptr};
   // every size is known up front (unlike a synthesis call's frame count): the arena is sized once, before the encoder binds it
   GlowDecLayout dl;
   const AlignLayout al = glow_align_layout(h, r.el, B, Pmax, Fmax, mel_ld, &dl);
-  CHECK(reserve(w, al.total));
   const size_t z_b = z_out && !out_dev ? sizeof(float) * (size_t)B * M * mel_ld : 0;
-  CHECK(reserve_pinned_out(w, z_b + sizeof(int) * (size_t)B * al.dur_ld + sizeof(float) * B));
-  if ((size_t)3 * B > w->pinned_ints) return fail(MI355TTS_ERR_INVALID, "batch too large");
+  CHECK(f.reserve(al.total, z_b + sizeof(int) * (size_t)B * al.dur_ld + sizeof(float) * B));
+  CHECK(f.pinned_ints((size_t)3 * B));
   CHECK(glow_encoder(r));
   const GlowEncView& v = r.ev;
   char* base = w->arena;
@@ -257,8 +254,7 @@ extern "C" int mi355tts_glow_align(mi355tts_ctx* ctx, int glow, const int64_t* i
   }
   launch_path(ctx, w, al, B, logp, lp_bs, v.len, d_frames, (unsigned*)(base + al.o_bits), d_dur, d_score);
   if (z_b) HIPCHECK(hipMemcpyAsync(w->pinned_out, d_z, z_b, hipMemcpyDeviceToHost, s));
-  w->flop_scale = 1.0;
-  CHECK(align_results(w, al, id_lens, B, d_dur, d_score, z_b, durations_out, dur_ld, score_out));
+  CHECK(align_results(f, al, id_lens, B, d_dur, d_score, z_b, durations_out, dur_ld, score_out));
   if (z_b) std::memcpy(z_out, w->pinned_out, z_b);
   return 0;
 }
@@ -272,16 +268,14 @@ extern "C" int mi355tts_op_maximum_path(mi355tts_ctx* ctx, const float* value, i
       return fail(MI355TTS_ERR_INVALID, "row %d: %d x %d outside [1, %d] x [1, %d]", b, id_lens[b], frames[b], P_ld, F_ld);
   int Pmax = 0, Fmax = 0;
   CHECK(path_precheck(id_lens, frames, B, dur_ld, &Pmax, &Fmax));
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  hipStream_t s = w->stream;
+  CallFrame f(ctx);
+  CHECK(f.open());
+  Worker* w = f.w;
+  hipStream_t s = f.s;
   const size_t nval = (size_t)B * P_ld * F_ld;
   const AlignLayout al = align_layout(0, B, Pmax, Fmax, nval, 0);
-  CHECK(reserve(w, al.total));
-  CHECK(reserve_pinned_out(w, sizeof(int) * (size_t)B * al.dur_ld + sizeof(float) * B));
-  if ((size_t)2 * B > w->pinned_ints) return fail(MI355TTS_ERR_INVALID, "batch too large");
+  CHECK(f.reserve(al.total, sizeof(int) * (size_t)B * al.dur_ld + sizeof(float) * B));
+  CHECK(f.pinned_ints((size_t)2 * B));
   char* base = w->arena;
   int* d_frames = (int*)(base + al.o_frames);
   int* d_plen = (int*)(base + al.o_plen);
@@ -301,5 +295,5 @@ extern "C" int mi355tts_op_maximum_path(mi355tts_ctx* ctx, const float* value, i
                        al.ldp, Fmax);
   }
   launch_path(ctx, w, al, B, logp, lp_bs, d_plen, d_frames, (unsigned*)(base + al.o_bits), (int*)(base + al.o_dur), (float*)(base + al.o_score));
-  return align_results(w, al, id_lens, B, (int*)(base + al.o_dur), (float*)(base + al.o_score), 0, durations_out, dur_ld, score_out);
+  return align_results(f, al, id_lens, B, (int*)(base + al.o_dur), (float*)(base + al.o_score), 0, durations_out, dur_ld, score_out);
 }

@@ -2,6 +2,7 @@
 // (one translation unit: included once by mi355tts.hip, after the kernel headers)
 // GlowPass (what a run of launches shares; the launch helpers are its members), the call struct, the workspace layouts and their
 // views, the fused launches, then the stages of a pass — encoder, durations, decoder (a function per flow block) — and glow_run.
+// The entry points open a CallFrame and pin their model with find_model (host_call.h).
 #pragma once
 
 // ------------------------------------------------------------------ GlowTTS forward
@@ -102,15 +103,6 @@ struct GlowCall {
   }
   bool has_prosody() const { return id_scales || durations_in || want_durations; }
 };
-
-// pins the model: the caller's shared_ptr keeps it alive until the call returns, whatever mi355tts_unload does meanwhile
-static int find_glow(mi355tts_ctx* ctx, int glow, std::shared_ptr<GlowModel>* out) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  auto it = ctx->glow.find(glow);
-  if (it == ctx->glow.end()) return fail(MI355TTS_ERR_NO_MODEL, "no GlowTTS model %d", glow);
-  *out = it->second;
-  return 0;
-}
 
 static int glow_precheck(const GlowModel* gm, const GlowCall& c, int* Pmax_out) {
   if ((!c.ids && !c.row_ids) || !c.id_lens) return fail(MI355TTS_ERR_INVALID, "null argument");
@@ -240,17 +232,6 @@ static GlowDecView glow_dec_view(const GlowDecLayout& L, char* base) {
   auto f = [&](size_t off) { return (float*)(base + off); };
   return {f(L.o_z), f(L.o_h), f(L.o_ac), f(L.o_sk), f(L.o_nz)};
 }
-
-// drops a mel on an error exit: its blocks go back to the pool, so nothing queued on the stream may still read or write them
-struct MelDrop {
-  hipStream_t st;
-  mi355tts_mel* m;
-  ~MelDrop() {
-    if (!m) return;
-    mi355_sync(st);
-    mel_destroy(m);
-  }
-};
 
 // One forward pass on worker `w`: what its stages share.
 struct GlowRun {
@@ -521,8 +502,8 @@ static int glow_encoder(GlowRun& r) {
   return glow_proj_durations(p, v);
 }
 
-// ---- stage 2, durations -> frame counts (the one host sync of the path): the mel object (handed to `drop` as soon as it
-// exists), duration_kernel, the read-back, the result blocks.  mel->max_frames == 0: nothing to decode.
+// ---- stage 2, durations -> frame counts (the one host sync of the path): the mel object (the frame's as soon as it exists),
+// duration_kernel, the read-back, the result blocks.  mel->max_frames == 0: nothing to decode.
 static int glow_mel_new(mi355tts_ctx* ctx, const GlowCall& call, int M, mi355tts_mel** out) {
   const int B = call.B;
   // frames live with the result object
@@ -546,22 +527,22 @@ static int glow_mel_new(mi355tts_ctx* ctx, const GlowCall& call, int M, mi355tts
   *out = m;
   return 0;
 }
-static int glow_durations(GlowRun& r, MelDrop& drop) {
+static int glow_durations(GlowRun& r, CallFrame& f) {
   const GlowCall& call = r.call;
   const mi355tts_glow_hparams& h = r.gm->hp;
   Worker* w = r.w;
   hipStream_t s = w->stream;
   const GlowEncView& v = r.ev;
   const int B = call.B, M = h.mel_channels, P = r.el.P;
-  CHECK(glow_mel_new(r.ctx, call, M, &r.mel));
-  mi355tts_mel* mel = drop.m = r.mel;
+  CHECK(glow_mel_new(r.ctx, call, M, &f.mel));
+  mi355tts_mel* mel = r.mel = f.mel;
   {
     ProfScope ps(r.ctx, w, KC_SMALL, 0);
     hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(64), 0, s, v.logw, (long long)P, v.len, call.length_scale, h.n_sqz, v.cum, P,
                        mel->frames_dev, 1 << 28, call.id_scales ? (const float*)v.pros : nullptr,
                        call.durations_in ? (const int*)v.pros : nullptr, P, mel->dur_dev, mel->dur_ld);
   }
-  if ((size_t)B > w->pinned_ints) return fail(MI355TTS_ERR_INVALID, "batch too large");
+  CHECK(f.pinned_ints(B));
   HIPCHECK(hipMemcpyAsync(w->pinned, mel->frames_dev, sizeof(int) * B, hipMemcpyDeviceToHost, s));
   if (mel->dur_dev)
     HIPCHECK(hipMemcpyAsync(mel->durations.data(), mel->dur_dev, sizeof(int) * mel->durations.size(), hipMemcpyDeviceToHost, s));
@@ -726,27 +707,18 @@ static int glow_decoder(GlowRun& r) {
   return 0;
 }
 
-// The forward pass on worker `w`.  With `final_sync` false the mel object is returned while
-// its last kernels are still queued on w->stream (the fused synthesize path launches the
-// vocoder behind them on the same stream).
-static int glow_run(mi355tts_ctx* ctx, Worker* w, const GlowModel* gm, const GlowCall& call, int Pmax, bool final_sync,
-                    mi355tts_mel** out) {
+// The forward pass on frame `f`, which holds the mel (f.mel) from the moment it exists.  With `final_sync` false the mel's last
+// kernels are still queued on f.s when this returns (the fused synthesize path launches the vocoder behind them on the same
+// stream).
+static int glow_run(CallFrame& f, const GlowModel* gm, const GlowCall& call, int Pmax, bool final_sync) {
+  Worker* w = f.w;
   const int glow_tiles = call.solo_tiles ? (1 << 30) : w->opt.env.glow_tiles > 0 ? w->opt.env.glow_tiles : 1024;
-  GlowRun r{ctx, w, gm, call, Pmax, glow_tiles, glow_enc_layout(gm->hp, call.B, call.ids_ld, Pmax), {}, nullptr};
+  GlowRun r{f.ctx, w, gm, call, Pmax, glow_tiles, glow_enc_layout(gm->hp, call.B, call.ids_ld, Pmax), {}, nullptr};
   CHECK(glow_encoder(r));
-  MelDrop drop{w->stream, nullptr};
-  CHECK(glow_durations(r, drop));
-  if (r.mel->max_frames > 0) {
-    CHECK(glow_decoder(r));
-    if (final_sync) {
-      HIPCHECK(mi355_sync(w->stream));
-      HIPCHECK(hipGetLastError());
-    }
-    w->flop_scale = 1.0;
-  }
-  drop.m = nullptr;
-  *out = r.mel;
-  return 0;
+  CHECK(glow_durations(r, f));
+  if (r.mel->max_frames == 0) f.done = true;  // nothing to decode, and glow_durations has waited for all there was
+  else CHECK(glow_decoder(r));
+  return final_sync && !f.done ? f.finish() : 0;
 }
 
 // the arguments the entry points share, in their order (the rest of a GlowCall is filled by the entry that has it)
@@ -763,15 +735,15 @@ static GlowCall glow_call(const int64_t* ids, const int32_t* id_lens, int B, int
 static int glow_infer_impl(mi355tts_ctx* ctx, int glow, const GlowCall& c, mi355tts_mel** out) {
   if (!ctx || !out) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GlowModel> gpin;
-  CHECK(find_glow(ctx, glow, &gpin));
+  CHECK(find_model(ctx, glow, &gpin));
   const GlowModel* gm = gpin.get();
   int Pmax = 0;
   CHECK(glow_precheck(gm, c, &Pmax));
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  return glow_run(ctx, w, gm, c, Pmax, true, out);
+  CallFrame f(ctx);
+  CHECK(f.open());
+  CHECK(glow_run(f, gm, c, Pmax, true));
+  *out = f.take_mel();
+  return 0;
 }
 
 extern "C" int mi355tts_glow_infer(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,

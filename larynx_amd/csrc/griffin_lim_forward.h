@@ -1,5 +1,6 @@
 // mi355tts host runtime — the Griffin-Lim vocoder's load and inference entry points (kernels: griffin_lim.h)
-// (one translation unit: included once by mi355tts.hip, after the launch helpers)
+// (one translation unit: included once by mi355tts.hip, after hifigan_forward.h for the row delivery it shares; the call frame,
+// the model table and context_table: host_call.h)
 #pragma once
 
 // window + twiddles in double precision, rounded once: tab[i] = np.hanning(1024)[i]; then (cos, -sin)(2 pi m / 1024) with the
@@ -19,29 +20,8 @@ static void gl_build_table(std::vector<float>& t) {
   }
 }
 
-// the context's copy of the table: built and uploaded by whichever load needs it first
-static int ensure_gl_table(mi355tts_ctx* ctx) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (ctx->gl_table) return 0;
-  std::vector<float> t;
-  gl_build_table(t);
-  float* d = nullptr;
-  if (hipMalloc(&d, t.size() * sizeof(float)) != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc Griffin-Lim table");
-  if (hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(d);
-    return fail(MI355TTS_ERR_HIP, "Griffin-Lim table upload failed");
-  }
-  ctx->gl_table = d;
-  return 0;
-}
-
-static int find_griffin(mi355tts_ctx* ctx, int model, std::shared_ptr<GriffinLimModel>* out) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  auto it = ctx->griffin.find(model);
-  if (it == ctx->griffin.end()) return fail(MI355TTS_ERR_NO_MODEL, "no Griffin-Lim model %d", model);
-  *out = it->second;
-  return 0;
-}
+// the context's copy of the table
+static int ensure_gl_table(mi355tts_ctx* ctx) { return context_table(ctx, &ctx->gl_table, "Griffin-Lim table", gl_build_table); }
 
 extern "C" int mi355tts_load_griffin_lim(mi355tts_ctx* ctx, const mi355tts_griffin_lim_params* params, const float* mel_basis,
                                          int* model_out) {
@@ -57,11 +37,7 @@ extern "C" int mi355tts_load_griffin_lim(mi355tts_ctx* ctx, const mi355tts_griff
   const size_t n = (size_t)params->num_mels * GL_BINS;
   if (hipMalloc(&gm->basis, n * sizeof(float)) != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc mel basis");
   HIPCHECK(hipMemcpy(gm->basis, mel_basis, n * sizeof(float), hipMemcpyHostToDevice));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const int id = ctx->next_id++;
-  ctx->griffin[id] = std::move(gm);
-  *model_out = id;
-  return 0;
+  return register_model(ctx, std::move(gm), model_out);
 }
 
 extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi355tts_mel* mel, const float* phase0, uint64_t seed,
@@ -69,7 +45,7 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
                                           uint32_t flags) {
   if (!ctx || !mel) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GriffinLimModel> pin;
-  CHECK(find_griffin(ctx, model, &pin));
+  CHECK(find_model(ctx, model, &pin));
   const GriffinLimModel* gm = pin.get();
   if (mel->ctx != ctx) return fail(MI355TTS_ERR_INVALID, "mel belongs to another context");
   if (mel->M != gm->p.num_mels) return fail(MI355TTS_ERR_INVALID, "mel has %d channels, the vocoder expects %d", mel->M, gm->p.num_mels);
@@ -81,13 +57,12 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
   if ((wav_f32 || wav_i16) && wav_ld < N) return fail(MI355TTS_ERR_TOO_SMALL, "wav_ld %lld < %lld samples", (long long)wav_ld, N);
   if (wav_ld < 0) return fail(MI355TTS_ERR_INVALID, "negative wav_ld");
   const bool in_dev = (flags & MI355TTS_IN_DEVICE) != 0, out_dev = (flags & MI355TTS_OUT_DEVICE) != 0;
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  hipStream_t s = w->stream;
+  CallFrame f(ctx);
+  CHECK(f.open());
+  Worker* w = f.w;
+  hipStream_t s = f.s;
   const OutRows rows = {nullptr, nullptr, 0, {wav_f32, wav_i16, wav_ld, 0, 0, (size_t)N}};
-  if (T == 0) return zero_outputs(rows, B, RowWriter{out_dev, s});  // every row has fewer than 2 frames: empty signals
+  if (T == 0) return zero_outputs(f, rows, B, out_dev);  // every row has fewer than 2 frames: empty signals
   const size_t nph = (size_t)B * GL_BINS * T;
   const size_t Nld = (size_t)((N + 3) & ~3LL);
   Carver cv;
@@ -99,7 +74,9 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
   const size_t o_peak = cv.take(sizeof(unsigned) * (size_t)B);
   const size_t o_pin = cv.take(phase0 && !in_dev ? sizeof(float) * nph : 0);
   const size_t o_pout = cv.take(phase_out && !out_dev ? sizeof(float) * nph : 0);
-  CHECK(reserve(w, cv.pos));
+  // host outputs wait in the pinned staging: the float rows, the int16 rows, the phases
+  const Staging st = host_staging(B, wav_f32 && !out_dev, Nld, wav_i16 && !out_dev, Nld, 0, phase_out && !out_dev ? sizeof(float) * nph : 0);
+  CHECK(f.reserve(cv.pos, st.end()));
   char* base = w->arena;
   float* mag = (float*)(base + o_mag);
   float* fb[2] = {(float*)(base + o_f0), (float*)(base + o_f1)};
@@ -151,25 +128,5 @@ extern "C" int mi355tts_griffin_lim_infer(mi355tts_ctx* ctx, int model, const mi
     if (out_dev) hipLaunchKernelGGL(griffin_lim_int16_kernel, dim3(128, B), dim3(256), 0, s, wav, wbs, d_frames, peak, wav_i16, (long long)wav_ld, (long long)wav_ld);
     else hipLaunchKernelGGL(griffin_lim_int16_kernel, dim3(128, B), dim3(256), 0, s, wav, wbs, d_frames, peak, i16, (long long)Nld, (long long)Nld);
   }
-  if (!out_dev) {
-    // host outputs: device -> the worker's pinned staging (async DMA) -> the caller's (pageable) buffers
-    const size_t f32_b = wav_f32 ? sizeof(float) * (size_t)B * Nld : 0;
-    const size_t i16_b = wav_i16 ? sizeof(short) * (size_t)B * Nld : 0;
-    const size_t ph_b = phase_out ? sizeof(float) * nph : 0;
-    CHECK(reserve_pinned_out(w, f32_b + i16_b + ph_b));
-    char* pf = w->pinned_out;
-    char* pi = pf + f32_b;
-    char* pp = pi + i16_b;
-    if (f32_b) HIPCHECK(hipMemcpyAsync(pf, wav, f32_b, hipMemcpyDeviceToHost, s));
-    if (i16_b) HIPCHECK(hipMemcpyAsync(pi, i16, i16_b, hipMemcpyDeviceToHost, s));
-    if (ph_b) HIPCHECK(hipMemcpyAsync(pp, dph_out, ph_b, hipMemcpyDeviceToHost, s));
-    HIPCHECK(mi355_sync(s));
-    HIPCHECK(hipGetLastError());
-    CHECK(scatter_rows(rows, B, WavRows{(float*)pf, Nld, (short*)pi, Nld}, RowWriter{false, s}));
-    if (phase_out) std::memcpy(phase_out, pp, ph_b);
-    return 0;
-  }
-  HIPCHECK(mi355_sync(s));
-  HIPCHECK(hipGetLastError());
-  return 0;
+  return out_dev ? f.finish() : deliver_rows(f, rows, B, WavRows{wav, Nld, i16, Nld}, st, true, phase_out, dph_out);
 }

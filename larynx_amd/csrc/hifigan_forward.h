@@ -2,17 +2,17 @@
 // (one translation unit: included once by mi355tts.hip, after the kernel headers)
 // The call struct and the workspace layout; the row view of a call's outputs (OutRows); VocPass (what a pass shares); the stage
 // bookkeeping both precisions use (VocStage, StageCursor, chain_planes / step_dst, run_forked); the f32 / split-bf16 generator and
-// the fp16 generator, each a walk over pre / upsample / resblocks / post; the delivery (zero_outputs, stage_rows, scatter_rows);
-// then hifigan_run: empty call, layout and bind, generate, denoise, deliver.
+// the fp16 generator, each a walk over pre / upsample / resblocks / post; the delivery (zero_outputs, stage_rows, scatter_rows and
+// deliver_rows, which Griffin-Lim and the resampler share); then hifigan_run: empty call, layout and bind, generate, denoise, deliver.
+// Every call runs on a CallFrame (host_call.h): it holds the worker and drains the streams when a call fails midway.
 #pragma once
 
 // ------------------------------------------------------------------ HiFi-GAN forward
 extern "C" int mi355tts_hifigan_hop(mi355tts_ctx* ctx, int vocoder) {
   if (!ctx) return fail(MI355TTS_ERR_INVALID, "ctx null");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  auto it = ctx->hifi.find(vocoder);
-  if (it == ctx->hifi.end()) return fail(MI355TTS_ERR_NO_MODEL, "no HiFi-GAN model %d", vocoder);
-  return it->second->hop;
+  std::shared_ptr<HifiModel> vpin;
+  CHECK(find_model(ctx, vocoder, &vpin));
+  return vpin->hop;
 }
 
 // One vocoder call's outputs: per row [pad_before zeros][frames[b]*hop samples][zeros up to wav_ld]
@@ -36,15 +36,6 @@ struct VocCall {
   // another thread meanwhile); the bias pass, the generator and the denoiser's bias slot all follow this value.
   int precision = -1;
 };
-
-// pins the model (see find_glow)
-static int find_hifi(mi355tts_ctx* ctx, int vocoder, std::shared_ptr<HifiModel>* out) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  auto it = ctx->hifi.find(vocoder);
-  if (it == ctx->hifi.end()) return fail(MI355TTS_ERR_NO_MODEL, "no HiFi-GAN model %d", vocoder);
-  *out = it->second;
-  return 0;
-}
 
 static int ensure_denoiser_bias(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, int precision);
 
@@ -141,9 +132,20 @@ static OutRows call_rows(const VocCall& c, const mi355tts_mel* mel, int hop) {
   return {nullptr, nullptr, 0, {c.wav_f32, c.wav_i16, c.wav_ld, (size_t)c.pad_before, (size_t)c.pad_after, (size_t)mel->max_frames * hop}};
 }
 
+// Where a call's host outputs wait in the worker's pinned staging, from byte `at` of it: the float rows [B][f_ld], the int16
+// rows [B][i_ld], then one extra block.  Sized before the call's first launch (CallFrame::reserve), read by deliver_rows.
+struct Staging {
+  size_t at = 0, f32_b = 0, i16_b = 0, extra_b = 0, f_ld = 0, i_ld = 0;
+  size_t end() const { return at + f32_b + i16_b + extra_b; }
+};
+static Staging host_staging(int B, bool f32, size_t f_ld, bool i16, size_t i_ld, size_t at = 0, size_t extra_b = 0) {
+  return {at, f32 ? sizeof(float) * (size_t)B * f_ld : 0, i16 ? sizeof(short) * (size_t)B * i_ld : 0, extra_b, f_ld, i_ld};
+}
+
 // ------------------------------------------------------------------ what one vocoder pass shares
 // Both generators, the denoiser and the delivery take this one argument.  `bind` lays the workspace out and fills the pointers.
 struct VocPass {
+  CallFrame& frame;
   mi355tts_ctx* ctx;
   Worker* w;
   HifiModel* hm;
@@ -174,10 +176,11 @@ struct VocPass {
   float* peak = nullptr;  // [B][peak_ld], or null when nobody reads them
   long long peak_ld = 0;
   const float* bias_spec = nullptr;
+  Staging staged;  // host outputs: rows of the samples alone / of samples + pauses (nothing for MI355TTS_OUT_DEVICE)
 
-  VocPass(mi355tts_ctx* ctx_, Worker* w_, HifiModel* hm_, const mi355tts_mel* mel_, const VocCall& call)
-      : ctx(ctx_), w(w_), hm(hm_), mel(mel_), s(w_->stream), B(mel_->B), F(mel_->max_frames), hop(hm_->hop), d_frames(mel_->frames_dev),
-        voc_host_len(mel_->B == 1 ? mel_->frames[0] : -1), opt(w_->opt), prec(call.precision), f16(call.precision == MI355TTS_PRECISION_F16),
+  VocPass(CallFrame& f, HifiModel* hm_, const mi355tts_mel* mel_, const VocCall& call)
+      : frame(f), ctx(f.ctx), w(f.w), hm(hm_), mel(mel_), s(f.s), B(mel_->B), F(mel_->max_frames), hop(hm_->hop), d_frames(mel_->frames_dev),
+        voc_host_len(mel_->B == 1 ? mel_->frames[0] : -1), opt(f.w->opt), prec(call.precision), f16(call.precision == MI355TTS_PRECISION_F16),
         denoiser_strength(call.denoiser_strength), denoise(call.denoiser_strength > 0.f && mel_->max_frames > 0),
         out_dev((call.flags & MI355TTS_OUT_DEVICE) != 0) {}
 
@@ -200,7 +203,9 @@ struct VocPass {
     }
     const HifiLayout lay = hifi_layout(h, hop, B, F, denoise, f16 || hifi_split_out(opt.serial_branches, h), pads);
     if (f16 && (size_t)((mel->M + 7) / 8) * F * 16 > lay.plane * sizeof(float)) return fail(MI355TTS_ERR_INVALID, "internal: mel octets exceed a plane buffer");
-    CHECK(reserve(w, lay.total));
+    // a pageable destination would make every hipMemcpyAsync a blocking staged copy: host rows travel through pinned staging
+    staged = host_staging(B, any_f32 && !out_dev, (size_t)F * hop, any_i16 && !out_dev, (size_t)F * hop + (size_t)pads);
+    CHECK(frame.reserve(lay.total, staged.end()));
     char* base = w->arena;
     for (int i = 0; i < lay.nbuf; ++i) buf[i] = (float*)(base + lay.o_buf[i]);
     wav = (float*)(base + lay.o_wav);
@@ -293,7 +298,7 @@ static P* step_dst(const ChainPlanes<P>& c, int d, int nd) {
 }
 
 // `body` with `n_side` of the worker's side streams forked off `s` before it and joined behind it (0: `body` alone).  One
-// function, so that no later edit separates a record from its wait; an error return leaves the streams to DrainOnError.
+// function, so that no later edit separates a record from its wait; an error return leaves the streams to the call frame.
 template <class Body>
 static int run_forked(Worker* w, hipStream_t s, int n_side, Body&& body) {
   if (n_side > 0) {
@@ -762,8 +767,9 @@ struct RowWriter {
   }
 };
 
-// an empty call: every output row all zeros (whole-batch rows lie back to back: one fill per form)
-static int zero_outputs(const OutRows& rows, int B, const RowWriter& wr) {
+// an empty call: every output row all zeros (whole-batch rows lie back to back: one fill per form); ends the frame's work
+static int zero_outputs(CallFrame& f, const OutRows& rows, int B, bool dev) {
+  const RowWriter wr{dev, f.s};
   const int nfill = rows.rows ? B : 1;
   const size_t span = rows.rows ? 1 : (size_t)B;
   for (int b = 0; b < nfill; ++b) {
@@ -771,7 +777,8 @@ static int zero_outputs(const OutRows& rows, int B, const RowWriter& wr) {
     if (r.f32) CHECK(wr.zero(r.f32, span * (size_t)r.ld));
     if (r.i16) CHECK(wr.zero(r.i16, span * (size_t)r.ld));
   }
-  if (wr.dev) HIPCHECK(mi355_sync(wr.s));
+  if (dev) HIPCHECK(f.wait());
+  f.done = true;
   return 0;
 }
 
@@ -808,6 +815,25 @@ static int stage_rows(const OutRows& rows, int B, const WavRows& dev, const WavR
     if (r.f32 && r.n) HIPCHECK(hipMemcpyAsync(pin.f32 + (size_t)b * pin.f_ld, dev.f32 + (size_t)b * dev.f_ld, sizeof(float) * r.n, hipMemcpyDeviceToHost, s));
     if (r.i16) HIPCHECK(hipMemcpyAsync(pin.i16 + (size_t)b * pin.i_ld, dev.i16 + (size_t)b * dev.i_ld, sizeof(short) * (r.n + r.pad_before + r.pad_after), hipMemcpyDeviceToHost, s));
   }
+  return 0;
+}
+
+// Host delivery: device rows -> the pinned staging `st` describes (async DMA) -> the end of the frame's device work -> the
+// caller's (pageable) rows.  `block`: the staging keeps the device rows' strides and each form goes in ONE copy; else row by
+// row, the part its caller receives.  `extra_src` (device, st.extra_b bytes) rides along to `extra_dst`.
+static int deliver_rows(CallFrame& f, const OutRows& rows, int B, const WavRows& dev, const Staging& st, bool block, void* extra_dst = nullptr,
+                        const void* extra_src = nullptr) {
+  char* pf = f.w->pinned_out + st.at;
+  char* pi = pf + st.f32_b;
+  char* px = pi + st.i16_b;
+  const WavRows pin = {(float*)pf, st.f_ld, (short*)pi, st.i_ld};
+  if (!block) CHECK(stage_rows(rows, B, dev, pin, f.s));
+  if (block && st.f32_b) HIPCHECK(hipMemcpyAsync(pf, dev.f32, st.f32_b, hipMemcpyDeviceToHost, f.s));
+  if (block && st.i16_b) HIPCHECK(hipMemcpyAsync(pi, dev.i16, st.i16_b, hipMemcpyDeviceToHost, f.s));
+  if (st.extra_b) HIPCHECK(hipMemcpyAsync(px, extra_src, st.extra_b, hipMemcpyDeviceToHost, f.s));
+  CHECK(f.finish());
+  CHECK(scatter_rows(rows, B, pin, RowWriter{false, f.s}));
+  if (st.extra_b) std::memcpy(extra_dst, px, st.extra_b);
   return 0;
 }
 
@@ -885,71 +911,36 @@ static int voc_tail_by_pieces(VocPass& p, const VocCall& call, float* wav) {
 // The finished rows `wav` to the caller; ends with the stream synchronised
 static int voc_deliver(VocPass& p, const VocCall& call, const OutRows& rows, float* wav) {
   const WavRows dev = {wav, p.Nld, p.i16, p.ild};
-  WavRows pin = {};
   if (p.voc_out) {
     CHECK(voc_tail_one_launch(p, call, wav));
   } else {
     CHECK(voc_tail_by_pieces(p, call, wav));
     if (p.out_dev) CHECK(scatter_rows(rows, p.B, dev, RowWriter{true, p.s}));
   }
-  if (!p.out_dev) {
-    // host outputs: device -> the worker's pinned staging (async DMA) -> the caller's (pageable)
-    // buffers; a pageable destination would make every hipMemcpyAsync a blocking staged copy
-    const size_t N = (size_t)p.F * p.hop, prl = N + (size_t)p.pads;  // staging strides in samples
-    const size_t f32_b = p.any_f32 ? sizeof(float) * (size_t)p.B * N : 0;
-    const size_t i16_b = p.any_i16 ? sizeof(short) * (size_t)p.B * prl : 0;
-    CHECK(reserve_pinned_out(p.w, f32_b + i16_b));
-    pin = {(float*)p.w->pinned_out, N, (short*)(p.w->pinned_out + f32_b), prl};
-    CHECK(stage_rows(rows, p.B, dev, pin, p.s));
-  }
-  HIPCHECK(mi355_sync(p.s));
-  HIPCHECK(hipGetLastError());
-  return p.out_dev ? 0 : scatter_rows(rows, p.B, pin, RowWriter{false, p.s});
+  return p.out_dev ? p.frame.finish() : deliver_rows(p.frame, rows, p.B, dev, p.staged, false);
 }
 
-// The forward pass proper on worker `w` (already checked by hifigan_precheck); ends with the
-// stream synchronised and the outputs delivered.
-static int hifigan_run(mi355tts_ctx* ctx, Worker* w, HifiModel* hm, const mi355tts_mel* mel, const VocCall& call) {
+// The forward pass proper on frame `f` (already checked by hifigan_precheck); ends with the stream synchronised and the outputs
+// delivered.  An error return behind queued kernels — possibly on the side streams — is drained by the frame.
+static int hifigan_run(CallFrame& f, HifiModel* hm, const mi355tts_mel* mel, const VocCall& call) {
   const OutRows rows = call_rows(call, mel, hm->hop);
-  if (mel->max_frames == 0) return zero_outputs(rows, mel->B, RowWriter{(call.flags & MI355TTS_OUT_DEVICE) != 0, w->stream});
-  // an error return after kernels were queued must not hand the worker (its arena!) to the
-  // next call while they still run — possibly on the side streams
-  struct DrainOnError {
-    Worker* w;
-    bool ok = false;
-    ~DrainOnError() {
-      if (ok) return;
-      mi355_sync(w->stream);
-      for (int i = 0; i < 2; ++i)
-        if (w->aux[i]) mi355_sync(w->aux[i]);
-    }
-  } drain{w};
-  struct FlopScale {  // profiled FLOP of a ragged batch count the rows' real frames, not B x the longest row
-    Worker* w;
-    ~FlopScale() { w->flop_scale = 1.0; }
-  } fscale{w};
-  {
-    long long sum = 0;
-    for (int b = 0; b < mel->B; ++b) sum += mel->frames[b];
-    w->flop_scale = (double)sum / ((double)mel->B * mel->max_frames);
-  }
-  VocPass p(ctx, w, hm, mel, call);
+  if (mel->max_frames == 0) return zero_outputs(f, rows, mel->B, (call.flags & MI355TTS_OUT_DEVICE) != 0);
+  long long sum = 0;  // profiled FLOP of a ragged batch count the rows' real frames, not B x the longest row
+  for (int b = 0; b < mel->B; ++b) sum += mel->frames[b];
+  f.w->flop_scale = (double)sum / ((double)mel->B * mel->max_frames);
+  VocPass p(f, hm, mel, call);
   CHECK(p.bind(call, rows));
   CHECK(p.f16 ? hifigan_body_f16(p) : hifigan_body_f32(p));
-  CHECK(voc_deliver(p, call, rows, voc_denoise(p)));
-  drain.ok = true;
-  return 0;
+  return voc_deliver(p, call, rows, voc_denoise(p));
 }
 
 
 // One vocoder call on a pinned model and a worker of its own; `call.precision` >= 0: the precision is already fixed
 static int hifigan_call_on(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, const mi355tts_mel* mel, VocCall call) {
   CHECK(hifigan_precheck(ctx, hm, vocoder, mel->frames.data(), mel->B, mel->M, mel->max_frames, call));
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  return hifigan_run(ctx, w, hm, mel, call);
+  CallFrame f(ctx);
+  CHECK(f.open());
+  return hifigan_run(f, hm, mel, call);
 }
 
 // The denoiser's bias spectrum of the generator of `precision` (the model keeps one per generator), computed on first use
@@ -980,13 +971,12 @@ static int ensure_denoiser_bias(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, i
     rc = hifigan_call_on(ctx, hm, vocoder, zm, c);
   }
   if (!rc) {
-    Worker* w = nullptr;
-    rc = acquire_worker(ctx, &w);
+    CallFrame f(ctx);
+    rc = f.open();
     if (!rc) {
-      WorkerGuard guard{ctx, w};
-      hipLaunchKernelGGL(stft_denoise_kernel, dim3(1, 1), dim3(256), 0, w->stream, dwav, (long long)N, zm->frames_dev, hop,
+      hipLaunchKernelGGL(stft_denoise_kernel, dim3(1, 1), dim3(256), 0, f.s, dwav, (long long)N, zm->frames_dev, hop,
                          (const float*)nullptr, 0.f, (float*)nullptr, 1, bias);
-      if (mi355_sync(w->stream) != hipSuccess) rc = fail(MI355TTS_ERR_HIP, "denoiser bias kernel failed");
+      if (f.wait() != hipSuccess) rc = fail(MI355TTS_ERR_HIP, "denoiser bias kernel failed");
     }
   }
   mel_destroy(zm);
@@ -1003,7 +993,7 @@ static int ensure_denoiser_bias(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, i
 static int hifigan_call(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, const VocCall& call) {
   if (!ctx || !mel) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<HifiModel> vpin;
-  CHECK(find_hifi(ctx, vocoder, &vpin));
+  CHECK(find_model(ctx, vocoder, &vpin));
   return hifigan_call_on(ctx, vpin.get(), vocoder, mel, call);
 }
 

@@ -1,4 +1,5 @@
 // mi355tts host runtime — context, per-call workers (stream + workspace + pinned staging), device-block pool
+// (a call checks its worker out and gives it back through its CallFrame: host_call.h)
 // (one translation unit: included once by mi355tts.hip, after the kernel headers)
 #pragma once
 
@@ -85,11 +86,12 @@ struct mi355tts_ctx : ProfSums {  // (the profiling switch, the launch sums and 
   int device = 0;
   int ncu = 256;  // compute units (hipGetDeviceProperties at create): the dispatch-order logic of grouped launches
   std::mutex mu;
-  std::map<int, std::shared_ptr<GlowModel>> glow;
-  std::map<int, std::shared_ptr<HifiModel>> hifi;
-  std::map<int, std::shared_ptr<GriffinLimModel>> griffin;
-  std::map<int, std::shared_ptr<AnalysisModel>> analysis;
-  std::map<int, std::shared_ptr<ResamplerModel>> resampler;
+  // every loaded model by id; `kind` is the model type's `missing` message (host_models.h; find_model / register_model: host_call.h)
+  struct ModelEntry {
+    const char* kind;
+    std::shared_ptr<void> model;
+  };
+  std::map<int, ModelEntry> models;
   // window + twiddles of the Griffin-Lim kernels (griffin_lim.h), built by the first load of a Griffin-Lim or analysis model
   float* gl_table = nullptr;
   float* hann_periodic = nullptr;  // the HiFi-GAN framing's window (mel_analysis.h), built by the first analysis load
@@ -198,14 +200,6 @@ static void release_worker(mi355tts_ctx* ctx, Worker* w) {
   if (w->qgroup >= 0 && w->qgroup < (int)ctx->qgroup_busy.size() && ctx->qgroup_busy[w->qgroup] > 0) ctx->qgroup_busy[w->qgroup] -= 1;
   ctx->free_workers.push_back(w);
 }
-
-struct WorkerGuard {
-  mi355tts_ctx* ctx;
-  Worker* w;
-  ~WorkerGuard() {
-    if (w) release_worker(ctx, w);
-  }
-};
 
 // grow-only workspace: a call computes its total need, then carves.
 static int reserve(Worker* w, size_t bytes) {

@@ -25,20 +25,18 @@
 //     solitary call and reports what that returns.
 #pragma once
 
-// GlowTTS, then the vocoder behind it on the same stream, on a freshly acquired worker: the body of every fused call.  The
+// GlowTTS, then the vocoder behind it on the same stream, on one call frame (host_call.h): the body of every fused call.  The
 // frame counts reach `frames_out` as soon as they are known — before the vocoder's checks can fail (TOO_SMALL reports them).
 // (Pmax: what glow_precheck returned for `g`)
 static int run_fused_call(mi355tts_ctx* ctx, const GlowModel* gm, HifiModel* hm, int vocoder, const GlowCall& g, int Pmax, VocCall& v,
                           int32_t* frames_out) {
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  MelDrop drop{w->stream, nullptr};
-  CHECK(glow_run(ctx, w, gm, g, Pmax, false, &drop.m));
-  const mi355tts_mel* mel = drop.m;
+  CallFrame f(ctx);
+  CHECK(f.open());
+  CHECK(glow_run(f, gm, g, Pmax, false));
+  const mi355tts_mel* mel = f.mel;  // an intermediate: it goes with the frame
   for (int b = 0; b < g.B; ++b) frames_out[b] = mel->frames[b];
   CHECK(hifigan_precheck(ctx, hm, vocoder, mel->frames.data(), g.B, mel->M, mel->max_frames, v));
-  return hifigan_run(ctx, w, hm, mel, v);
+  return hifigan_run(f, hm, mel, v);
 }
 
 struct CallReq {
@@ -105,7 +103,6 @@ static void call_join_run(mi355tts_ctx* ctx, std::vector<CallReq*>& rows) {
   auto run = [&]() -> int {
     int Pmax = 0;
     CHECK(glow_precheck(lead.gm, c, &Pmax));
-    HIPCHECK(hipSetDevice(ctx->device));
     return run_fused_call(ctx, lead.gm, lead.hm, lead.vocoder, c, Pmax, v, frames.data());
   };
   const int rc = run();

@@ -1,7 +1,7 @@
 // mi355tts host runtime — model loading: a weight blob in manifest order becomes a model.  BlobReader walks the blob against
 // the manifest, build_glow_model / build_hifi_model pack every tensor into a ModelPacker's host arenas (stage by stage, in the
 // order of the manifest), ModelPacker::upload moves the arenas to the device and binds every conv the model's each_conv
-// visits.  The C ABI's loaders (mi355tts.hip) are open_blob -> build -> upload -> register_model.
+// visits.  The C ABI's loaders (mi355tts.hip) are open_blob -> build -> upload -> register_model (host_call.h).
 // (one translation unit: included once by mi355tts.hip, after hifigan_f16.h for the fp16 packers)
 #pragma once
 
@@ -83,15 +83,6 @@ struct WorkerWeights {
     return 0;
   }
 };
-
-template <class Model>
-static int register_model(mi355tts_ctx* ctx, std::map<int, std::shared_ptr<Model>>& models, std::shared_ptr<Model> m, int* model_out) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const int id = ctx->next_id++;
-  models[id] = std::move(m);
-  *model_out = id;
-  return 0;
-}
 
 // ------------------------------------------------------------------ GlowTTS
 // a plain conv in its f32 tile packing and, where the shape has one, the lin16 packing

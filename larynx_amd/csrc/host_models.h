@@ -292,6 +292,8 @@ struct ModelArenas {
 };
 
 struct GlowModel : ModelArenas {
+  // what a lookup of another id says; also the type's tag in the context's model table (host_call.h)
+  static constexpr const char* missing = "no GlowTTS model %d";
   mi355tts_glow_hparams hp;
   // the `half` switch: MI355TTS_PRECISION_F16 = the decoder's WaveNets in fp16 (wn_f16.h) when the geometry is covered
   // (f16_ok; f16_why says what is not); everything else of the acoustic model computes in f32 in every mode
@@ -335,6 +337,7 @@ struct MrfStage {
   double mac_per_col = 0;  // algorithmic MACs per output column (all 18 convs)
 };
 struct HifiModel : ModelArenas {
+  static constexpr const char* missing = "no HiFi-GAN model %d";
   mi355tts_hifigan_hparams hp;
   // the native fp16 mode (MI355TTS_PRECISION_F16): every conv of the generator packed for conv_f16.h; f16_ok = the model's
   // geometry is one the fp16 tiles cover (f16_why says what is not)
@@ -381,6 +384,7 @@ struct HifiModel : ModelArenas {
 
 // The Griffin-Lim vocoder (griffin_lim.h) has no weights: its "model" is the mel filter bank [num_mels][513] and three numbers
 struct GriffinLimModel {
+  static constexpr const char* missing = "no Griffin-Lim model %d";
   mi355tts_griffin_lim_params p;
   int device = 0;
   float* basis = nullptr;
@@ -393,6 +397,7 @@ struct GriffinLimModel {
 // Mel analysis (mel_analysis.h) has no weights either: the filter bank, the non-zero band [first, one past last) of each of its
 // rows (made from the uploaded basis at load time, not from the mel scale) and the framing
 struct AnalysisModel {
+  static constexpr const char* missing = "no analysis model %d";
   mi355tts_analysis_params p;
   int device = 0;
   float* basis = nullptr;
@@ -407,6 +412,7 @@ struct AnalysisModel {
 // A resampler (resample.h) is its polyphase table: the caller's prototype laid out [phase p][t] = taps[p + t * up], rows of Tp
 // floats (T = ceil((2 H + 1) / up) rounded up to 4, zero-filled), made at load time
 struct ResamplerModel {
+  static constexpr const char* missing = "no resampler %d";
   mi355tts_resampler_params p;
   int device = 0;
   int T = 0, Tp = 0;

@@ -53,6 +53,7 @@ using namespace mi355tts;
 #include "host_models.h"
 #include "host_options.h"
 #include "host_context.h"
+#include "host_call.h"
 #include "host_group.h"
 #include "host_launch.h"
 #include "hifigan_f16.h"
@@ -183,7 +184,7 @@ extern "C" int mi355tts_load_glow(mi355tts_ctx* ctx, const mi355tts_glow_hparams
   ModelPacker pk;
   CHECK(build_glow_model(*hp, r, pk, *gm));
   CHECK(pk.upload(ctx, *gm));
-  return register_model(ctx, ctx->glow, std::move(gm), model_out);
+  return register_model(ctx, std::move(gm), model_out);
 }
 
 static int dispatch_selfcheck_run(mi355tts_ctx* ctx);
@@ -201,46 +202,24 @@ extern "C" int mi355tts_load_hifigan(mi355tts_ctx* ctx, const mi355tts_hifigan_h
   CHECK(pk.upload(ctx, *hm));
   // the first vocoder with a 256-channel stage: check the dispatcher rule its batch-1 schedule relies on (once per context)
   if ((hp->upsample_initial_channel >> 1) >= 256 && hp->resblock_type == 1) dispatch_selfcheck_run(ctx);  // (a failed check leaves the defaults)
-  return register_model(ctx, ctx->hifi, std::move(hm), model_out);
+  return register_model(ctx, std::move(hm), model_out);
 }
 
-// Safe while other threads are synthesising with the model: every call pins its models (find_glow / find_hifi hand out
-// shared_ptr copies), so this only drops the context's reference and the id; the arenas are freed by whoever lets go
+// Safe while other threads are synthesising with the model: every call pins its models (find_model hands out shared_ptr
+// copies), so this only drops the context's reference and the id; the arenas are freed by whoever lets go
 // last — here, or the last call still using the model when it returns.  The reference frees a voice by dropping its
 // Python object the same way (larynx/__init__.py:290-300 keeps models in a dict).
 extern "C" int mi355tts_unload(mi355tts_ctx* ctx, int model) {
   if (!ctx) return fail(MI355TTS_ERR_INVALID, "ctx null");
-  std::shared_ptr<GlowModel> g;
-  std::shared_ptr<HifiModel> v;
-  std::shared_ptr<GriffinLimModel> gl;
-  std::shared_ptr<AnalysisModel> an;
-  std::shared_ptr<ResamplerModel> rs;
+  std::shared_ptr<void> dropped;
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
-    auto gi = ctx->glow.find(model);
-    auto li = ctx->griffin.find(model);
-    auto ai = ctx->analysis.find(model);
-    auto ri = ctx->resampler.find(model);
-    if (gi != ctx->glow.end()) {
-      g = std::move(gi->second);
-      ctx->glow.erase(gi);
-    } else if (li != ctx->griffin.end()) {
-      gl = std::move(li->second);
-      ctx->griffin.erase(li);
-    } else if (ai != ctx->analysis.end()) {
-      an = std::move(ai->second);
-      ctx->analysis.erase(ai);
-    } else if (ri != ctx->resampler.end()) {
-      rs = std::move(ri->second);
-      ctx->resampler.erase(ri);
-    } else {
-      auto vi = ctx->hifi.find(model);
-      if (vi == ctx->hifi.end()) return fail(MI355TTS_ERR_NO_MODEL, "no model %d", model);
-      v = std::move(vi->second);
-      ctx->hifi.erase(vi);
-    }
+    auto it = ctx->models.find(model);
+    if (it == ctx->models.end()) return fail(MI355TTS_ERR_NO_MODEL, "no model %d", model);
+    dropped = std::move(it->second.model);
+    ctx->models.erase(it);
   }
-  return 0;  // g / v / gl / an / rs released outside the lock (hipFree synchronises the device)
+  return 0;  // `dropped` is released outside the lock (hipFree synchronises the device)
 }
 
 // §8(e): the one collective of the path.  The library does not link RCCL: the entry point is resolved from the
@@ -269,13 +248,11 @@ extern "C" int mi355tts_broadcast_weights(mi355tts_ctx* ctx, void* nccl_comm, in
   bcast_fn bcast = (bcast_fn)dlsym(lib, "ncclBroadcast");
   errstr_fn errstr = (errstr_fn)dlsym(lib, "ncclGetErrorString");
   if (!bcast) return fail(MI355TTS_ERR_INVALID, "ncclBroadcast not found in the RCCL library");
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
-  const int rc = bcast(device_blob, device_blob, (size_t)numel, /*ncclFloat32*/ 7, root, nccl_comm, w->stream);
+  CallFrame f(ctx);
+  CHECK(f.open());
+  const int rc = bcast(device_blob, device_blob, (size_t)numel, /*ncclFloat32*/ 7, root, nccl_comm, f.s);
   if (rc != 0) return fail(MI355TTS_ERR_HIP, "ncclBroadcast failed: %s", errstr ? errstr(rc) : "?");
-  HIPCHECK(mi355_sync(w->stream));
+  HIPCHECK(f.wait());
   return 0;
 }
 
@@ -285,20 +262,22 @@ extern "C" int mi355tts_model_set_precision(mi355tts_ctx* ctx, int model, int pr
       precision != MI355TTS_PRECISION_F16)
     return fail(MI355TTS_ERR_INVALID, "unknown precision %d", precision);
   std::lock_guard<std::mutex> lk(ctx->mu);
-  auto v = ctx->hifi.find(model);
-  if (v != ctx->hifi.end()) {
-    if (precision == MI355TTS_PRECISION_F16 && !v->second->f16_ok)
-      return fail(MI355TTS_ERR_INVALID, "fp16 mode is not available for this vocoder: %s", v->second->f16_why.c_str());
-    v->second->precision.store(precision);
+  auto it = ctx->models.find(model);
+  const char* kind = it == ctx->models.end() ? nullptr : it->second.kind;
+  if (kind == HifiModel::missing) {
+    HifiModel* hm = static_cast<HifiModel*>(it->second.model.get());
+    if (precision == MI355TTS_PRECISION_F16 && !hm->f16_ok)
+      return fail(MI355TTS_ERR_INVALID, "fp16 mode is not available for this vocoder: %s", hm->f16_why.c_str());
+    hm->precision.store(precision);
     return 0;
   }
   // GlowTTS: MI355TTS_PRECISION_F16 puts the decoder's WaveNets — 84 % of the acoustic model's FLOPs, 97 of its ~140 launches —
   // on the fp16 matrix cores (wn_f16.h) where the geometry is covered; the split-bf16 requests, and F16 on a geometry the
   // kernel is not built for, are REPORTED as having no effect (a distinct positive status: not an error, not a silent success)
-  auto gi = ctx->glow.find(model);
-  if (gi != ctx->glow.end()) {
-    if (precision == MI355TTS_PRECISION_F32 || (precision == MI355TTS_PRECISION_F16 && gi->second->f16_ok)) {
-      gi->second->precision.store(precision);
+  if (kind == GlowModel::missing) {
+    GlowModel* gm = static_cast<GlowModel*>(it->second.model.get());
+    if (precision == MI355TTS_PRECISION_F32 || (precision == MI355TTS_PRECISION_F16 && gm->f16_ok)) {
+      gm->precision.store(precision);
       return 0;
     }
     return MI355TTS_PRECISION_NOOP;
@@ -410,44 +389,35 @@ static int mel_alloc(mi355tts_ctx* ctx, int B, int M, int ld, mi355tts_mel** out
 extern "C" int mi355tts_mel_from_buffer(mi355tts_ctx* ctx, const float* mel, const int32_t* frames, int B, int M, int ld,
                                         const mi355tts_audio_settings* audio, uint32_t flags, mi355tts_mel** out) {
   if (!ctx || !mel || !frames || !out || B <= 0 || M <= 0 || ld < 0) return fail(MI355TTS_ERR_INVALID, "bad argument");
-  HIPCHECK(hipSetDevice(ctx->device));
   int mx = 0;
   for (int b = 0; b < B; ++b) {
     if (frames[b] < 0 || frames[b] > ld) return fail(MI355TTS_ERR_INVALID, "frames[%d]=%d outside [0,%d]", b, frames[b], ld);
     mx = std::max(mx, frames[b]);
   }
-  mi355tts_mel* m = nullptr;
+  CallFrame f(ctx);
+  CHECK(f.open());
   const int ldp = (ld + 3) & ~3;
-  CHECK(mel_alloc(ctx, B, M, ldp, &m));
+  CHECK(mel_alloc(ctx, B, M, ldp, &f.mel));
+  mi355tts_mel* m = f.mel;
   m->max_frames = mx;
   for (int b = 0; b < B; ++b) m->frames[b] = frames[b];
-  Worker* w = nullptr;
-  int rc = acquire_worker(ctx, &w);
-  if (rc) {
-    mel_destroy(m);
-    return rc;
-  }
-  WorkerGuard guard{ctx, w};
   const size_t n = (size_t)B * M * ldp;
-  hipError_t e = hipMemcpyAsync(m->frames_dev, frames, sizeof(int) * B, hipMemcpyHostToDevice, w->stream);
-  if (e == hipSuccess && n) e = hipMemsetAsync(m->raw, 0, n * sizeof(float), w->stream);
+  hipError_t e = hipMemcpyAsync(m->frames_dev, frames, sizeof(int) * B, hipMemcpyHostToDevice, f.s);
+  if (e == hipSuccess && n) e = hipMemsetAsync(m->raw, 0, n * sizeof(float), f.s);
   if (e == hipSuccess && n)
     e = hipMemcpy2DAsync(m->raw, sizeof(float) * ldp, mel, sizeof(float) * ld, sizeof(float) * ld, (size_t)B * M,
-                         (flags & MI355TTS_IN_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, w->stream);
+                         (flags & MI355TTS_IN_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, f.s);
   if (e == hipSuccess && n) {
     if (audio) {
-      hipLaunchKernelGGL(mel_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, w->stream, m->raw, m->voc,
+      hipLaunchKernelGGL(mel_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, f.s, m->raw, m->voc,
                          (long long)n, to_mt(audio));
     } else {
-      e = hipMemcpyAsync(m->voc, m->raw, n * sizeof(float), hipMemcpyDeviceToDevice, w->stream);
+      e = hipMemcpyAsync(m->voc, m->raw, n * sizeof(float), hipMemcpyDeviceToDevice, f.s);
     }
   }
-  if (e == hipSuccess) e = mi355_sync(w->stream);
-  if (e != hipSuccess) {
-    mel_destroy(m);
-    return fail(MI355TTS_ERR_HIP, "mel_from_buffer: %s", hipGetErrorString(e));
-  }
-  *out = m;
+  if (e == hipSuccess) e = f.wait();
+  if (e != hipSuccess) return fail(MI355TTS_ERR_HIP, "mel_from_buffer: %s", hipGetErrorString(e));
+  *out = f.take_mel();
   return 0;
 }
 
@@ -469,14 +439,13 @@ static int synthesize_impl(mi355tts_ctx* ctx, int glow, int vocoder, const GlowC
   if (!ctx || !frames_out) return fail(MI355TTS_ERR_INVALID, "null argument");
   std::shared_ptr<GlowModel> gpin;
   std::shared_ptr<HifiModel> vpin;
-  CHECK(find_glow(ctx, glow, &gpin));
-  CHECK(find_hifi(ctx, vocoder, &vpin));
+  CHECK(find_model(ctx, glow, &gpin));
+  CHECK(find_model(ctx, vocoder, &vpin));
   const GlowModel* gm = gpin.get();
   HifiModel* hm = vpin.get();
   int Pmax = 0;
   CHECK(glow_precheck(gm, g, &Pmax));
   CHECK(hifigan_precheck(ctx, hm, vocoder, nullptr, g.B, gm->hp.mel_channels, -1, v));  // incl. the one-time denoiser bias
-  HIPCHECK(hipSetDevice(ctx->device));
   // (decided before a worker, and with it a CallOptions, exists: the one place that reads these options off the context)
   const int lanes = g_env.call_coalesce_off ? 0 : ctx->opts.call_coalesce.load();
   if (lanes > 0 && g.B == 1 && !g.noise && !g.speaker_ids && !g.has_prosody() && g.id_lens[0] <= ATTM_MAXP && ctx->opts.voc_out.load() && !ctx->opts.serial_branches.load()) {
@@ -620,8 +589,8 @@ extern "C" int mi355tts_reserve(mi355tts_ctx* ctx, int workers, int glow, int vo
     return fail(MI355TTS_ERR_INVALID, "bad argument");
   std::shared_ptr<GlowModel> gpin;
   std::shared_ptr<HifiModel> vpin;
-  if (glow > 0) CHECK(find_glow(ctx, glow, &gpin));
-  if (vocoder > 0) CHECK(find_hifi(ctx, vocoder, &vpin));
+  if (glow > 0) CHECK(find_model(ctx, glow, &gpin));
+  if (vocoder > 0) CHECK(find_model(ctx, vocoder, &vpin));
   const GlowModel* gm = gpin.get();
   HifiModel* hm = vpin.get();
   if (gm && max_frames % gm->hp.n_sqz) max_frames += gm->hp.n_sqz - max_frames % gm->hp.n_sqz;
@@ -702,7 +671,12 @@ static int op_conv_common(mi355tts_ctx* ctx, const float* x, int B, int Cin, int
                           bool transposed) {
   if (!ctx || !x || !wt || !y || B <= 0 || Cin <= 0 || Cout <= 0 || L <= 0 || K <= 0)
     return fail(MI355TTS_ERR_INVALID, "bad argument");
-  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<int> hl(B, L);
+  if (lens)
+    for (int b = 0; b < B; ++b) {
+      if (lens[b] < 0 || lens[b] > L) return fail(MI355TTS_ERR_INVALID, "lens[%d] out of range", b);
+      hl[b] = lens[b];
+    }
   ArenaBuilder ab;
   DevConv c;
   int Lout = L;
@@ -715,9 +689,10 @@ static int op_conv_common(mi355tts_ctx* ctx, const float* x, int B, int Cin, int
     if (!(K % 2)) return fail(MI355TTS_ERR_INVALID, "conv1d needs an odd kernel size");
     c = add_conv(ab, wt, bias, Cout, Cin, K, ROWS_PLAIN);
   }
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
+  CallFrame f(ctx);
+  CHECK(f.open());
+  Worker* w = f.w;
+  hipStream_t s = f.s;
   Carver cv;
   const WorkerWeights ww(ab, cv);
   const int Lp = (L + 3) & ~3;
@@ -729,17 +704,10 @@ static int op_conv_common(mi355tts_ctx* ctx, const float* x, int B, int Cin, int
   float* dx = (float*)(base + o_x);
   float* dy = (float*)(base + o_y);
   int* dl = (int*)(base + o_l);
-  hipStream_t s = w->stream;
   CHECK(ww.copy_and_bind(w, &c, 1));
   HIPCHECK(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)B * Cin * Lp, s));
   HIPCHECK(hipMemcpy2DAsync(dx, sizeof(float) * Lp, x, sizeof(float) * L, sizeof(float) * L, (size_t)B * Cin, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemsetAsync(dy, 0, sizeof(float) * (size_t)B * Cout * Lout, s));
-  std::vector<int> hl(B, L);
-  if (lens)
-    for (int b = 0; b < B; ++b) {
-      if (lens[b] < 0 || lens[b] > L) return fail(MI355TTS_ERR_INVALID, "lens[%d] out of range", b);
-      hl[b] = lens[b];
-    }
   HIPCHECK(hipMemcpyAsync(dl, hl.data(), sizeof(int) * B, hipMemcpyHostToDevice, s));
   int rc;
   if (transposed) {
@@ -758,9 +726,7 @@ static int op_conv_common(mi355tts_ctx* ctx, const float* x, int B, int Cin, int
   }
   if (rc) return rc;
   HIPCHECK(hipMemcpyAsync(y, dy, sizeof(float) * (size_t)B * Cout * Lout, hipMemcpyDeviceToHost, s));
-  HIPCHECK(mi355_sync(s));
-  HIPCHECK(hipGetLastError());
-  return 0;
+  return f.finish();
 }
 
 extern "C" int mi355tts_op_conv1d(mi355tts_ctx* ctx, const float* x, int B, int Cin, int L, const int32_t* lens,
@@ -777,10 +743,10 @@ extern "C" int mi355tts_op_denoise(mi355tts_ctx* ctx, const float* wav, int B, i
                                    float strength, float* out) {
   if (!ctx || !wav || !bias_spec || !out || B <= 0 || N <= DN_FFT || (N % DN_HOP))
     return fail(MI355TTS_ERR_INVALID, "bad argument (N must be a multiple of 256 and > 1024)");
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
+  CallFrame f(ctx);
+  CHECK(f.open());
+  Worker* w = f.w;
+  hipStream_t s = f.s;
   const int T = (int)((N - DN_FFT + DN_HOP - 1) / DN_HOP);
   Carver cv;
   const size_t o_in = cv.take(sizeof(float) * (size_t)B * N);
@@ -795,7 +761,6 @@ extern "C" int mi355tts_op_denoise(mi355tts_ctx* ctx, const float* wav, int B, i
   float* fb = (float*)(base + o_f);
   float* db = (float*)(base + o_b);
   int* dfr = (int*)(base + o_fr);
-  hipStream_t s = w->stream;
   std::vector<int> fr(B, (int)(N / DN_HOP));
   HIPCHECK(hipMemcpyAsync(din, wav, sizeof(float) * (size_t)B * N, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemcpyAsync(db, bias_spec, sizeof(float) * (DN_FFT / 2 + 1), hipMemcpyHostToDevice, s));
@@ -804,32 +769,25 @@ extern "C" int mi355tts_op_denoise(mi355tts_ctx* ctx, const float* wav, int B, i
                      (float*)nullptr);
   hipLaunchKernelGGL(overlap_add_kernel, dim3(256, B), dim3(256), 0, s, fb, T, dfr, DN_HOP, dout, (long long)N, (long long)N);
   HIPCHECK(hipMemcpyAsync(out, dout, sizeof(float) * (size_t)B * N, hipMemcpyDeviceToHost, s));
-  HIPCHECK(mi355_sync(s));
-  HIPCHECK(hipGetLastError());
-  return 0;
+  return f.finish();
 }
 
 extern "C" int mi355tts_op_gauss_noise(mi355tts_ctx* ctx, uint64_t seed, int B, int C, int T, float* out) {
   if (!ctx || !out || B <= 0 || C <= 0 || T <= 0 || C > 65535 || B > 65535) return fail(MI355TTS_ERR_INVALID, "bad argument");
-  HIPCHECK(hipSetDevice(ctx->device));
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
+  CallFrame f(ctx);
+  CHECK(f.open());
   const size_t n = (size_t)B * C * T;
-  CHECK(reserve(w, n * sizeof(float)));
-  float* d = (float*)w->arena;
-  hipLaunchKernelGGL(noise_fill_kernel, dim3((T + 255) / 256, C, B), dim3(256), 0, w->stream, d, C, T, seed);
-  HIPCHECK(hipMemcpyAsync(out, d, n * sizeof(float), hipMemcpyDeviceToHost, w->stream));
-  HIPCHECK(mi355_sync(w->stream));
-  HIPCHECK(hipGetLastError());
-  return 0;
+  CHECK(reserve(f.w, n * sizeof(float)));
+  float* d = (float*)f.w->arena;
+  hipLaunchKernelGGL(noise_fill_kernel, dim3((T + 255) / 256, C, B), dim3(256), 0, f.s, d, C, T, seed);
+  HIPCHECK(hipMemcpyAsync(out, d, n * sizeof(float), hipMemcpyDeviceToHost, f.s));
+  return f.finish();
 }
 
 extern "C" int mi355tts_bench_conv1d(mi355tts_ctx* ctx, int B, int Cin, int Cout, int K, int dilation, int L,
                                      int tile_shape, int iters, float* ms_per_launch) {
   if (!ctx || !ms_per_launch || B <= 0 || Cin <= 0 || Cout <= 0 || L <= 0 || iters <= 0 || !(K % 2) || (L % 4))
     return fail(MI355TTS_ERR_INVALID, "bad argument (L must be a multiple of 4)");
-  HIPCHECK(hipSetDevice(ctx->device));
   std::vector<float> wh((size_t)Cout * Cin * K), bh(Cout), xh((size_t)B * Cin * L);
   uint32_t st = 12345u;
   auto rnd = [&]() {
@@ -842,9 +800,10 @@ extern "C" int mi355tts_bench_conv1d(mi355tts_ctx* ctx, int B, int Cin, int Cout
   for (auto& v : xh) v = rnd();
   ArenaBuilder ab;
   DevConv c = add_conv(ab, wh.data(), bh.data(), Cout, Cin, K, ROWS_PLAIN);
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
+  CallFrame f(ctx);
+  CHECK(f.open());
+  Worker* w = f.w;
+  hipStream_t s = f.s;
   Carver cv;
   const WorkerWeights ww(ab, cv);
   const size_t o_x = cv.take(sizeof(float) * xh.size());
@@ -853,7 +812,6 @@ extern "C" int mi355tts_bench_conv1d(mi355tts_ctx* ctx, int B, int Cin, int Cout
   char* base = w->arena;
   float* dx = (float*)(base + o_x);
   float* dy = (float*)(base + o_y);
-  hipStream_t s = w->stream;
   CHECK(ww.copy_and_bind(w, &c, 1));
   HIPCHECK(hipMemcpyAsync(dx, xh.data(), sizeof(float) * xh.size(), hipMemcpyHostToDevice, s));
   ConvArgs a = base_args(dx, (long long)Cin * L, L, nullptr, 1, dy, (long long)Cout * L, L, nullptr, 1, dilation,
@@ -873,7 +831,7 @@ extern "C" int mi355tts_bench_conv1d(mi355tts_ctx* ctx, int B, int Cin, int Cout
     hipEventRecord(e0, s);
     for (int i = 0; i < iters && !rc; ++i) rc = launch_conv(ctx, w, c, a, EPI_LINEAR, B, L, KC_RESBLOCK);
     hipEventRecord(e1, s);
-    hipError_t e = mi355_sync(s);
+    hipError_t e = f.wait();
     float ms = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
     if (e != hipSuccess) rc = fail(MI355TTS_ERR_HIP, "bench_conv1d: %s", hipGetErrorString(e));
@@ -907,7 +865,6 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
     const bool emu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && std::strncmp(prop.gcnArchName, "hipemu", 6) == 0;
     if (now.selfcheck_off || emu) return 0;  // (the CPU emulator build of the tests: nothing to measure)
   }
-  HIPCHECK(hipSetDevice(ctx->device));
   const int C = 256, L = 78 * 64;
   const int Ks[3] = {11, 7, 3};
   ArenaBuilder ab;
@@ -923,9 +880,10 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
     for (auto& v : wh) v = rnd() * sc;
     cv[m] = add_conv(ab, wh.data(), bh.data(), C, C, Ks[m], ROWS_PLAIN);
   }
-  Worker* w = nullptr;
-  CHECK(acquire_worker(ctx, &w));
-  WorkerGuard guard{ctx, w};
+  CallFrame f(ctx);
+  CHECK(f.open());
+  Worker* w = f.w;
+  hipStream_t s = f.s;
   Carver cvr;
   const WorkerWeights ww(ab, cvr);
   const size_t o_x = cvr.take(sizeof(float) * (size_t)C * L);
@@ -934,7 +892,6 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
   CHECK(reserve(w, cvr.pos));
   char* base = w->arena;
   float* dx = (float*)(base + o_x);
-  hipStream_t s = w->stream;
   CHECK(ww.copy_and_bind(w, cv, 3));
   HIPCHECK(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)C * L, s));
   ConvPlan plans[3];
@@ -980,6 +937,7 @@ static int dispatch_selfcheck_run(mi355tts_ctx* ctx) {
     if (e1) hipEventDestroy(e1);
   }
   if (rc != 0) return rc < 0 ? rc : 0;  // state becomes 3: skipped
+  f.done = true;  // every timed pair above ended with a wait
   ctx->selfcheck_plain_us = us[0];
   ctx->selfcheck_snake_us = us[1];
   if (us[1] > 1.02f * us[0]) {

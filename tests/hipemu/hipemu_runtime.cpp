@@ -139,7 +139,13 @@ static int worker_count() {
   return std::max(1, std::min(n, 64));
 }
 
+// Stream operations issued since the last host wait (kernel launches, *Async copies and memsets), process-wide.  The emulator
+// runs them at once, so nothing is ever really pending: the count shows whether the host code WOULD have returned with work
+// still queued on a device (hipemu_pending_ops).
+std::atomic<long> g_pending{0};
+
 void launch(dim3 grid, dim3 block, size_t /*shmem*/, const std::function<void()>& body) {
+  g_pending.fetch_add(1, std::memory_order_relaxed);
   const size_t nblocks = (size_t)grid.x * grid.y * grid.z;
   const int nthreads = (int)(block.x * block.y * block.z);
   if (nblocks == 0 || nthreads == 0) return;
@@ -250,13 +256,17 @@ hipError_t hipHostMalloc(void** p, size_t n, unsigned) {
 }
 hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) std::memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { if (n) std::memmove(d, s, n); return hipSuccess; }
+static hipError_t issued() { hipemu::g_pending.fetch_add(1, std::memory_order_relaxed); return hipSuccess; }
+static hipError_t waited(hipError_t e) { hipemu::g_pending.store(0, std::memory_order_relaxed); return e; }
+extern "C" long hipemu_pending_ops() { return hipemu::g_pending.load(std::memory_order_relaxed); }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { if (n) std::memmove(d, s, n); return issued(); }
 hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t) {
+  issued();
   for (size_t r = 0; r < height; ++r) std::memmove((char*)d + r * dpitch, (const char*)s + r * spitch, width);
   return hipSuccess;
 }
 hipError_t hipMemset(void* d, int v, size_t n) { if (n) std::memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { if (n) std::memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { if (n) std::memset(d, v, n); return issued(); }
 struct hipemuStream { int id; };
 struct hipemuEvent { std::chrono::steady_clock::time_point t; };
 hipError_t hipStreamCreate(hipStream_t* s) { *s = new hipemuStream{1}; return hipSuccess; }
@@ -268,14 +278,14 @@ hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) {
   return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipemu_check_guards() ? hipErrorUnknown : hipSuccess; }
-hipError_t hipDeviceSynchronize() { return hipemu_check_guards() ? hipErrorUnknown : hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) { return waited(hipemu_check_guards() ? hipErrorUnknown : hipSuccess); }
+hipError_t hipDeviceSynchronize() { return waited(hipemu_check_guards() ? hipErrorUnknown : hipSuccess); }
 hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipemuEvent{}; return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }  // kernels run synchronously at launch
+hipError_t hipStreamQuery(hipStream_t) { return waited(hipSuccess); }  // kernels run synchronously at launch
 hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t) { return waited(hipSuccess); }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
   *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();
   return hipSuccess;

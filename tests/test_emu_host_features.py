@@ -2,6 +2,7 @@
 `mi355tts_synthesize` call, device-side pause padding, `mi355tts_reserve`, the
 load-adaptive vocoder schedule, unusual-but-legal vocoder configurations and
 hyper-parameter validation (round-1 advisor findings)."""
+import ctypes as C
 import dataclasses
 import threading
 
@@ -11,7 +12,8 @@ import pytest
 from larynx_amd import ffi
 from larynx_amd import hparams as HP
 from larynx_amd import synthetic
-from larynx_amd.audio import ljspeech_audio_settings
+from larynx_amd.audio import ljspeech_audio_settings, mel_basis
+from larynx_amd.resample import design_lowpass
 from oracle import audio_np, glow_tts_np, hifi_gan_np
 
 
@@ -889,3 +891,111 @@ def test_counts_of_two_contexts_on_one_thread(emu_library):
     assert counts_b == counts_f == counts_a
     assert prof_b == prof_f and all(acc["launches"] == 0 for acc in prof_b.values()) and kern_b == kern_f == {}
     assert np.array_equal(wav_b, wav_f) and np.array_equal(wav_b, wav_a)
+
+
+def refused(eng, code, call):
+    with pytest.raises(ffi.Mi355ttsError) as e:
+        call()
+    assert e.value.code == code, e.value
+
+
+def synthesize_too_small(eng, g, v, ids):
+    """`mi355tts_synthesize` into an output row of 8 samples: TOO_SMALL, with the frame counts reported."""
+    lens = np.array([len(ids)], np.int32)
+    frames = np.zeros(1, np.int32)
+    i16 = np.zeros((1, 8), np.int16)
+    i32 = C.POINTER(C.c_int32)
+    rc = eng.lib.mi355tts_synthesize(eng._ctx, g, v, ids.ctypes.data, lens.ctypes.data_as(i32), 1, len(ids), 0.667, 1.0, None, 0, 5, None, 0.0,
+                                     0, 0, frames.ctypes.data_as(i32), None, i16.ctypes.data, 8, 0)
+    assert rc == -4 and int(frames[0]) > 0
+    return frames
+
+
+def check_refusals_leave_the_worker_clean(eng, g, v, num_symbols, num_mels, after=lambda what: None):
+    """The three refusals that arrive after a call has queued work — conv1d with a tap count no tile is built for, a fused
+    call whose output row is too small, explicit noise of too few columns — and, behind each, two calls made before on the
+    same engine: the same bits.  `after(what)` runs behind every call (the emulator test reads its pending-operation count
+    there).  Returns what the two calls gave."""
+    rng = np.random.default_rng(53)
+    ids = synthetic.synthetic_phoneme_ids(rng, 13, num_symbols)
+    x = rng.standard_normal((1, 32, 64)).astype(np.float32)
+    w3 = (rng.standard_normal((32, 32, 3)) / 10).astype(np.float32)
+    w9 = (rng.standard_normal((32, 32, 9)) / 17).astype(np.float32)
+    s = ljspeech_audio_settings()
+
+    def good(what):
+        y = eng.conv1d(x, w3, in_slope=0.1)
+        after(what + ": conv1d")
+        out = eng.synthesize(g, v, ids, 0.667, 1.0, seed=5, audio_settings=s, want_float=True)
+        after(what + ": synthesize")
+        return (y,) + tuple(out)
+
+    first = good("before")
+    refusals = {
+        "conv1d K = 9": lambda: refused(eng, -1, lambda: eng.conv1d(x, w9)),
+        "synthesize, row too small": lambda: synthesize_too_small(eng, g, v, ids),
+        "glow_infer, noise too short": lambda: refused(eng, -4, lambda: eng.glow_infer(g, ids, 0.667, 1.0, noise=np.zeros((num_mels, 4), np.float32))),
+    }
+    for what, refusal in refusals.items():
+        refusal()
+        after(what)
+        again = good("after " + what)
+        assert all(np.array_equal(a, b) for a, b in zip(first, again)), what
+    return first
+
+
+def test_every_call_ends_with_nothing_queued(emu_engine, emu_library, tiny):
+    """An entry point hands its worker back (and a mel's blocks to the pool) only with nothing of its own still queued: the
+    emulator counts the stream operations issued since the last host wait (`hipemu_pending_ops`), and that count is 0 after
+    one successful call of every entry point and after each refusal that arrives behind queued work."""
+    eng, g, v = emu_engine, tiny["g"], tiny["v"]
+    num_mels, hop = HP.TINY_HIFIGAN.num_mels, HP.TINY_HIFIGAN.hop
+    pending = C.CDLL(str(emu_library)).hipemu_pending_ops
+    pending.restype = C.c_long
+
+    def drained(what):
+        assert pending() == 0, what
+
+    rng = np.random.default_rng(59)
+    ids = synthetic.synthetic_phoneme_ids(rng, 13, HP.TINY_GLOW.num_symbols)
+    mel = eng.glow_infer(g, ids, 0.667, 1.0, seed=3, audio_settings=ljspeech_audio_settings())
+    drained("glow_infer")
+    eng.hifigan_infer(v, mel)
+    drained("hifigan_infer to the host")
+    n = mel.max_frames * hop
+    dev = np.zeros((1, n), np.float32)
+    eng.hifigan_infer_raw(v, mel, dev.ctypes.data, None, n, flags=ffi.OUT_DEVICE)
+    drained("hifigan_infer to OUT_DEVICE")
+    empty = eng.mel_from_numpy(np.zeros((1, num_mels, 4), np.float32), frames=np.zeros(1, np.int32))
+    drained("mel_from_numpy")
+    for flags in (0, ffi.OUT_DEVICE):
+        eng.hifigan_infer_raw(v, empty, dev.ctypes.data, None, n, flags=flags)
+        drained("the empty hifigan_infer")
+    basis = mel_basis(22050, 1024, num_mels, 0.0, 8000)
+    gl = eng.load_griffin_lim(basis, iterations=2)
+    eng.griffin_lim_infer(gl, mel, want_int16=True, want_phase=True)
+    drained("griffin_lim_infer")
+    wav = (rng.standard_normal((2, 3000)) / 4).astype(np.float32)
+    an = eng.load_analysis(basis)
+    rec = eng.mel_from_audio(an, wav, samples=np.array([3000, 2100], np.int64))
+    drained("mel_from_audio")
+    taps, _ = design_lowpass(2, 3)
+    rs = eng.load_resampler(taps, 2, 3)
+    eng.resample(rs, wav, samples=np.array([3000, 2100], np.int64), want_int16=True, normalize=True)
+    drained("resample")
+    eng.glow_align(g, ids, mel)
+    drained("glow_align")
+    eng.maximum_path(rng.standard_normal((2, 5, 9)).astype(np.float32), id_lens=[5, 3], frames=[9, 6])
+    drained("op_maximum_path")
+    x = rng.standard_normal((2, 8, 10)).astype(np.float32)
+    eng.conv_transpose1d(x, (rng.standard_normal((8, 4, 4)) / 4).astype(np.float32), None, 2)
+    drained("conv_transpose1d")
+    eng.denoise((rng.standard_normal((1, 2048)) / 4).astype(np.float32), np.zeros(513, np.float32), 0.01)
+    drained("denoise")
+    eng.gauss_noise(7, 1, 4, 33)
+    drained("gauss_noise")
+    check_refusals_leave_the_worker_clean(eng, g, v, HP.TINY_GLOW.num_symbols, num_mels, after=drained)  # conv1d, synthesize + the refusals
+    for m in (gl, an, rs):
+        eng.unload(m)
+    for m in (mel, empty, rec):
+        m.free()

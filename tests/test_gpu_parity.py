@@ -1095,3 +1095,24 @@ def test_broadcast_weights_over_a_callers_rccl_communicator(gpu_engine):
             gpu_engine.broadcast_weights(0, 0, t.data_ptr(), blob.size)
     finally:
         rccl.ncclCommDestroy(comm)
+
+
+def test_refused_calls_leave_the_worker_clean_on_the_device():
+    """A context with ONE worker, so that every call runs on the worker the call before it gave back: the three refusals that
+    arrive behind queued work (conv1d with K = 9, a fused call into a row that is too small, explicit noise of too few
+    columns) are plain INVALID / TOO_SMALL returns, and conv1d (B = 1, 32 -> 32 channels, K = 3, L = 64) and a 13-id
+    `synthesize` behind each of them give the bits they gave before (the emulator suite's check, tiny models)."""
+    from larynx_amd.engine import Engine
+    from tests.test_emu_host_features import check_refusals_leave_the_worker_clean
+
+    eng = Engine(device=0)
+    try:
+        g = eng.load_glow(HP.TINY_GLOW, synthetic.make_glow_state_dict(HP.TINY_GLOW, seed=7))
+        v = eng.load_hifigan(HP.TINY_HIFIGAN, synthetic.make_hifigan_state_dict(HP.TINY_HIFIGAN, seed=7))
+        eng.reserve(1, g, v, max_batch=1, max_ids=16, max_frames=256)
+        assert len(eng.worker_queue_groups()) == 1
+        y, frames, f32, i16 = check_refusals_leave_the_worker_clean(eng, g, v, HP.TINY_GLOW.num_symbols, HP.TINY_HIFIGAN.num_mels)
+        assert int(frames[0]) > 0 and np.any(i16) and np.all(np.isfinite(f32)) and np.any(y)
+        assert len(eng.worker_queue_groups()) == 1  # no call ever found the worker taken
+    finally:
+        eng.close()
