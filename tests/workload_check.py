@@ -10,6 +10,7 @@ library itself shows (`kernel_signature`) and from where a stage's last tile is 
 tests/test_gpu_glow_sweep.py and tests/test_emu_glow_sweep.py."""
 import threading
 import time
+import zlib
 
 import numpy as np
 
@@ -122,6 +123,14 @@ TILE_WIDTHS = (
     ("pair_f16 TO", "f16", "f16pair", lambda C, K: (128 if C > 64 else 256) - (K - 1)),
     # conv_f16.h HPOST_TW
     ("HPOST_TW", "f16", "post", lambda C, K: 256),
+    # "bf16" = both reduced modes of the f32 schedule (split bf16 and plain bf16: the same tiles, another operand split).
+    # host_launch.h plan_conv: BF_A / BF_K / BF_C / BF_D are 128 columns wide (BF_B, 32 columns, only under MI355TTS_BF_K=0)
+    ("conv_bf16 128 columns", "bf16", "bf16conv", lambda C, K: 128),
+    # resblock_pair_bf16.h T2 = T1 - (K - 1), T1 = 32 * NB16 * WN16 = 256 (host_launch.h PAIR_TILES)
+    ("pair_bf16 T2", "bf16", "pair", lambda C, K: 256 - (K - 1)),
+    # the narrow stages and conv_post stay on their f32 kernels in these modes
+    ("mrf_small T", "bf16", "mrf", lambda C, K: 256),
+    ("POST_TW", "bf16", "post", lambda C, K: 256),
 )
 
 
@@ -148,7 +157,8 @@ def vocoder_tiles(hp, precision="f32"):
                     for k, d in chains:
                         out.append((f"{label} K={k}", i, width(C, k), (k - 1) * max(d) // 2))
                 continue
-            ok = {"conv": (C >= 128) if rb1 else True, "mrf": rb1 and C <= 16, "f16conv": (C > 128) if rb1 else True}[rule]
+            ok = {"conv": (C >= 128) if rb1 else True, "bf16conv": (C >= 128) if rb1 else True, "mrf": rb1 and C <= 16,
+                  "f16conv": (C > 128) if rb1 else True}[rule]
             if ok:
                 out.append((label, i, width(C, 3), halo_all))
     return sorted(set(out), key=lambda t: (t[1], t[2], t[0]))
@@ -585,6 +595,117 @@ def check_interior_columns_equal(eng, g, hp, F2, label=""):
     assert bad.size == 0, (label, "decoder columns differ in the interior: frames", (bad[:8] + reach).tolist(),
                            float(np.abs(a - b).max()))
     return a.shape[1] // hp.n_sqz
+
+
+# ---- the vocoder's counterpart: a constant mel gives a hop-periodic waveform ----------------------------------------
+# Every frame of the mel the same column: everything between mel and waveform is a convolution along time, a polyphase
+# transposed convolution or a pointwise function, the phase of a transposed convolution at output sample t depends on t modulo the
+# stage's cumulative rate, and every cumulative rate divides `hop`.  So samples t and t + hop, both further than the receptive field
+# from the two ends, are the same arithmetic on the same numbers in the same order whichever tile, wave or lane computes them, in
+# every precision: equal bit for bit.  A tile that stages too narrow a halo, reads a neighbour's or an uninitialised column,
+# masks a column too many at its end or deals a row the wrong tile origin breaks that at its seams.  No tolerance, no oracle.
+STFT_HOP, STFT_WIN = 256, 1024  # the denoiser's STFT (oracle/denoise_np.py): its frames repeat every 256 samples
+
+
+def vocoder_reach(hp, denoise=False):
+    """Samples from either end of the waveform past which a sample no longer sees the end: the receptive field of the generator,
+    from the hparams alone.  3 frames for conv_pre (k = 7); per upsampler i, with rest = hop / (u_0 ... u_i) samples per column of
+    its output, ((k_i - u_i) // 2 + u_i) columns for the transposed conv and h columns for its ResBlocks — h = the longest chain's
+    sum over its dilations of (K - 1) d / 2 (conv1) + (K - 1) / 2 (conv2, ResBlock1 only); 3 samples for conv_post (k = 7).  With
+    the denoiser, one STFT window and one STFT hop more."""
+    hop = hp.hop
+    rb1 = hp.resblock == "1"
+    reach, rest = 3 * hop, hop
+    for u, k in zip(hp.upsample_rates, hp.upsample_kernel_sizes):
+        rest //= u
+        h = max(sum((K - 1) * d // 2 + ((K - 1) // 2 if rb1 else 0) for d in ds)
+                for K, ds in zip(hp.resblock_kernel_sizes, hp.resblock_dilation_sizes))
+        reach += ((k - u) // 2 + u) * rest + h * rest
+    reach += 3
+    return reach + (STFT_WIN + STFT_HOP if denoise else 0)
+
+
+def blind_tiles(hp, precision="f32"):
+    """What check_hop_periodic cannot see: a seam that recurs at the same phase of every period shows the same error at t and
+    t + hop.  That is every tile of vocoder_tiles(hp, precision) whose width in samples (width * rest, rest = samples per column of
+    its stage) divides hop -> [(label, stage, width)].  ("bf16" = both bf16 modes.)"""
+    hop = hp.hop
+    out = []
+    for label, stage, width, _ in vocoder_tiles(hp, precision):
+        rest = hop // int(np.prod(hp.upsample_rates[: stage + 1]))
+        if hop % (width * rest) == 0:
+            out.append((label, stage, width))
+    return out
+
+
+def short_frames(hp, precision="f32"):
+    """The smallest frame count check_hop_periodic accepts (8 interior periods) whose interior also holds three whole stage-0
+    tiles of the widest stage-0 tile of vocoder_tiles(hp, precision) (the stage with the fewest columns per frame: the first to
+    run out of seams as F shrinks)."""
+    hop, u0 = hp.hop, hp.upsample_rates[0]
+    Rf = -(-vocoder_reach(hp) // hop)  # the reach in whole frames
+    w = max(width for _, stage, width, _ in vocoder_tiles(hp, precision) if stage == 0)
+    F = 2 * Rf + 8
+    while (F - Rf) * u0 // w - -(-Rf * u0 // w) < 3:
+        F += 1
+    return F
+
+
+def constant_mel(hp, rows):
+    """[B, num_mels, max(rows)]: row b = one column (0.57 + 0.06 randn, seeded by the geometry and b) repeated rows[b] times, 0
+    behind it."""
+    seed = zlib.crc32(repr(hp).encode())
+    mel = np.zeros((len(rows), hp.num_mels, max(rows)), F32)
+    for b, F in enumerate(rows):
+        col = (0.57 + 0.06 * np.random.default_rng(seed + b).standard_normal(hp.num_mels)).astype(F32)
+        mel[b, :, :F] = col[:, None]
+    return mel
+
+
+def check_hop_periodic(eng, v, vhp, F, *, rows=None, denoise=0.0, label=""):
+    """One vocoder call on a constant mel of F frames (`rows`: a ragged batch of these frame counts, another column per row).  Per
+    row, with n = frames * hop, R = vocoder_reach rounded up to whole hops and the period P = hop (with the denoiser: the least
+    common multiple of hop and the STFT's hop): samples [R, n - R - P) equal samples [R + P, n - R) bit for bit, float and int16;
+    the interior [R, n - R) holds at least 8 periods (a shorter F is refused); the interior's first period is not flat and
+    nowhere at +-1.0 (a saturated waveform would be periodic whatever the kernels do); the tail past n is 0.  Returns the
+    kernel signature of the call."""
+    hop = vhp.hop
+    rows = [int(F)] if rows is None else [int(f) for f in rows]
+    P = int(np.lcm(hop, STFT_HOP)) if denoise else hop
+    reach = vocoder_reach(vhp, bool(denoise))
+    R = -(-reach // hop) * hop
+    for f in rows:
+        if (f * hop - 2 * R) // P < 8:
+            raise ValueError(f"{label}: {f} frames leave fewer than 8 periods of {P} samples between the two reaches of {R}")
+    mb = eng.mel_from_numpy(constant_mel(vhp, rows), np.array(rows, np.int32))
+    try:
+        eng.profile_reset()
+        wav, i16 = eng.hifigan_infer(v, mb, denoiser_strength=float(denoise))
+        sig = kernel_signature(eng)
+    finally:
+        mb.free()
+    rest0 = hop // vhp.upsample_rates[0]
+    for b, f in enumerate(rows):
+        n = f * hop
+        tag = f"{label} F={f} " + ("B=1" if len(rows) == 1 else f"row {b} of B={len(rows)}")
+        assert np.all(wav[b, n:] == 0) and np.all(i16[b, n:] == 0), (tag, "samples past the row's end are not 0")
+        one = wav[b, R : R + P]
+        sd = float(one.std())
+        print(f"{tag}: n {n} reach {reach} interior [{R}, {n - R}) = {(n - 2 * R) // P} periods of {P}, period std {sd:.3e} "
+              f"peak {float(np.abs(one).max()):.3e}")
+        assert sd > 0.0 and np.all(np.isfinite(one)), (tag, "the period is flat", sd)
+        assert float(np.abs(one).max()) < 1.0, (tag, "the period touches +-1.0")
+        for name, x in (("float", wav[b]), ("int16", i16[b])):
+            lo, hi = x[R : n - R - P], x[R + P : n - R]
+            bad = np.flatnonzero(lo != hi)
+            if bad.size:
+                d = np.abs(lo[bad].astype(np.float64) - hi[bad].astype(np.float64))
+                first = (bad[:8] + R).tolist()
+                raise AssertionError(
+                    f"{tag}: {name} samples t and t + {P} differ at {bad.size} of {lo.size} interior samples; first t = {first} "
+                    f"(stage-0 columns {[t // rest0 for t in first]}, frames {[t // hop for t in first]}), last t = {int(bad[-1]) + R}, "
+                    f"largest difference {float(d.max()):.3e} at t = {int(bad[int(d.argmax())]) + R}")
+    return sig
 
 
 def choose_glow_lengths(sigs, must=(), edges=None, cap=16, label=""):
