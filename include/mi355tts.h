@@ -403,6 +403,59 @@ int mi355tts_resample(mi355tts_ctx* ctx, int model, const float* in_f32, const i
                       int64_t in_ld, float* out_f32, int16_t* out_i16, int64_t out_ld, int pcm_mode, int64_t* samples_out,
                       uint32_t flags);
 
+/* ---- loudness: a level target for the delivered rows ---------------------------
+ * The int16 rows the library delivers are peak-normalised sentence by sentence (the reference's rule, and the default).  This
+ * measures a row's ITU-R BS.1770-4 integrated loudness (mono) where the samples already are and delivers it at a target level
+ * under a sample-peak ceiling: FIVE launches measure, a SIXTH delivers, whatever N and B are (csrc/loudness.h).  The reference
+ * has no such step.
+ *   K-weighting:   two biquads in series, first the shelf and then the high-pass, each
+ *                    y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2],
+ *                  every row from zero state, no state across calls.  The ten coefficients are the caller's, passed in like any
+ *                  other table (larynx_amd.loudness.k_weighting(fs): the standard's 48 kHz filters re-derived for fs).
+ *   Blocks:        block j covers weighted samples [j hop, j hop + block) for every j with j hop + block <= N; z_j is their mean
+ *                  square, l_j = -0.691 + 10 log10 z_j.  block = round(0.4 fs) and hop = round(0.1 fs) are the caller's too.
+ *                  A row with 0 < N < block has ONE block, made of its N samples: BS.1770 gives such a row no value, and a
+ *                  sentence can be 0.3 s long.  This is this library's rule, not the standard's.
+ *   Gates:         absolute, l_j > -70; relative, l_j > -0.691 + 10 log10(mean of the absolutely gated z_j) - 10.  Both are
+ *                  decided on z itself: z_j > 10^((-70 + 0.691) / 10), and z_j > 0.1 x that mean.
+ *   Integrated:    L = -0.691 + 10 log10(mean of the z_j past both gates); -inf when no block passes the absolute gate or N = 0.
+ *   Gain:          g = 1 when target_lufs is NaN (measure only) or L = -inf.  Else g = 10^((target_lufs - L) / 20), then
+ *                  g = min(g, 10^(max_gain_db / 20)), then g = min(g, peak_ceiling / max|x|) when max|x| > 0; computed in f64,
+ *                  rounded to f32 once, and stepped down by an ulp where that rounding would carry max|x| * g past
+ *                  peak_ceiling.  The ceiling is on the SAMPLE peak, not the true peak: the signal between the samples may
+ *                  pass it.
+ *   Outputs:       out_f32[n] = x[n] * g (one f32 multiply); out_i16[n] = clamp(rintf(out_f32[n] * 32768), -32768, 32767), the
+ *                  rule of MI355TTS_PCM_SATURATE; every output row is zero-filled from its N up to out_ld.
+ *                  lufs_out / gain_out / peak_out (host [B], each or NULL): L, the linear g that was applied, max|x|.
+ *                  weighted_out ([B][in_ld], or NULL; a device pointer with MI355TTS_OUT_DEVICE, like out_f32 / out_i16): the
+ *                  K-weighted signal itself, N samples | zeros up to in_ld, so that a test can compare every sample.
+ *   Arithmetic:    the recurrence runs in f64 on the caller's f32 coefficients (widened), exactly decomposed: chunks of 64
+ *                  samples from zero state, their 4-element states carried across the chunk seams with the powers of the chunk
+ *                  transition matrix (computed at load time in double), then every chunk again from its true state.  The
+ *                  weighted samples are rounded to f32; the sums of their squares are f64, per hop-sized segment in a fixed
+ *                  order, a block is the sum of its segments; z_j and L are f32 values, g is computed in f64 and rounded once.
+ *                  The order of every sum is fixed by the row alone, not by the grid or B; no sum uses an atomic.  Row b of a
+ *                  batch gives the bits of its own batch-1 call; int16 input is converted as s * 2^-15 (exact) inside the launch
+ *                  and gives the bits of the equal f32 input; host and device pointers give the same bits.
+ * mi355tts_load_loudness: computes the transition-matrix powers and keeps them on the device; mi355tts_unload frees the model.
+ * mi355tts_loudness: exactly one of in_f32 / in_i16 [B][in_ld] (host, or device with MI355TTS_IN_DEVICE); row b holds samples[b]
+ * <= in_ld samples (host array).  out_f32 / out_i16 [B][out_ld] (host, or device with MI355TTS_OUT_DEVICE) are optional: a call
+ * with no output pointer at all is valid and measures only.  The workspace grows on demand (mi355tts_reserve does not cover this
+ * call).
+ * MI355TTS_ERR_INVALID with the reason (MI355TTS_ERR_NO_MODEL for an unknown id): null pointers; both inputs or neither; a
+ * non-finite coefficient; block < 1; hop < 1 or hop > block; samples[b] outside [0, in_ld] or above 2^24; out_ld below the
+ * longest row (when an output is asked for); peak_ceiling outside (0, 1]; a non-finite max_gain_db.
+ * Added in ABI version 2 (additive: the version number is unchanged). */
+typedef struct {
+  float shelf_b[3], shelf_a[2]; /* b0 b1 b2, a1 a2 (a0 = 1) */
+  float hp_b[3], hp_a[2];
+  int32_t block, hop;           /* 1 <= hop <= block */
+} mi355tts_loudness_params;
+int mi355tts_load_loudness(mi355tts_ctx* ctx, const mi355tts_loudness_params* params, int* model_out);
+int mi355tts_loudness(mi355tts_ctx* ctx, int model, const float* in_f32, const int16_t* in_i16, const int64_t* samples, int B,
+                      int64_t in_ld, float target_lufs, float peak_ceiling, float max_gain_db, float* out_f32, int16_t* out_i16,
+                      int64_t out_ld, float* lufs_out, float* gain_out, float* peak_out, float* weighted_out, uint32_t flags);
+
 /* ---- fused call: replaces the model half of _sentence_task -------------------
  * (larynx/__init__.py:229-283: phonemes_to_mels -> mel transforms -> mels_to_audio -> pause
  * padding) with ONE call on one stream: arguments as in mi355tts_glow_infer +
@@ -560,7 +613,9 @@ int mi355tts_profile_json(mi355tts_ctx* ctx, char* buf, int cap);
 int mi355tts_profile_kernels_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Launches per kernel NAME since the last mi355tts_profile_reset, {"rb_group_kernel": n, ...}; counted whether profiling is
  * on or not.  The class counters cannot tell a kernel from the fallback that would silently take its place (same launch count,
- * same bits by design): the device tests assert on these.  No reference counterpart (measurement only). */
+ * same bits by design): the device tests assert on these.  The first 44 keys and their order are fixed and always present,
+ * zero or not; the names of later entry points (the six loudness_*_kernel) follow them once they have launched since the last
+ * reset.  No reference counterpart (measurement only). */
 int mi355tts_kernel_counts_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Median elapsed time (microseconds) of `pairs` EMPTY event pairs on an idle stream: what the two hipEventRecord calls around a
  * profiled launch add to its event-timed duration (rocprofv3's kernel durations do not contain it). */

@@ -34,7 +34,7 @@ _LOGGER = logging.getLogger("larynx_amd")
 
 __all__ = [
     "AudioSettings", "InferenceBackend", "TextToSpeechResult", "load_tts_model", "load_vocoder_model",
-    "sentence_task", "sentence_task_aligned", "sentence_task_at_rate", "phonemes_to_speech",
+    "sentence_task", "sentence_task_aligned", "sentence_task_at_rate", "sentence_task_leveled", "phonemes_to_speech",
 ]
 
 
@@ -86,18 +86,30 @@ def sentence_task_at_rate(text: str, phoneme_ids, audio_settings, tts_model, tts
                      pause_before_ms, pause_after_ms, sample_rate)[0]
 
 
+def sentence_task_leveled(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                          pause_before_ms: int = 0, pause_after_ms: int = 0, sample_rate: typing.Optional[int] = None,
+                          loudness: typing.Optional[float] = None) -> np.ndarray:
+    """`sentence_task` delivered at `loudness` LUFS: the vocoder's FLOAT row, SSML pauses included (and resampled first when
+    `sample_rate` asks for another rate), is measured on the device (BS.1770 integrated loudness at the delivered rate) and
+    becomes int16 there at ONE gain, under a -1 dBFS sample-peak ceiling (`larynx_amd.loudness`).  This replaces the peak
+    normalisation for this call only; `loudness=None` is `sentence_task_at_rate`."""
+    return _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                     pause_before_ms, pause_after_ms, sample_rate, loudness)[0]
+
+
 def sentence_task_aligned(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
-                          pause_before_ms: int = 0, pause_after_ms: int = 0,
-                          sample_rate: typing.Optional[int] = None) -> typing.Tuple[np.ndarray, np.ndarray]:
+                          pause_before_ms: int = 0, pause_after_ms: int = 0, sample_rate: typing.Optional[int] = None,
+                          loudness: typing.Optional[float] = None) -> typing.Tuple[np.ndarray, np.ndarray]:
     """`sentence_task` that also returns where every phoneme id sounds: `(audio, spans)`, spans int64 [P, 2] in samples
     of `audio`, leading pause included (`larynx_amd.alignment.phoneme_spans`).  The TTS model must be one whose mels
     carry durations (`HipGlowTextToSpeech`); the audio is what `sentence_task` gives for the same settings.  With a
     Griffin-Lim vocoder the spans are nominal frame positions (hop 256), see `phoneme_spans`.  With `sample_rate` (see
-    `sentence_task_at_rate`) the spans are positions in the delivered audio: both ends scaled by (s * up) // down."""
+    `sentence_task_at_rate`) the spans are positions in the delivered audio: both ends scaled by (s * up) // down.  `loudness`
+    (see `sentence_task_leveled`) changes the level of the audio, not the spans."""
     settings = dict(tts_settings or {})
     settings["alignment"] = True
     audio, mels, before, resampler = _sentence(text, phoneme_ids, audio_settings, tts_model, settings, vocoder_model,
-                                               vocoder_settings, pause_before_ms, pause_after_ms, sample_rate)
+                                               vocoder_settings, pause_before_ms, pause_after_ms, sample_rate, loudness)
     from .alignment import phoneme_spans, scale_spans
 
     durations = getattr(mels, "durations", None)
@@ -134,7 +146,7 @@ def _float_row(vocoder_model, mels, vocoder_settings, before, after) -> np.ndarr
 
 
 def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
-              pause_after_ms, deliver_rate=None):
+              pause_after_ms, deliver_rate=None, deliver_lufs=None):
     """-> (audio, the mels the vocoder consumed, leading pause in samples at the voice's rate, the `Resampler` the audio went
     through or None)"""
     t0 = time.perf_counter()
@@ -156,7 +168,20 @@ def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocode
     t2 = time.perf_counter()
     resampler = _resampler_for(vocoder_model, audio_settings, deliver_rate)
     padded = getattr(vocoder_model, "mels_to_audio_padded", None)
-    if resampler is not None:
+    if deliver_lufs is not None:
+        # a level target: the float row, pauses included, at the delivered rate; measured, scaled and made int16 on the device
+        engine = getattr(vocoder_model, "engine", None)
+        if engine is None:
+            raise ValueError("loudness: the vocoder has no HIP engine to measure on")
+        from .loudness import get_loudness
+
+        row = _float_row(vocoder_model, mels, vocoder_settings, before, after)
+        if resampler is not None:
+            row = resampler.resample(row)
+            sample_rate = resampler.rate_out
+        audio = get_loudness(engine, sample_rate).normalize(row, target=float(deliver_lufs))
+        before = after = 0
+    elif resampler is not None:
         # another rate: the float row, pauses included, resampled on the device and normalised to int16 there
         audio = resampler.resample(_float_row(vocoder_model, mels, vocoder_settings, before, after), normalize=True)
         sample_rate = resampler.rate_out
@@ -192,13 +217,15 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
                        tts_settings: typing.Optional[SettingsType] = None,
                        vocoder_settings: typing.Optional[SettingsType] = None,
                        executor: typing.Optional[Executor] = None, alignment: bool = False,
-                       sample_rate: typing.Optional[int] = None) -> typing.Iterable[TextToSpeechResult]:
+                       sample_rate: typing.Optional[int] = None,
+                       loudness: typing.Optional[float] = None) -> typing.Iterable[TextToSpeechResult]:
     """`text_to_speech` (`larynx/__init__.py:47-190`) from the point where gruut /
     phonemes2ids have produced ids: one task per sentence on an executor, results
     yielded in submission order.  `alignment`: every result also carries `phoneme_spans`, the start and end sample
     of each phoneme id in its audio (`sentence_task_aligned`); the audio is the same either way.  `sample_rate`: deliver
     the audio at that rate instead of the voice's own (`sentence_task_at_rate`: resampled on the device, int16 of
-    ceil(n * up / down) samples, spans scaled to match); `None` or the voice's rate changes nothing."""
+    ceil(n * up / down) samples, spans scaled to match); `None` or the voice's rate changes nothing.  `loudness`: deliver
+    every sentence at that many LUFS instead of with its peak on 32767 (`sentence_task_leveled`); `None` changes nothing."""
     own = executor is None
     executor = executor or ThreadPoolExecutor()
     _ensure_pool_workers(executor, tts_model, vocoder_model)
@@ -209,6 +236,8 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
         if _resampler_for(vocoder_model, audio_settings, sample_rate) is not None:  # (made here, once, before the pool needs it)
             sr = int(sample_rate)
             task = functools.partial(sentence_task_aligned if alignment else sentence_task_at_rate, sample_rate=sr)
+        if loudness is not None:  # (the voice's own rate as `sample_rate` is no resampling)
+            task = functools.partial(sentence_task_aligned if alignment else sentence_task_leveled, sample_rate=sr, loudness=float(loudness))
         futures = []
         for text, ids in sentences:
             fut = executor.submit(task, text, np.asarray(ids, np.int64), audio_settings, tts_model, tts_settings,

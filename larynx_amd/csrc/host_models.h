@@ -423,6 +423,19 @@ struct ResamplerModel {
   }
 };
 
+// A loudness meter (loudness.h) is its ten coefficients, its block and hop, and the powers M^0 .. M^256 of the chunk transition
+// matrix (f64, computed at load time: loudness_forward.h)
+struct LoudnessModel {
+  static constexpr const char* missing = "no loudness meter %d";
+  mi355tts_loudness_params p;
+  int device = 0;
+  double* pw = nullptr;
+  ~LoudnessModel() {
+    DeviceScope ds(device);
+    if (pw) hipFree(pw);
+  }
+};
+
 static std::vector<std::pair<std::string, int64_t>> glow_manifest(const mi355tts_glow_hparams& h) {
   std::vector<std::pair<std::string, int64_t>> m;
   auto add = [&](const std::string& n, int64_t e) { m.emplace_back(n, e); };

@@ -26,7 +26,13 @@
   X(KN_POST_F16, "post_f16_kernel") X(KN_PACK_OCTETS, "pack_octets_kernel") X(KN_PAIR_F16_GROUP, "pair_f16_group_kernel") X(KN_WN_F16, "wn_f16_kernel") \
   X(KN_RB_GROUP_NB4, "rb_group_kernel.nb4") X(KN_GL_MAG, "griffin_lim_mag_kernel") X(KN_GL_INIT, "griffin_lim_init_kernel") X(KN_GL_ITER, "griffin_lim_iter_kernel") \
   X(KN_GL_OUT, "griffin_lim_out_kernel") X(KN_GL_INT16, "griffin_lim_int16_kernel") X(KN_GLOW_FWD, "glow_fwd_kernel") X(KN_ALIGN_SCORE, "align_score_kernel") \
-  X(KN_ALIGN_PATH, "align_path_kernel") X(KN_MEL_ANALYSIS, "mel_analysis_kernel") X(KN_ATTENTION_P768, "attention_mfma_kernel.p768") X(KN_ATTENTION_VALU, "attention_kernel")
+  X(KN_ALIGN_PATH, "align_path_kernel") X(KN_MEL_ANALYSIS, "mel_analysis_kernel") X(KN_ATTENTION_P768, "attention_mfma_kernel.p768") X(KN_ATTENTION_VALU, "attention_kernel") \
+  X(KN_LOUD_CHUNK, "loudness_chunk_kernel") X(KN_LOUD_CARRY, "loudness_carry_kernel") X(KN_LOUD_WEIGHT, "loudness_weight_kernel") \
+  X(KN_LOUD_SEGMENT, "loudness_segment_kernel") X(KN_LOUD_GATE, "loudness_gate_kernel") X(KN_LOUD_APPLY, "loudness_apply_kernel")
+// The first KN_PINNED names are always rendered by mi355tts_kernel_counts_json, zero or not: that key list and its order are
+// ABI.  A name behind them is rendered once it has launched since the last reset, so a caller that never uses the newer entry
+// points reads exactly the list it always read.
+constexpr int KN_PINNED = 44;
 #define MI355TTS_X_ID(id, str) id,
 #define MI355TTS_X_STR(id, str) str,
 enum KClass { MI355TTS_KCLASSES(MI355TTS_X_ID) KC_COUNT };
@@ -35,7 +41,7 @@ static const char* const kclass_name[KC_COUNT] = {MI355TTS_KCLASSES(MI355TTS_X_S
 static const char* const kname_name[KN_COUNT] = {MI355TTS_KNAMES(MI355TTS_X_STR)};
 #undef MI355TTS_X_ID
 #undef MI355TTS_X_STR
-static_assert(KC_COUNT == 7 && KN_COUNT == 44, "a new class or name goes at the END of its table (the JSON key order is ABI) and is counted here");
+static_assert(KC_COUNT == 7 && KN_COUNT == 50, "a new class or name goes at the END of its table (the JSON key order is ABI) and is counted here");
 
 // ------------------------------------------------------------------ what the scope works on
 struct ProfEvent {
@@ -171,7 +177,9 @@ static std::string kernel_counts_json(const ProfSums& p) {
   std::string s = "{";
   for (int i = 0; i < KN_COUNT; ++i) {
     char tmp[128];
-    std::snprintf(tmp, sizeof(tmp), "%s\"%s\": %lld", i ? ", " : "", kname_name[i], p.kn[i].load(std::memory_order_relaxed));
+    const long long n = p.kn[i].load(std::memory_order_relaxed);
+    if (i >= KN_PINNED && n == 0) continue;
+    std::snprintf(tmp, sizeof(tmp), "%s\"%s\": %lld", i ? ", " : "", kname_name[i], n);
     s += tmp;
   }
   return s + "}";

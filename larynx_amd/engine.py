@@ -688,6 +688,66 @@ class Engine:
         )
         return out
 
+    # ---- loudness ------------------------------------------------------------------
+    def load_loudness(self, shelf_b, shelf_a, hp_b, hp_a, block: int, hop: int) -> int:
+        """`mi355tts_load_loudness`: a BS.1770 meter from its K-weighting (two biquads: b0 b1 b2 and a1 a2 each, a0 = 1), its
+        block and its hop in samples (`larynx_amd.loudness.k_weighting`).  `unload` frees it."""
+        p = ffi.LoudnessParamsC()
+        for name, vals, n in (("shelf_b", shelf_b, 3), ("shelf_a", shelf_a, 2), ("hp_b", hp_b, 3), ("hp_a", hp_a, 2)):
+            vals = np.asarray(vals, np.float32).reshape(-1)
+            if vals.shape != (n,):
+                raise ValueError(f"{name}: {n} coefficients")
+            setattr(p, name, (C.c_float * n)(*vals.tolist()))
+        p.block, p.hop = int(block), int(hop)
+        model = C.c_int()
+        ffi.check(self.lib, self.lib.mi355tts_load_loudness(self._ctx, C.byref(p), C.byref(model)))
+        return int(model.value)
+
+    def loudness(self, model: int, audio: np.ndarray, samples=None, target: float = float("nan"), ceiling: float = 1.0,
+                 max_gain_db: float = 30.0, want_float: bool = False, want_int16: bool = False, want_weighted: bool = False) -> dict:
+        """`audio`: float32 or int16 (read as s / 32768), [N] or [B, N], row b valid for `samples[b]` entries (default: all) ->
+        {"lufs", "gain", "peak": float32 [B]; "f32", "i16", "weighted": [B, N] or None}.  `target` NaN measures only (gain 1);
+        rows are zero-filled behind their samples.  A 1-D input gives 1-D rows (the three per-row results stay [1])."""
+        audio = np.asarray(audio)
+        if audio.dtype != np.int16:
+            audio = audio.astype(np.float32, copy=False)
+        audio = np.ascontiguousarray(audio)
+        flat = audio.ndim == 1
+        if flat:
+            audio = audio[None]
+        if audio.ndim != 2:
+            raise ValueError("audio: [N] or [B, N]")
+        B, N = audio.shape
+        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        if n.shape != (B,):
+            raise ValueError("samples: one count per row")
+        f32 = np.empty((B, N), np.float32) if want_float else None
+        i16 = np.empty((B, N), np.int16) if want_int16 else None
+        wgt = np.empty((B, N), np.float32) if want_weighted else None
+        f_in, i_in = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
+        if N == 0:  # (an empty array has no address worth passing)
+            f_in, i_in = (None, np.zeros(1, np.int16).ctypes.data) if audio.dtype == np.int16 else (np.zeros(1, np.float32).ctypes.data, None)
+        lufs, gain, peak = self.loudness_raw(model, f_in, i_in, n, N, target, ceiling, max_gain_db, ffi.ptr(f32), ffi.ptr(i16), N,
+                                             ffi.ptr(wgt))
+        if flat:
+            f32, i16, wgt = (None if f32 is None else f32[0]), (None if i16 is None else i16[0]), (None if wgt is None else wgt[0])
+        return {"lufs": lufs, "gain": gain, "peak": peak, "f32": f32, "i16": i16, "weighted": wgt}
+
+    def loudness_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, target: float, ceiling: float, max_gain_db: float,
+                     out_f32_ptr=None, out_i16_ptr=None, out_ld: int = 0, weighted_ptr=None, flags: int = 0):
+        """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE); the output pointers
+        [B][out_ld] and the weighted rows [B][in_ld] are optional (device memory with ffi.OUT_DEVICE); returns the rows'
+        (lufs, gain, peak), float32 [B] each."""
+        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        res = np.zeros((3, len(n)), np.float32)
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_loudness(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+                                       float(target), float(ceiling), float(max_gain_db), out_f32_ptr, out_i16_ptr, int(out_ld),
+                                       res[0].ctypes.data, res[1].ctypes.data, res[2].ctypes.data, weighted_ptr, int(flags)),
+        )
+        return res[0], res[1], res[2]
+
     # ---- single operators ------------------------------------------------------
     def conv1d(self, x, w, bias=None, dilation=1, in_slope=1.0, out_act=0, lens=None) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

@@ -89,6 +89,13 @@ class ResamplerParamsC(C.Structure):
     _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("half_len", C.c_int32)]
 
 
+class LoudnessParamsC(C.Structure):
+    """`mi355tts_loudness_params`: the K-weighting's ten coefficients (shelf, then high-pass; a0 = 1), the block and the hop."""
+
+    _fields_ = [("shelf_b", C.c_float * 3), ("shelf_a", C.c_float * 2), ("hp_b", C.c_float * 3), ("hp_a", C.c_float * 2),
+                ("block", C.c_int32), ("hop", C.c_int32)]
+
+
 PCM_SATURATE = 0  # MI355TTS_PCM_*: clamp(rint(y * 32768)) / the reference's audio_float_to_int16 on the resampled row
 PCM_NORMALIZE = 1
 
@@ -177,6 +184,12 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
     "mi355tts_resample": (
         C.c_int,
         [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, _VP, _VP, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_uint32],
+    ),
+    "mi355tts_load_loudness": (C.c_int, [_VP, C.POINTER(LoudnessParamsC), C.POINTER(C.c_int)]),
+    "mi355tts_loudness": (
+        C.c_int,
+        [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, _VP, _VP, C.c_int64,
+         _VP, _VP, _VP, _VP, C.c_uint32],
     ),
     "mi355tts_synthesize": (
         C.c_int,

@@ -1,0 +1,82 @@
+"""A loudness target for delivered audio on the HIP backend (`mi355tts_loudness`, csrc/loudness.h): the ITU-R BS.1770-4
+integrated loudness (mono) of each row, measured where the samples already are, and the row delivered at a target level under
+a sample-peak ceiling.  The default delivery stays the reference's: every sentence's peak on 32767
+(`larynx/audio.py:118-125`), which lets the level of a document jump from sentence to sentence.  The K-weighting design lives
+here; the library takes its ten coefficients like any other table."""
+from __future__ import annotations
+
+import math
+import threading
+import typing
+
+import numpy as np
+
+from .engine import Engine
+
+
+def k_weighting(fs: float) -> typing.Dict[str, np.ndarray]:
+    """The two K-weighting biquads at sample rate `fs`, float64: {"shelf_b": [3], "shelf_a": [2], "hp_b": [3], "hp_a": [2]}
+    (a0 = 1 is not stored).  The usual re-derivation of the standard's 48 kHz filters: the analogue prototypes behind the
+    published table, taken through the bilinear transform at `fs`.  At 48 000 Hz it reproduces the table to 1e-15."""
+    fs = float(fs)
+    if not fs > 0:
+        raise ValueError("fs must be positive")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / fs)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf_b = np.array([Vh + Vb * K / Q + K * K, 2.0 * (K * K - Vh), Vh - Vb * K / Q + K * K]) / a0
+    shelf_a = np.array([2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + K / Q + K * K
+    hp_b = np.array([1.0, -2.0, 1.0])
+    hp_a = np.array([2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    return {"shelf_b": shelf_b, "shelf_a": shelf_a, "hp_b": hp_b, "hp_a": hp_a}
+
+
+def block_and_hop(fs: float) -> typing.Tuple[int, int]:
+    """The 400 ms gating block and its 100 ms hop (75 % overlap) in samples: 8820 and 2205 at 22 050 Hz."""
+    return int(round(0.4 * float(fs))), int(round(0.1 * float(fs)))
+
+
+class Loudness:
+    """`Loudness(engine, sample_rate)`: a meter for audio at that rate.  `measure` reads the integrated loudness of each row
+    (-inf for a row with nothing above -70 LUFS); `normalize` delivers the rows at a target level."""
+
+    def __init__(self, engine: Engine, sample_rate: int):
+        self.engine = engine
+        self.sample_rate = int(sample_rate)
+        if self.sample_rate < 1:
+            raise ValueError(f"sample rate must be positive, got {sample_rate}")
+        self.coefficients = {k: v.astype(np.float32) for k, v in k_weighting(self.sample_rate).items()}
+        self.block, self.hop = block_and_hop(self.sample_rate)
+        self.model_id = engine.load_loudness(block=self.block, hop=self.hop, **self.coefficients)
+
+    def measure(self, audio: np.ndarray, samples=None) -> np.ndarray:
+        """float32 or int16, [N] or [B, N] (row b valid for `samples[b]` entries) -> LUFS, float32 [B]."""
+        return self.engine.loudness(self.model_id, audio, samples)["lufs"]
+
+    def normalize(self, audio: np.ndarray, target: float = -16.0, ceiling: float = 10 ** (-1 / 20), max_gain_db: float = 30.0,
+                  int16: bool = True, samples=None) -> np.ndarray:
+        """The rows scaled to `target` LUFS, each by ONE gain: never more than `max_gain_db`, and never so much that a sample
+        passes `ceiling` (-1 dBFS by default; the sample peak, not the true peak).  int16 out (clamp(rint(y * 32768))), or
+        float32 with `int16=False`; rows are zero-filled behind their samples."""
+        out = self.engine.loudness(self.model_id, audio, samples, target=target, ceiling=ceiling, max_gain_db=max_gain_db,
+                                   want_float=not int16, want_int16=int16)
+        return out["i16"] if int16 else out["f32"]
+
+
+_cache_lock = threading.Lock()
+
+
+def get_loudness(engine: Engine, sample_rate: int) -> Loudness:
+    """One `Loudness` per (engine, rate), made on first use (the sentence path's `loudness=`) and kept ON the engine: it lives
+    and dies with the context its model id belongs to."""
+    key = int(sample_rate)
+    with _cache_lock:
+        cache = engine.__dict__.setdefault("_loudness_meters", {})
+        if key not in cache:
+            cache[key] = Loudness(engine, key)
+        return cache[key]
