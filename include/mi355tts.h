@@ -456,6 +456,70 @@ int mi355tts_loudness(mi355tts_ctx* ctx, int model, const float* in_f32, const i
                       int64_t in_ld, float target_lufs, float peak_ceiling, float max_gain_db, float* out_f32, int16_t* out_i16,
                       int64_t out_ld, float* lufs_out, float* gain_out, float* peak_out, float* weighted_out, uint32_t flags);
 
+/* ---- limiter: a true-peak meter and a look-ahead limiter for the delivered rows --
+ * mi355tts_loudness delivers a row at ONE gain, capped by peak_ceiling / max|x|: a row with a high peak-to-loudness ratio comes
+ * out under its target.  This measures a row's TRUE peak (ITU-R BS.1770-4 Annex 2: the peak of the oversampled signal) and
+ * delivers the row at the full gain G with only the neighbourhood of each peak turned down, where the samples already are:
+ * TWO launches for a meter call, SIX for a limited row, whatever N and B are (csrc/limiter.h).  The reference has no such step.
+ * Per row x[0 .. N); everything outside the row is silence; no state is kept across calls.
+ *   Parameters (fixed at load time): oversample os in 1 .. 8 (BS.1770 uses 4); a symmetric interpolation prototype
+ *                  taps[2 H + 1] at the oversampled rate, at most 128 taps per phase, the caller's
+ *                  (larynx_amd.limiter.design_interpolator); lookahead la in 0 .. 1024 samples; release a in [0, 1): the depth
+ *                  decays by a per sample; a smoothing window w[la + 1], finite, non-negative, its sum (in double) within 1e-6
+ *                  of 1 (larynx_amd.limiter.smoothing_window).
+ *   Per call:      a gain G[b] per row (host array; NULL: 1) and ceiling in (0, 1].
+ *   1 Interpolation  u[m] = sum_i x[i] taps[m + H - i os] for m in [0, N os): the arithmetic and term order of mi355tts_resample
+ *                  with up = os, down = 1 (f32, one fma per term, the polyphase row of phase (m + H) mod os walked from its
+ *                  first entry, one accumulator from +0), so max|u| equals, bit for bit, the maximum over that call's output.
+ *   2 True peak    tp[n] = max(|x[n]|, max over p < os of |u[n os + p]|); the row's TP = max_n tp[n].  With os = 1 no taps are
+ *                  read and tp = |x|.
+ *   3 Required gain  c[n] = 1 where tp[n] * G <= ceiling (one f32 product), else ceiling / (tp[n] * G), one correctly rounded
+ *                  f32 division.  Outside [0, N), c = 1.
+ *   4 Hold         m[k] = min(c[k - 1], .., c[k + la]) for k = -la .. N - 1 (the k - 1 term: a peak between samples k - 1 and
+ *                  k turns both down).
+ *   5 Release      d[-la - 1] = 0, d[k] = max(1 - m[k], a d[k - 1]): the depth, f32.
+ *   6 Smoothing    s[n] = max(0, 1 - sum over j = 0 .. la of w[j] d[n - j]), j ascending, one fma per term from +0, then one
+ *                  subtraction.  (With r = 1 - d this is sum_j w[j] r[n - j] for a window that sums to 1; it is taken on the
+ *                  depth so that a row that needs no limiting has s = 1 and s <= 1 holds for every window, both exactly.)  Every
+ *                  d[n - j] >= 1 - m[n - j] >= 1 - min(c[n], c[n - 1]), so s[n] <= min(c[n], c[n - 1]) up to the window's
+ *                  distance from sum 1 and f32 round-off: the property that makes it a limiter.
+ *   7 Delivery     out_f32[n] = clamp((x[n] * G) * s[n], -ceiling, +ceiling) (the clamp catches the round-off above);
+ *                  out_i16[n] = clamp(rintf(out_f32[n] * 32768), -32768, 32767), the rule of MI355TTS_PCM_SATURATE; every output
+ *                  row is zero-filled from its N up to out_ld.
+ *   Outputs (each optional): out_f32 / out_i16 [B][out_ld] and curve_out [B][in_ld] (s itself, zeros behind N: for tests, like
+ *                  weighted_out), host, or device with MI355TTS_OUT_DEVICE; true_peak_out [B] (host): TP of the INPUT, before
+ *                  G; min_gain_out [B] (host): min_n s[n] (1 for an empty row).  A call with no waveform output and no curve is a
+ *                  METER CALL: it runs only the two launches TP needs, and min_gain_out receives 1.
+ *   Arithmetic:    all f32.  The release is the one recurrence; its operator (max, x a^len) is associative, so it is decomposed:
+ *                  chunks of 16 positions from d = 0, the chunks' end states scanned inside a workgroup of 256 chunks, the
+ *                  workgroups' end states carried in sequence, every position resolved from its true start state, with the
+ *                  powers a^0 .. a^4096 computed in double at load time and rounded to f32 once.  With a = 0 every step is the
+ *                  sequential definition bit for bit; with a > 0 a carried term is a^len * d in ONE product where the sequential
+ *                  form multiplies len times.  No atomics; every order is fixed by the row alone.  Row b of a batch gives the
+ *                  bits of its own batch-1 call; int16 input is converted as s * 2^-15 (exact) inside the launch and gives the
+ *                  bits of the equal f32 input; host and device pointers give the same bits.
+ * mi355tts_load_limiter: lays out the polyphase table and the powers on the device; taps may be NULL with oversample 1;
+ * mi355tts_unload frees the model.
+ * mi355tts_limit: exactly one of in_f32 / in_i16 [B][in_ld] (host, or device with MI355TTS_IN_DEVICE); row b holds samples[b]
+ * <= in_ld <= 2^24 samples (host array).  The workspace grows on demand (mi355tts_reserve does not cover this call).
+ * MI355TTS_ERR_INVALID with the reason (MI355TTS_ERR_NO_MODEL for an unknown id): null pointers; oversample outside [1, 8];
+ * half_len < 0; more than 128 taps per phase; a non-finite tap; lookahead outside [0, 1024]; release outside [0, 1); a
+ * non-finite or negative window entry; a window sum further than 1e-6 from 1; both inputs or neither; samples[b] outside
+ * [0, in_ld] or above 2^24; out_ld below the longest row (when a waveform output is asked for); ceiling outside (0, 1]; a
+ * non-finite or negative G[b].
+ * Added in ABI version 2 (additive: the version number is unchanged). */
+typedef struct {
+  int32_t oversample; /* 1 .. 8 */
+  int32_t half_len;   /* H >= 0: the prototype has 2 H + 1 taps, at most 128 per phase (ignored with oversample 1) */
+  int32_t lookahead;  /* 0 .. 1024 samples */
+  float release;      /* [0, 1): the depth's decay per sample */
+} mi355tts_limiter_params;
+int mi355tts_load_limiter(mi355tts_ctx* ctx, const mi355tts_limiter_params* params, const float* taps, const float* window,
+                          int* model_out);
+int mi355tts_limit(mi355tts_ctx* ctx, int model, const float* in_f32, const int16_t* in_i16, const int64_t* samples, int B,
+                   int64_t in_ld, const float* gain, float ceiling, float* out_f32, int16_t* out_i16, int64_t out_ld,
+                   float* true_peak_out, float* min_gain_out, float* curve_out, uint32_t flags);
+
 /* ---- fused call: replaces the model half of _sentence_task -------------------
  * (larynx/__init__.py:229-283: phonemes_to_mels -> mel transforms -> mels_to_audio -> pause
  * padding) with ONE call on one stream: arguments as in mi355tts_glow_infer +
@@ -614,7 +678,7 @@ int mi355tts_profile_kernels_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Launches per kernel NAME since the last mi355tts_profile_reset, {"rb_group_kernel": n, ...}; counted whether profiling is
  * on or not.  The class counters cannot tell a kernel from the fallback that would silently take its place (same launch count,
  * same bits by design): the device tests assert on these.  The first 44 keys and their order are fixed and always present,
- * zero or not; the names of later entry points (the six loudness_*_kernel) follow them once they have launched since the last
+ * zero or not; the names of later entry points (the six loudness_*_kernel, the five limiter_*_kernel) follow them once they have launched since the last
  * reset.  No reference counterpart (measurement only). */
 int mi355tts_kernel_counts_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Median elapsed time (microseconds) of `pairs` EMPTY event pairs on an idle stream: what the two hipEventRecord calls around a

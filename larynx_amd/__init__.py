@@ -34,7 +34,8 @@ _LOGGER = logging.getLogger("larynx_amd")
 
 __all__ = [
     "AudioSettings", "InferenceBackend", "TextToSpeechResult", "load_tts_model", "load_vocoder_model",
-    "sentence_task", "sentence_task_aligned", "sentence_task_at_rate", "sentence_task_leveled", "phonemes_to_speech",
+    "sentence_task", "sentence_task_aligned", "sentence_task_at_rate", "sentence_task_leveled", "sentence_task_limited",
+    "phonemes_to_speech",
 ]
 
 
@@ -97,19 +98,34 @@ def sentence_task_leveled(text: str, phoneme_ids, audio_settings, tts_model, tts
                      pause_before_ms, pause_after_ms, sample_rate, loudness)[0]
 
 
+def sentence_task_limited(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                          pause_before_ms: int = 0, pause_after_ms: int = 0, sample_rate: typing.Optional[int] = None,
+                          loudness: typing.Optional[float] = None) -> np.ndarray:
+    """`sentence_task_leveled` through the true-peak limiter: the float row takes the gain its level asks for, whatever its
+    peaks, and the limiter turns down only what would pass the -1 dBFS TRUE-peak ceiling, on the device
+    (`Loudness.normalize_limited`, `larynx_amd.limiter`): the row reaches `loudness` LUFS where the single gain of
+    `sentence_task_leveled` stops at the ceiling.  `loudness` is required."""
+    if loudness is None:
+        raise ValueError("limiter: valid only together with loudness")
+    return _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                     pause_before_ms, pause_after_ms, sample_rate, loudness, True)[0]
+
+
 def sentence_task_aligned(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
                           pause_before_ms: int = 0, pause_after_ms: int = 0, sample_rate: typing.Optional[int] = None,
-                          loudness: typing.Optional[float] = None) -> typing.Tuple[np.ndarray, np.ndarray]:
+                          loudness: typing.Optional[float] = None, limiter: typing.Optional[bool] = None) -> typing.Tuple[np.ndarray, np.ndarray]:
     """`sentence_task` that also returns where every phoneme id sounds: `(audio, spans)`, spans int64 [P, 2] in samples
     of `audio`, leading pause included (`larynx_amd.alignment.phoneme_spans`).  The TTS model must be one whose mels
     carry durations (`HipGlowTextToSpeech`); the audio is what `sentence_task` gives for the same settings.  With a
     Griffin-Lim vocoder the spans are nominal frame positions (hop 256), see `phoneme_spans`.  With `sample_rate` (see
     `sentence_task_at_rate`) the spans are positions in the delivered audio: both ends scaled by (s * up) // down.  `loudness`
-    (see `sentence_task_leveled`) changes the level of the audio, not the spans."""
+    (see `sentence_task_leveled`; with `limiter`, `sentence_task_limited`) changes the level of the audio, not the spans."""
+    if limiter and loudness is None:
+        raise ValueError("limiter: valid only together with loudness")
     settings = dict(tts_settings or {})
     settings["alignment"] = True
     audio, mels, before, resampler = _sentence(text, phoneme_ids, audio_settings, tts_model, settings, vocoder_model,
-                                               vocoder_settings, pause_before_ms, pause_after_ms, sample_rate, loudness)
+                                               vocoder_settings, pause_before_ms, pause_after_ms, sample_rate, loudness, bool(limiter))
     from .alignment import phoneme_spans, scale_spans
 
     durations = getattr(mels, "durations", None)
@@ -146,7 +162,7 @@ def _float_row(vocoder_model, mels, vocoder_settings, before, after) -> np.ndarr
 
 
 def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
-              pause_after_ms, deliver_rate=None, deliver_lufs=None):
+              pause_after_ms, deliver_rate=None, deliver_lufs=None, limited=False):
     """-> (audio, the mels the vocoder consumed, leading pause in samples at the voice's rate, the `Resampler` the audio went
     through or None)"""
     t0 = time.perf_counter()
@@ -179,7 +195,12 @@ def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocode
         if resampler is not None:
             row = resampler.resample(row)
             sample_rate = resampler.rate_out
-        audio = get_loudness(engine, sample_rate).normalize(row, target=float(deliver_lufs))
+        if limited:  # the full gain, and the true-peak limiter in place of the single gain's cap
+            from .limiter import get_limiter
+
+            audio = get_loudness(engine, sample_rate).normalize_limited(row, target=float(deliver_lufs), limiter=get_limiter(engine, sample_rate))
+        else:
+            audio = get_loudness(engine, sample_rate).normalize(row, target=float(deliver_lufs))
         before = after = 0
     elif resampler is not None:
         # another rate: the float row, pauses included, resampled on the device and normalised to int16 there
@@ -218,14 +239,19 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
                        vocoder_settings: typing.Optional[SettingsType] = None,
                        executor: typing.Optional[Executor] = None, alignment: bool = False,
                        sample_rate: typing.Optional[int] = None,
-                       loudness: typing.Optional[float] = None) -> typing.Iterable[TextToSpeechResult]:
+                       loudness: typing.Optional[float] = None,
+                       limiter: typing.Optional[bool] = None) -> typing.Iterable[TextToSpeechResult]:
     """`text_to_speech` (`larynx/__init__.py:47-190`) from the point where gruut /
     phonemes2ids have produced ids: one task per sentence on an executor, results
     yielded in submission order.  `alignment`: every result also carries `phoneme_spans`, the start and end sample
     of each phoneme id in its audio (`sentence_task_aligned`); the audio is the same either way.  `sample_rate`: deliver
     the audio at that rate instead of the voice's own (`sentence_task_at_rate`: resampled on the device, int16 of
     ceil(n * up / down) samples, spans scaled to match); `None` or the voice's rate changes nothing.  `loudness`: deliver
-    every sentence at that many LUFS instead of with its peak on 32767 (`sentence_task_leveled`); `None` changes nothing."""
+    every sentence at that many LUFS instead of with its peak on 32767 (`sentence_task_leveled`); `None` changes nothing.
+    `limiter=True` (only together with `loudness`): through the true-peak limiter, so that the level is reached whatever the
+    sentence's peaks (`sentence_task_limited`); `None` or `False` changes nothing."""
+    if limiter and loudness is None:
+        raise ValueError("limiter: valid only together with loudness")
     own = executor is None
     executor = executor or ThreadPoolExecutor()
     _ensure_pool_workers(executor, tts_model, vocoder_model)
@@ -238,6 +264,9 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
             task = functools.partial(sentence_task_aligned if alignment else sentence_task_at_rate, sample_rate=sr)
         if loudness is not None:  # (the voice's own rate as `sample_rate` is no resampling)
             task = functools.partial(sentence_task_aligned if alignment else sentence_task_leveled, sample_rate=sr, loudness=float(loudness))
+            if limiter:
+                task = (functools.partial(sentence_task_aligned, sample_rate=sr, loudness=float(loudness), limiter=True) if alignment
+                        else functools.partial(sentence_task_limited, sample_rate=sr, loudness=float(loudness)))
         futures = []
         for text, ids in sentences:
             fut = executor.submit(task, text, np.asarray(ids, np.int64), audio_settings, tts_model, tts_settings,

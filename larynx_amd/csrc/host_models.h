@@ -436,6 +436,25 @@ struct LoudnessModel {
   }
 };
 
+// A limiter (limiter.h) is its parameters and three device tables: the interpolator's polyphase table (laid out as a
+// resampler's with up = oversample; none with oversample 1), the smoothing window [lookahead + 1] and the powers
+// a^0 .. a^LM_GROUP of the release (computed in double at load time: limiter_forward.h)
+struct LimiterModel {
+  static constexpr const char* missing = "no limiter %d";
+  mi355tts_limiter_params p;
+  int device = 0;
+  int T = 0, Tp = 1;
+  float* table = nullptr;
+  float* win = nullptr;
+  float* pw = nullptr;
+  ~LimiterModel() {
+    DeviceScope ds(device);
+    if (table) hipFree(table);
+    if (win) hipFree(win);
+    if (pw) hipFree(pw);
+  }
+};
+
 static std::vector<std::pair<std::string, int64_t>> glow_manifest(const mi355tts_glow_hparams& h) {
   std::vector<std::pair<std::string, int64_t>> m;
   auto add = [&](const std::string& n, int64_t e) { m.emplace_back(n, e); };

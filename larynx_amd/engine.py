@@ -748,6 +748,75 @@ class Engine:
         )
         return res[0], res[1], res[2]
 
+    # ---- limiter -------------------------------------------------------------------
+    def load_limiter(self, taps, window, oversample: int, release: float) -> int:
+        """`mi355tts_load_limiter`: a true-peak meter and look-ahead limiter from its interpolation prototype `taps` [2 H + 1]
+        at the oversampled rate (None with `oversample` 1), its smoothing `window` [lookahead + 1] and its release, the depth's
+        decay per sample (`larynx_amd.limiter`).  `unload` frees it."""
+        window = np.ascontiguousarray(window, np.float32).reshape(-1)
+        if len(window) < 1:
+            raise ValueError("window must be [lookahead + 1]")
+        half_len = 0
+        if taps is not None:
+            taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+            if len(taps) % 2 != 1:
+                raise ValueError(f"taps must be [2 H + 1] (a symmetric prototype around its centre), got {len(taps)}")
+            half_len = len(taps) // 2
+        p = ffi.LimiterParamsC(int(oversample), half_len, len(window) - 1, float(release))
+        model = C.c_int()
+        ffi.check(self.lib, self.lib.mi355tts_load_limiter(self._ctx, C.byref(p), ffi.ptr(taps), window.ctypes.data, C.byref(model)))
+        return int(model.value)
+
+    def limit(self, model: int, audio: np.ndarray, samples=None, gain=None, ceiling: float = 1.0, want_float: bool = False,
+              want_int16: bool = False, want_curve: bool = False) -> dict:
+        """`audio`: float32 or int16 (read as s / 32768), [N] or [B, N], row b valid for `samples[b]` entries (default: all);
+        `gain`: one per row (default 1) -> {"true_peak", "min_gain": float32 [B]; "f32", "i16", "curve": [B, N] or None}.  With
+        nothing asked for it is a meter call (`true_peak` of the input alone).  A 1-D input gives 1-D rows."""
+        audio = np.asarray(audio)
+        if audio.dtype != np.int16:
+            audio = audio.astype(np.float32, copy=False)
+        audio = np.ascontiguousarray(audio)
+        flat = audio.ndim == 1
+        if flat:
+            audio = audio[None]
+        if audio.ndim != 2:
+            raise ValueError("audio: [N] or [B, N]")
+        B, N = audio.shape
+        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        if n.shape != (B,):
+            raise ValueError("samples: one count per row")
+        g = None
+        if gain is not None:
+            g = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, np.float32).reshape(-1), (B,)))
+        f32 = np.empty((B, N), np.float32) if want_float else None
+        i16 = np.empty((B, N), np.int16) if want_int16 else None
+        crv = np.empty((B, N), np.float32) if want_curve else None
+        f_in, i_in = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
+        if N == 0:  # (an empty array has no address worth passing)
+            f_in, i_in = (None, np.zeros(1, np.int16).ctypes.data) if audio.dtype == np.int16 else (np.zeros(1, np.float32).ctypes.data, None)
+        tp, mg = self.limit_raw(model, f_in, i_in, n, N, g, ceiling, ffi.ptr(f32), ffi.ptr(i16), N, ffi.ptr(crv))
+        if flat:
+            f32, i16, crv = (None if f32 is None else f32[0]), (None if i16 is None else i16[0]), (None if crv is None else crv[0])
+        return {"true_peak": tp, "min_gain": mg, "f32": f32, "i16": i16, "curve": crv}
+
+    def limit_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, gain, ceiling: float, out_f32_ptr=None, out_i16_ptr=None,
+                  out_ld: int = 0, curve_ptr=None, flags: int = 0):
+        """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE); `gain`: float32 [B] or
+        None; the output pointers [B][out_ld] and the curve [B][in_ld] are optional (device memory with ffi.OUT_DEVICE); returns
+        the rows' (true_peak, min_gain), float32 [B] each."""
+        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32).reshape(-1)
+        if g is not None and g.shape != n.shape:
+            raise ValueError("gain: one per row")
+        res = np.zeros((2, len(n)), np.float32)
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_limit(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+                                    ffi.ptr(g), float(ceiling), out_f32_ptr, out_i16_ptr, int(out_ld), res[0].ctypes.data,
+                                    res[1].ctypes.data, curve_ptr, int(flags)),
+        )
+        return res[0], res[1]
+
     # ---- single operators ------------------------------------------------------
     def conv1d(self, x, w, bias=None, dilation=1, in_slope=1.0, out_act=0, lens=None) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

@@ -96,6 +96,13 @@ class LoudnessParamsC(C.Structure):
                 ("block", C.c_int32), ("hop", C.c_int32)]
 
 
+class LimiterParamsC(C.Structure):
+    """`mi355tts_limiter_params`: the oversampling factor, the interpolator's half-length, the look-ahead in samples and the
+    release (the depth's decay per sample)."""
+
+    _fields_ = [("oversample", C.c_int32), ("half_len", C.c_int32), ("lookahead", C.c_int32), ("release", C.c_float)]
+
+
 PCM_SATURATE = 0  # MI355TTS_PCM_*: clamp(rint(y * 32768)) / the reference's audio_float_to_int16 on the resampled row
 PCM_NORMALIZE = 1
 
@@ -190,6 +197,11 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
         C.c_int,
         [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, _VP, _VP, C.c_int64,
          _VP, _VP, _VP, _VP, C.c_uint32],
+    ),
+    "mi355tts_load_limiter": (C.c_int, [_VP, C.POINTER(LimiterParamsC), _VP, _VP, C.POINTER(C.c_int)]),
+    "mi355tts_limit": (
+        C.c_int,
+        [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, _VP, C.c_float, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_uint32],
     ),
     "mi355tts_synthesize": (
         C.c_int,

@@ -67,6 +67,37 @@ class Loudness:
                                    want_float=not int16, want_int16=int16)
         return out["i16"] if int16 else out["f32"]
 
+    def normalize_limited(self, audio: np.ndarray, target: float = -16.0, limiter=None, ceiling: float = 10 ** (-1 / 20),
+                          max_gain_db: float = 30.0, int16: bool = True, samples=None) -> np.ndarray:
+        """The rows at `target` LUFS through `limiter` (a `larynx_amd.limiter.Limiter` at this rate): each row takes the gain
+        its level asks for, G = min(10^((target - L) / 20), 10^(max_gain_db / 20)) (f64, rounded once; 1 for L = -inf), and the
+        limiter turns down what would pass the true-peak `ceiling`.  Limiting costs a little level, so the delivered float row
+        is measured again on the device, and where it reads more than `LEVEL_TOLERANCE` under the target with G below its cap,
+        ONE correction pass limits the row again with G raised by the deficit.  Rows that need no limiting equal `normalize`'s."""
+        if limiter is None:
+            raise ValueError("normalize_limited needs a Limiter")
+        target = float(np.float32(target))
+        cap = 10.0 ** (float(np.float32(max_gain_db)) / 20.0)
+
+        def gains(lufs, base):
+            with np.errstate(over="ignore"):
+                g = np.where(np.isfinite(lufs), np.minimum(base * 10.0 ** ((target - lufs.astype(np.float64)) / 20.0), cap), 1.0)
+            return g
+
+        lufs = self.measure(audio, samples)
+        g64 = gains(lufs, 1.0)
+        out = self.engine.limit(limiter.model_id, audio, samples, gain=g64.astype(np.float32), ceiling=ceiling, want_float=True,
+                                want_int16=int16)
+        after = self.measure(out["f32"], samples)
+        short = np.isfinite(lufs) & np.isfinite(after) & (after.astype(np.float64) < target - LEVEL_TOLERANCE) & (g64 < cap)
+        if short.any():
+            g64 = np.where(short, gains(after, g64), g64)
+            out = self.engine.limit(limiter.model_id, audio, samples, gain=g64.astype(np.float32), ceiling=ceiling,
+                                    want_float=not int16, want_int16=int16)
+        return out["i16"] if int16 else out["f32"]
+
+
+LEVEL_TOLERANCE = 0.1  # LU: the meter tolerance of EBU Tech 3341, the project's bound on a delivered level
 
 _cache_lock = threading.Lock()
 

@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import sentence_task, sentence_task_at_rate, sentence_task_leveled
+from . import sentence_task, sentence_task_at_rate, sentence_task_leveled, sentence_task_limited
 
 Sentence = typing.Union[typing.Tuple[str, typing.Sequence[int]], typing.Tuple[str, typing.Sequence[int], int, int]]
 
@@ -34,7 +34,8 @@ class RawStreamStats(typing.NamedTuple):
 def stream_raw_pcm(sentences: typing.Iterable[Sentence], tts_model, vocoder_model, sink: typing.BinaryIO,
                    tts_settings=None, vocoder_settings=None, max_thread_workers: int = 2,
                    raw_stream_queue_size: int = 5, max_pending: typing.Optional[int] = None,
-                   sample_rate: typing.Optional[int] = None, loudness: typing.Optional[float] = None) -> RawStreamStats:
+                   sample_rate: typing.Optional[int] = None, loudness: typing.Optional[float] = None,
+                   limiter: typing.Optional[bool] = None) -> RawStreamStats:
     """Synthesise `sentences` — `(text, phoneme_ids)` or `(text, phoneme_ids,
     pause_before_ms, pause_after_ms)` — and write 16-bit mono PCM to `sink` in
     sentence order.  `max_thread_workers=2` is the reference's raw-stream default
@@ -43,7 +44,10 @@ def stream_raw_pcm(sentences: typing.Iterable[Sentence], tts_model, vocoder_mode
     queue size), so an unbounded sentence source cannot pile audio up in memory.
     A failed sentence re-raises here after the writer has been shut down.  `sample_rate`: write the PCM at that rate instead
     of the voice's own (`sentence_task_at_rate`); `None` or the voice's rate changes nothing.  `loudness`: write every sentence
-    at that many LUFS instead of with its peak on 32767 (`sentence_task_leveled`); `None` changes nothing."""
+    at that many LUFS instead of with its peak on 32767 (`sentence_task_leveled`); `None` changes nothing.  `limiter=True`
+    (only together with `loudness`): through the true-peak limiter (`sentence_task_limited`); `None` or `False` changes nothing."""
+    if limiter and loudness is None:
+        raise ValueError("limiter: valid only together with loudness")
     audio_settings = getattr(tts_model, "audio_settings", None)
     max_pending = max_pending or (max_thread_workers + raw_stream_queue_size)
     voice_rate = audio_settings.sample_rate if audio_settings is not None else 22050
@@ -92,7 +96,7 @@ def stream_raw_pcm(sentences: typing.Iterable[Sentence], tts_model, vocoder_mode
                 text, ids = item[0], np.asarray(item[1], np.int64)
                 before, after = (int(item[2]), int(item[3])) if len(item) >= 4 else (0, 0)
                 if loudness is not None:
-                    pending.append(pool.submit(sentence_task_leveled, text, ids, audio_settings, tts_model, tts_settings, vocoder_model,
+                    pending.append(pool.submit(sentence_task_limited if limiter else sentence_task_leveled, text, ids, audio_settings, tts_model, tts_settings, vocoder_model,
                                                vocoder_settings, before, after, int(sample_rate) if at_rate else None, float(loudness)))
                 elif at_rate:
                     pending.append(pool.submit(sentence_task_at_rate, text, ids, audio_settings, tts_model, tts_settings,
