@@ -620,6 +620,9 @@ int mi355tts_set_profiling(mi355tts_ctx* ctx, int enabled);
  *     launch; "adaptive_schedule" (0/1, default 0) — while other calls are in flight, launch the members of a group one by one;
  *   "rb_conv" (0/1, default 1) — the grouped 128-row ResBlock launches on the continuous-stream tile of rb_conv.h (0 = the
  *     chunked tile of conv_mfma.h);
+ *   "rb_dil" (0/1, default 1) — the grouped ResBlock launches of rb_conv.h / rb_pair.h whose members share a dilation of 1, 3
+ *     or 5 on the kernel compiled for that dilation (operand offsets as instruction immediates; 0 = the kernel that reads the
+ *     dilation from its arguments, which every other dilation takes anyway);
  *   "group_snake" (0/1, default 1) — the workgroup ORDER of fully resident grouped launches (a snake over the dispatcher's
  *     rounds).  The one option the library may change by itself: mi355tts_dispatch_selfcheck switches it off on a device where
  *     the order does not win;

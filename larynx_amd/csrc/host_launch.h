@@ -39,6 +39,9 @@ static void launch_conv_inst(ProfScope& ps, hipStream_t s, dim3 grid, const Conv
 //           128 x 128 form: +1.4 % on the class — finer granularity, four workgroups per CU.)
 enum TileShape { TILE_SMALL = 0, TILE_W128 = 1, TILE_NB2 = 2, TILE_TINY = 3, TILE_LAST = 3, TILE_M128 = 4 };
 
+// rb_tile stages its input through 32-bit byte offsets from the batch row's plane: the plane must be < 4 GiB
+static bool rb_plane_ok(const ConvArgs& a) { return (long long)a.Cin * a.x_ld < (1LL << 30); }
+
 // rb_conv: the call's option "rb_conv" and not MI355TTS_NO_RB_CONV (the upsamplers' continuous-stream tile); ps: the caller's scope
 // (the launch is named, with its output rows as the sub-key, where its kernel is chosen)
 template <int K, int EPI>
@@ -60,7 +63,7 @@ static int launch_conv_k(ProfScope& ps, hipStream_t s, int MB, int shape, dim3 g
     if (shape == TILE_M128) {  // the polyphase upsampler's virtual rows, 128 per workgroup from one staged input tile
       if constexpr (K == 2) {
         // the continuous-stream tile (rb_conv.h; same bits): taps 2 — every upsampler of the shipped vocoders (k_u = 2 u)
-        if (rb_conv && a.Cin % 16 == 0 && !a.res && !a.accum && a.alpha == 1.0f) {
+        if (rb_conv && a.Cin % 16 == 0 && !a.res && !a.accum && a.alpha == 1.0f && rb_plane_ok(a)) {
           if (a.x2 && a.x3) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_conv_kernel<2, 4, EPI_UPSAMPLE, true>), grid, dim3(256), 0, s, a);
           else if (!a.x2) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_conv_kernel<2, 4, EPI_UPSAMPLE, false>), grid, dim3(256), 0, s, a);
           if ((a.x2 && a.x3) || !a.x2) {
@@ -341,7 +344,7 @@ static void launch_group_k(ProfScope& ps, hipStream_t s, int tile, dim3 grid, co
 static bool rb_member_ok(const ConvArgs& a, int K) {
   const int halo = K == 11 ? RbCfg<11>::HALO : K == 7 ? RbCfg<7>::HALO : RbCfg<3>::HALO;
   return !a.x2 && !a.x3 && a.bias && a.alpha == 1.0f && !a.accum && a.out_act == ACT_NONE && a.split >= a.rows && !a.y2 &&
-         a.rows % 128 == 0 && halo_fits(K, a.dil, a.pad, halo);
+         a.rows % 128 == 0 && halo_fits(K, a.dil, a.pad, halo) && rb_plane_ok(a);
 }
 
 // The same-geometry convs of the three MRF chains of a step (hifigan_forward.h plans them together).  At batch 1, members that
@@ -392,6 +395,17 @@ static void promote_group_plans(const CallOptions& o, ConvPlan* const* plans, in
     p.a.rows_major = 0;
     p.grid = dim3((p.n_max + 63) / 64, p.a.rows / 128, 1);
   }
+}
+
+// The continuous-stream group kernel for a step: the one compiled for its dilation (`dil` = 1 / 3 / 5, the same for the three
+// members: every B-operand offset an instruction immediate) or, for any other value (0 = members differ, option rb_dil off),
+// the one that reads the dilation from its arguments.  Same bits.
+template <int NB>
+static void launch_rb_group(int dil, dim3 grid, hipStream_t s, const ConvGroupArgs& g) {
+  const bool fixed = switch_const<1, 3, 5>(dil, [&](auto d) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_dil_kernel<11, 7, 3, NB, decltype(d)::value>), grid, dim3(256), 0, s, g);
+  });
+  if (!fixed) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3, NB>), grid, dim3(256), 0, s, g);
 }
 
 static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* const* plans, int n, hipStream_t s) {
@@ -445,6 +459,7 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* const* plans,
     for (int i = 0; i < 3; ++i) rb_ok = rb_ok && rb_member_ok(g.c[i], i == 0 ? 11 : i == 1 ? 7 : 3);
     if (rb_ok) {
       const bool snake = o.group_snake && !o.env.snake_off;
+      const int dil = (o.rb_dil && g.c[0].dil == g.c[1].dil && g.c[0].dil == g.c[2].dil) ? g.c[0].dil : 0;
       // 128-column tiles (NB = 4: half the weight-fragment bytes and staged halo per MFMA, three workgroups per CU) when the launch
       // still more than fills the chip with them.  Same chains per output element: same bits.
       // Measured A B A B (profiles/r06_nb4_ab.txt): the 128-channel stage's launch alone 240 -> 250 us (927 workgroups deal worse over
@@ -463,13 +478,13 @@ static int run_group(mi355tts_ctx* ctx, Worker* w, const ConvPlan* const* plans,
           const dim3 grid4(g.off[3], 1, 1);
           if (snake) group_snake_order(g, ncu, 3 * ncu);
           ps.kernel(KN_RB_GROUP_NB4, p0.a.rows);
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3, 4>), grid4, dim3(256), 0, s, g);
+          launch_rb_group<4>(dil, grid4, s, g);
           return 0;
         }
       }
       if (grid.z == 1 && snake) group_snake_order(g, ncu, 4 * ncu);  // four of these workgroups fit a CU (32 KB, <= 128 VGPRs)
       ps.kernel(g.nseg ? KN_RB_GROUP_SNAKE : KN_RB_GROUP, p0.a.rows);
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_group_kernel<11, 7, 3>), grid, dim3(256), 0, s, g);
+      launch_rb_group<2>(dil, grid, s, g);
       return 0;
     }
   }
@@ -591,12 +606,18 @@ static int run_pair_group(mi355tts_ctx* ctx, Worker* w, const PairPlan* const* p
   const dim3 grid(g.off[3], 1, p0.grid.z);
   ProfScope ps(ctx, w, KC_RESBLOCK, flop, s);
   const bool rb = w->opt.rb_pair && p0.rb;
+  const int dil = (w->opt.rb_dil && g.p[0].dil == g.p[1].dil && g.p[0].dil == g.p[2].dil) ? g.p[0].dil : 0;
   ps.kernel(p0.bf16 ? KN_PAIR_BF16_GROUP : rb ? KN_RB_PAIR_GROUP : KN_PAIR_GROUP, p0.C);
   pair_tile_dispatch(p0.C, [&](auto c) {
     constexpr PairTile t = PAIR_TILES[decltype(c)::value];
     if (p0.bf16 == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, t.CB, t.WN16, t.NB16, 3>), grid, dim3(64 * t.CB * t.WN16), 0, s, g);
     else if (p0.bf16 == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_bf16_group_kernel<11, 7, 3, t.CB, t.WN16, t.NB16, 1>), grid, dim3(64 * t.CB * t.WN16), 0, s, g);
-    else if (rb) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_group_kernel<11, 7, 3, t.CB>), grid, dim3(256), 0, s, g);
+    else if (rb) {  // the kernel compiled for conv1's dilation, or the one that reads it from its arguments (same bits)
+      const bool fixed = switch_const<1, 3, 5>(dil, [&](auto d) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(rbp_dil_group_kernel<11, 7, 3, t.CB, decltype(d)::value>), grid, dim3(256), 0, s, g);
+      });
+      if (!fixed) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_pair_group_kernel<11, 7, 3, t.CB>), grid, dim3(256), 0, s, g);
+    }
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_group_kernel<11, 7, 3, t.CB, t.NB>), grid, dim3(512), 0, s, g);
   });
   return 0;

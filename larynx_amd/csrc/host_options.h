@@ -99,6 +99,7 @@ struct ContextOptions {
   std::atomic<bool> mrf_group{true};  // grouped launches of the MRF chains' same-geometry convs (hifigan_forward.h)
   std::atomic<bool> rb_conv{true};    // grouped 128-row launches on the continuous-stream tile (rb_conv.h; same bits)
   std::atomic<bool> rb_pair{true};    // fused ResBlock steps (64 / 32 channels) on the 4-wave tile without a k-split (rb_pair.h)
+  std::atomic<bool> rb_dil{true};     // rb_conv / rb_pair grouped launches on the kernel compiled for the step's dilation (1 / 3 / 5); 0 = the run-time-dilation kernel (same bits)
   std::atomic<bool> group_promote{true};  // batch-1 ResBlock steps move to the 128-row tile when the snake deal is balanced (promote_group_plans)
   // Grouped launches whose workgroups are all resident at once are laid out as a snake over the dispatcher's rounds
   // (group_snake_order).  That order encodes an OBSERVED dispatcher rule (workgroup i -> CU i mod #CUs);
@@ -132,6 +133,7 @@ static const struct OptionRow {
     {"group_snake", &ContextOptions::group_snake, nullptr},
     {"group_promote", &ContextOptions::group_promote, nullptr},
     {"rb_pair", &ContextOptions::rb_pair, nullptr},
+    {"rb_dil", &ContextOptions::rb_dil, nullptr},
     {"gate16_wide", nullptr, &ContextOptions::gate16_wide},
     {"voc_out", &ContextOptions::voc_out, nullptr},
     {"serial_branches", &ContextOptions::serial_branches, nullptr},
@@ -157,7 +159,7 @@ static int set_context_option(ContextOptions& c, const char* name, int value) {
 // Everything that selects a kernel, a tile or a schedule, as the call saw it when it checked its worker out: a
 // mi355tts_set_option or a setenv from another thread never changes a call half way through.  Plain values, owned by the worker.
 struct CallOptions {
-  bool glow_fuse = true, gate16 = true, rb_conv = true, rb_pair = true, group_promote = true, group_snake = true;
+  bool glow_fuse = true, gate16 = true, rb_conv = true, rb_pair = true, rb_dil = true, group_promote = true, group_snake = true;
   bool mrf_group = true, mrf_small = true, serial_branches = false, adaptive_schedule = false, voc_out = true;
   int gate16_wide = 512;
   int pin_tile = -1;  // mi355tts_bench_conv1d's tile shape: ahead of MI355TTS_FORCE_TILE[_DYNAMIC] (set by that entry point only)
@@ -176,6 +178,7 @@ static void snapshot_options(const ContextOptions& c, int device_ncu, CallOption
   o->gate16_wide = c.gate16_wide.load();
   o->rb_conv = c.rb_conv.load();
   o->rb_pair = c.rb_pair.load();
+  o->rb_dil = c.rb_dil.load();
   o->group_promote = c.group_promote.load();
   o->group_snake = c.group_snake.load();
   o->mrf_group = c.mrf_group.load();

@@ -33,6 +33,31 @@ namespace mi355tts {
 #define RB_ABL 0
 #endif
 
+// A per-lane LDS byte offset the optimiser must keep in ITS register: the reads that follow address it with immediates
+// instead of re-deriving every address from one common base (one v_add_u32 per read).  No instruction.
+__device__ __forceinline__ int rb_opaque_off(int v) {
+#if defined(__AMDGCN__)
+  asm("" : "+v"(v));
+#endif
+  return v;
+}
+// 16 bytes of a packed weight stream: wave-uniform base (scalar registers) + this lane's 32-bit byte offset — no 64-bit
+// per-lane address arithmetic.  (The empty asm pins `base` to a scalar register pair: without it the optimiser hoists base +
+// lane_off out of the loop as a 64-bit vector value and adds the step to THAT, one v_lshl_add_u64 per load.)
+__device__ __forceinline__ float4 rb_a_load(const char* __restrict__ base, unsigned& lane_off) {
+#if defined(__AMDGCN__)
+  typedef float rb_f4 __attribute__((ext_vector_type(4)));
+  unsigned long long p = reinterpret_cast<unsigned long long>(base);
+  // lane_off too: its zero-extension then stays next to the load, where the scalar-base form is matched.  By reference: the
+  // next load takes the value this statement "returns", so the register is handed on and never copied.
+  asm("" : "+s"(p), "+v"(lane_off));
+  const rb_f4 v = *reinterpret_cast<const __attribute__((address_space(1))) rb_f4*>(p + lane_off);  // global_load_dwordx4 v, v_off, s[base]
+  return make_float4(v.x, v.y, v.z, v.w);
+#else
+  return *reinterpret_cast<const float4*>(base + lane_off);
+#endif
+}
+
 // ring buffer stride: whole sweeps of the 256 threads (a thread past the tile's last float4 stores into padding)
 template <int HALO, int NB = 2, int CI_C = 16>
 constexpr int rb_buf_floats() { return ((CI_C * (32 * NB + HALO) / 4 + 255) / 256) * 256 * 4; }
@@ -47,7 +72,11 @@ constexpr int rb_lds_floats() { return 4 * rb_buf_floats<HALO, NB, CI_C>(); }
 // CI_C = channels per staged chunk (16 everywhere).  32 was measured for the two-tap upsamplers, whose 16-channel chunk is only
 // 32 MFMAs per wave between two chunk seams: 48 KB of LDS and 141 VGPRs instead of 32 KB / 101 for -2 us per utterance
 // (profiles/NOTES.md, round 5) — not instantiated.  The MFMA sequence does not depend on it: same bits.
-template <int K, int HALO, int EPI = EPI_LINEAR, bool MRF = false, int NB = 2, int CI_C = 16>
+// DIL = the conv's dilation as a compile-time value (1 / 3 / 5: hifi_gan/models.py:91-98), 0 = a.dil at run time.  With DIL
+// known every B-operand LDS offset of an (octet, row pair) is an instruction immediate: four base registers per octet
+// (rb_opaque_off keeps them from being folded back into one add per tap), k * DIL + 32 nb in ds_read2_b32's offset fields.
+// Same reads, same MFMA sequence: same bits as DIL = 0.
+template <int K, int HALO, int EPI = EPI_LINEAR, bool MRF = false, int NB = 2, int CI_C = 16, int DIL = 0>
 __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, const int tile_y, const int b, float* __restrict__ xs) {
   static_assert(EPI == EPI_LINEAR || EPI == EPI_UPSAMPLE, "rb_tile: linear and upsample epilogues");
   constexpr int NT = 256, T_T = 32 * NB;  // NB column blocks of 32 per wave: 64-column tiles, or 32 (NB = 1) where a
@@ -57,6 +86,7 @@ __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, con
   constexpr int BUF = rb_buf_floats<HALO, NB, CI_C>();  // floats per ring buffer (>= CI_C * XW)
   static_assert(BUF == NE * NT * 4, "ring stride = whole thread sweeps");
   static_assert(XW % 4 == 0 && S >= NE + 2, "bad tile parameters");
+  static_assert(DIL == 0 || ((K - 1) * DIL + (NB - 1) * 32 <= 255 && (K - 1) * DIL + 3 <= HALO), "tap offsets: ds_read2_b32 immediates, inside the halo");
 
   const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
   const int t0 = tile_x * T_T;
@@ -79,17 +109,23 @@ __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, con
   const float* xb3 = MRF ? a.x3 + (long long)b * a.x_bs : nullptr;
   float4 pre[NE * NP];
   auto gload = [&](int chunk) {
+    // channel min(chunk * CI_C + row, Cin - 1) = the chunk's first channel (clamped; scalar: it goes into the base) + this
+    // lane's row in the chunk (clamped) — no per-lane channel counter runs along the chunks
+    const int cb = chunk * CI_C < cin_last ? chunk * CI_C : cin_last;
+    const long long cbo = (long long)cb * a.x_ld;
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
       const int e = tid + NT * i;
       const int row = e / XW4, f = e - row * XW4;
-      const int ci = chunk * CI_C + (row < CI_C ? row : CI_C - 1);
+      const int rowc = row < CI_C ? row : CI_C - 1, rel = rowc < cin_last - cb ? rowc : cin_last - cb;
       const int c0 = t0 - PA + 4 * f;
-      const int off = (ci < a.Cin ? ci : cin_last) * a.x_ld + (c0 < 0 ? 0 : (c0 > ld_last4 ? ld_last4 : c0));
-      pre[i] = *reinterpret_cast<const float4*>(xb + off);
+      const int off = rel * a.x_ld + (c0 < 0 ? 0 : (c0 > ld_last4 ? ld_last4 : c0));
+      // off >= 0 (clamped) and a batch row's plane is < 2^30 floats (the host checks): uniform base + 32-bit byte offset
+      unsigned off4 = (unsigned)off * 4u;
+      pre[i] = rb_a_load(reinterpret_cast<const char*>(xb + cbo), off4);
       if constexpr (MRF) {
-        pre[NE + i] = *reinterpret_cast<const float4*>(xb2 + off);
-        pre[2 * NE + i] = *reinterpret_cast<const float4*>(xb3 + off);
+        pre[NE + i] = rb_a_load(reinterpret_cast<const char*>(xb2 + cbo), off4);
+        pre[2 * NE + i] = rb_a_load(reinterpret_cast<const char*>(xb3 + cbo), off4);
       }
     }
   };
@@ -97,7 +133,7 @@ __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, con
     const int e = tid + NT * i;
     const int row = e / XW4, f = e - row * XW4;
     const int c0 = t0 - PA + 4 * f;
-    const bool fok = chunk * CI_C + row < a.Cin && f < used4;
+    const bool fok = row < a.Cin - chunk * CI_C && f < used4;  // (the right side is scalar: no per-lane channel counter)
     float4 v = pre[i];
     if constexpr (MRF) {  // xs / num_kernels of hifi_gan/models.py:191-197, in conv_tile's order: ((x + x2) + x3) / in_div
       const float4 v2 = pre[NE + i], v3 = pre[2 * NE + i];
@@ -124,12 +160,16 @@ __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, con
     for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
 
   // A fragments: float4 index ((mt * noct + oct) * K + k) * 64 + lane, step q of chunk c = octet 2 c + q / K, tap q % K
-  const float4* wq = reinterpret_cast<const float4*>(a.w) + (long long)mt0 * a.noct * K * 64 + lane;
+  // The m-tile's base is wave-uniform (readfirstlane makes that provable) and so is the step: both stay on the scalar unit,
+  // the lane adds its 16-byte slot once.
+  const int mt0u = tile_y * 4 + __builtin_amdgcn_readfirstlane(wm);
+  const char* wq = reinterpret_cast<const char*>(a.w) + (long long)mt0u * a.noct * K * 1024;
+  unsigned lane16 = lane * 16;
   const int last_step = nchunks * S - 1;
-  auto a_index = [&](int chunk, int q) -> long long {
+  auto a_frag = [&](int chunk, int q) -> float4 {
     int g = chunk * S + q;
     g = g < last_step ? g : last_step;
-    return (long long)g * 64;  // (octet, tap) pairs are consecutive: g = (chunk * OCTS + oi) * K + k
+    return rb_a_load(wq + (long long)g * 1024, lane16);  // (octet, tap) pairs are consecutive: g = (chunk * OCTS + oi) * K + k
   };
   constexpr int RD = MI355TTS_ARING;
   float4 ar[RD];
@@ -142,7 +182,7 @@ __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, con
   if (RB_PRIO) __builtin_amdgcn_s_setprio(RB_PRIO);
   gload(0);
 #pragma unroll
-  for (int i = 0; i < RD - 1; ++i) ar[i] = wq[a_index(0, i)];
+  for (int i = 0; i < RD - 1; ++i) ar[i] = a_frag(0, i);
   {
     constexpr int NR = NE * NP;
     float4 p0[NR];
@@ -171,7 +211,20 @@ __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, con
 
   const int b_off = (lane >> 5) * XW + (lane & 31) + (PA - a.pad);
   float bcur[4][NB], bnxt[4][NB];
-  {
+  // DIL > 0: byte offsets of this lane's element in rows 0 / 2 / 4 / 6 of the octet being read, re-based once per octet
+  int bj[4];
+  auto rebase = [&](int buf, int oi) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bj[j] = rb_opaque_off(b_off * 4 + (buf * BUF + (oi * 8 + 2 * j) * XW) * 4);  // vector + scalar: one add
+  };
+  auto b_at = [&](int j, int c) -> float { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(xs) + bj[j] + c * 4); };
+  if constexpr (DIL > 0) {
+    rebase(0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) bcur[j][nb] = b_at(j, nb * 32);
+  } else {
     const float* xt = xs + b_off;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -197,15 +250,23 @@ __device__ __forceinline__ void rb_tile(const ConvArgs& a, const int tile_x, con
       } else if (s == NE + 1) {
         if (!(RB_ABL & 4)) __syncthreads();
       }
-      if (!(RB_ABL & 2)) ar[(s + RD - 1) % RD] = wq[a_index(chunk, s + RD - 1)];
+      if (!(RB_ABL & 2)) ar[(s + RD - 1) % RD] = a_frag(chunk, s + RD - 1);
       if (!(RB_ABL & 8)) {
         const int oi = (s + 1 < S) ? (s + 1) / K : 0;
         const int k = (s + 1 < S) ? (s + 1) - oi * K : 0;
-        const float* bp = ((s + 1 < S) ? xt : xn) + (oi * 8) * XW + k * a.dil;
+        if constexpr (DIL > 0) {
+          if (k == 0) rebase((s + 1 < S) ? (chunk & 3) : ((chunk + 1) & 3), oi);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < 4; ++j)
 #pragma unroll
-          for (int nb = 0; nb < NB; ++nb) bnxt[j][nb] = bp[(2 * j) * XW + nb * 32];
+            for (int nb = 0; nb < NB; ++nb) bnxt[j][nb] = b_at(j, k * DIL + nb * 32);
+        } else {
+          const float* bp = ((s + 1 < S) ? xt : xn) + (oi * 8) * XW + k * a.dil;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) bnxt[j][nb] = bp[(2 * j) * XW + nb * 32];
+        }
       }
       // one accumulator (NB = 1): every MFMA depends on the previous one and a filler between two dependent MFMAs costs
       // ~40 cycles (MI355X_MICROARCH.md) — the fillers go first, the MFMAs stay back to back
@@ -431,12 +492,10 @@ template <> struct RbCfg<11> { static constexpr int HALO = 56; };
 template <> struct RbCfg<7> { static constexpr int HALO = 36; };
 template <> struct RbCfg<3> { static constexpr int HALO = 16; };
 
-// the three MRF chains' same-geometry convs in one launch, longest first (cf. conv_group_kernel)
-template <int K0, int K1, int K2, int NB = 2>
-__global__ __launch_bounds__(256, NB > 2 ? 3 : 4) void rb_group_kernel(const ConvGroupArgs g) {
+// the three MRF chains' same-geometry convs in one launch, longest first (cf. conv_group_kernel); DIL as rb_tile's
+template <int K0, int K1, int K2, int NB, int DIL>
+__device__ __forceinline__ void rb_group_body(const ConvGroupArgs& g, float* __restrict__ xs) {
   constexpr int H0 = RbCfg<K0>::HALO, H1 = RbCfg<K1>::HALO, H2 = RbCfg<K2>::HALO;
-  constexpr int L0 = rb_lds_floats<H0, NB>(), L1 = rb_lds_floats<H1, NB>(), L2 = rb_lds_floats<H2, NB>();
-  __shared__ float xs[max3(L0, L1, L2)];
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
   const bool ragged = gridDim.z > 1;
@@ -456,19 +515,37 @@ __global__ __launch_bounds__(256, NB > 2 ? 3 : 4) void rb_group_kernel(const Con
     const int gx = ragged ? row_tiles(conv_n_len<K0, EPI_LINEAR>(g.c[0], b), 32 * NB) : g.gx[0];
     if (l >= gx * g.gy[0]) return;
     xcd_tile_lin(l, gx, g.gy[0], tx, ty);
-    rb_tile<K0, H0, EPI_LINEAR, false, NB>(g.c[0], tx, ty, b, xs);
+    rb_tile<K0, H0, EPI_LINEAR, false, NB, 16, DIL>(g.c[0], tx, ty, b, xs);
   } else if (m == 1) {
     const int gx = ragged ? row_tiles(conv_n_len<K1, EPI_LINEAR>(g.c[1], b), 32 * NB) : g.gx[1];
     if (l >= gx * g.gy[1]) return;
     xcd_tile_lin(l, gx, g.gy[1], tx, ty);
-    rb_tile<K1, H1, EPI_LINEAR, false, NB>(g.c[1], tx, ty, b, xs);
+    rb_tile<K1, H1, EPI_LINEAR, false, NB, 16, DIL>(g.c[1], tx, ty, b, xs);
   } else {
     const int gx = ragged ? row_tiles(conv_n_len<K2, EPI_LINEAR>(g.c[2], b), 32 * NB) : g.gx[2];
     if (l >= gx * g.gy[2]) return;
     xcd_tile_lin(l, gx, g.gy[2], tx, ty);
-    rb_tile<K2, H2, EPI_LINEAR, false, NB>(g.c[2], tx, ty, b, xs);
+    rb_tile<K2, H2, EPI_LINEAR, false, NB, 16, DIL>(g.c[2], tx, ty, b, xs);
   }
   CONV_WG_STAMP(lin, 1);
+}
+template <int K0, int K1, int K2, int NB>
+constexpr int rb_group_lds_floats() {
+  return max3(rb_lds_floats<RbCfg<K0>::HALO, NB>(), rb_lds_floats<RbCfg<K1>::HALO, NB>(), rb_lds_floats<RbCfg<K2>::HALO, NB>());
+}
+
+// any dilation the halos hold, read from the arguments: the fallback for a model with other dilations than 1 / 3 / 5, and what
+// the tests compare the kernels below with
+template <int K0, int K1, int K2, int NB = 2>
+__global__ __launch_bounds__(256, NB > 2 ? 3 : 4) void rb_group_kernel(const ConvGroupArgs g) {
+  __shared__ float xs[rb_group_lds_floats<K0, K1, K2, NB>()];
+  rb_group_body<K0, K1, K2, NB, 0>(g, xs);
+}
+// every member's dilation = DIL (the host checks): one kernel per dilation, not one kernel with three loop sets
+template <int K0, int K1, int K2, int NB, int DIL>
+__global__ __launch_bounds__(256, NB > 2 ? 3 : 4) void rb_group_dil_kernel(const ConvGroupArgs g) {
+  __shared__ float xs[rb_group_lds_floats<K0, K1, K2, NB>()];
+  rb_group_body<K0, K1, K2, NB, DIL>(g, xs);
 }
 
 }  // namespace mi355tts

@@ -44,30 +44,53 @@ struct RbPairGeom {
   static_assert(TW <= XW, "the parked tile must fit over the x tile");
 };
 
-// one MFMA phase of a wave: acc[nb] += sum over (octet, tap) of A-fragment x B-column; bt = this lane's first B element
-template <int K, int NOCT>
-__device__ __forceinline__ void rbp_phase(floatx16 (&acc)[2], const float4* wq, const float* bt, int RS, int dil) {
+// one MFMA phase of a wave: acc[nb] += sum over (octet, tap) of A-fragment x B-column.  wq = the wave's m-block of the packed
+// weights (wave-uniform: scalar registers), lane16 = this lane's 16-byte slot in a fragment; xs + boff = this lane's first B
+// element, RS the LDS row stride.  DIL = the dilation at compile time (every B offset of an octet's row pair an immediate of
+// ds_read2_b32, four base registers per octet: rb_tile, rb_conv.h), 0 = `dil` at run time.  Same reads, same bits.
+template <int K, int NOCT, int DIL>
+__device__ __forceinline__ void rbp_phase(floatx16 (&acc)[2], const char* wq, unsigned& lane16, const float* xs, int boff, int RS, int dil) {
   constexpr int S = NOCT * K;
-  auto a_index = [&](int q) -> long long { return (long long)(q < S ? q : S - 1) * 64; };  // (octet, tap) pairs are consecutive
+  static_assert(DIL == 0 || (K - 1) * DIL + 32 <= 255, "tap offsets: ds_read2_b32 immediates");
+  auto a_frag = [&](int q) -> float4 { return rb_a_load(wq + (q < S ? q : S - 1) * 1024, lane16); };  // (octet, tap) pairs are consecutive
   float4 ar[3];
-  ar[0] = wq[a_index(0)];
-  ar[1] = wq[a_index(1)];
+  ar[0] = a_frag(0);
+  ar[1] = a_frag(1);
   float bcur[4][2], bnxt[4][2];
+  const float* bt = xs + boff;
+  int bj[4];  // DIL > 0: byte offsets of this lane's element in rows 0 / 2 / 4 / 6 of the octet being read
+  auto rebase = [&](int oi) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bj[j] = rb_opaque_off(boff * 4 + (oi * 8 + 2 * j) * RS * 4);
+  };
+  auto b_at = [&](int j, int c) -> float { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(xs) + bj[j] + c * 4); };
+  if constexpr (DIL > 0) rebase(0);
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) bcur[j][nb] = bt[(2 * j) * RS + nb * 32];
+    for (int nb = 0; nb < 2; ++nb) {
+      if constexpr (DIL > 0) bcur[j][nb] = b_at(j, nb * 32);
+      else bcur[j][nb] = bt[(2 * j) * RS + nb * 32];
+    }
 #pragma unroll
   for (int s = 0; s < S; ++s) {
-    ar[(s + 2) % 3] = wq[a_index(s + 2)];
+    ar[(s + 2) % 3] = a_frag(s + 2);
     if (s + 1 < S) {
       const int oi = (s + 1) / K;
       const int k = (s + 1) - oi * K;
-      const float* bp = bt + (oi * 8) * RS + k * dil;
+      if constexpr (DIL > 0) {
+        if (k == 0) rebase(oi);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) bnxt[j][nb] = bp[(2 * j) * RS + nb * 32];
+          for (int nb = 0; nb < 2; ++nb) bnxt[j][nb] = b_at(j, k * DIL + nb * 32);
+      } else {
+        const float* bp = bt + (oi * 8) * RS + k * dil;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) bnxt[j][nb] = bp[(2 * j) * RS + nb * 32];
+      }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -94,7 +117,8 @@ __device__ __forceinline__ void rbp_phase(floatx16 (&acc)[2], const float4* wq, 
 }
 
 // One workgroup's tile: output columns [tile_x * T2, +T2) of batch row b.  xs = RbPairGeom::LDS floats of LDS.
-template <int K, int CB>
+// DIL = conv1's dilation at compile time (the host launches it only where a.dil == DIL), 0 = a.dil; conv2's is always 1.
+template <int K, int CB, int DIL = 0>
 __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, const int b, float* __restrict__ xs) {
   using G = RbPairGeom<K, CB>;
   constexpr int C = G::C, T1 = G::T1, XW = G::XW, TW = G::TW;
@@ -111,15 +135,18 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
   const int j0 = tile_x * T2;  // first output column of this workgroup
   if (j0 >= L) return;
   const int gt0 = j0 - P2;             // global column of parked-tile column 0
-  const int p1 = (K - 1) * a.dil / 2;  // conv1 "same" padding
+  const int dil = DIL > 0 ? DIL : a.dil;
+  const int p1 = (K - 1) * dil / 2;  // conv1 "same" padding
   const int gx0 = (gt0 - p1) & ~3;     // 4-aligned global column of staged-tile column 0
   const int shift = (gt0 - p1) - gx0;
   const float* xb = a.x + (long long)b * a.bs;
   const float slope = a.slope;
 
   // first fragments of conv1 and conv1's bias: requested with the activation tile
-  const float4* wq1 = reinterpret_cast<const float4*>(a.w1) + (long long)mb * a.noct * K * 64 + lane;
-  const float4* wq2 = reinterpret_cast<const float4*>(a.w2) + (long long)mb * a.noct * K * 64 + lane;
+  const int mbu = __builtin_amdgcn_readfirstlane(wave) % CB;  // provably wave-uniform: the fragment base stays in scalar registers
+  const char* wq1 = reinterpret_cast<const char*>(a.w1) + (long long)mbu * a.noct * K * 1024;
+  const char* wq2 = reinterpret_cast<const char*>(a.w2) + (long long)mbu * a.noct * K * 1024;
+  unsigned lane16 = lane * 16;
   // ---- phase 0: stage lrelu(x) for all C channels, 16-byte loads, branch-free, in batches of NEB loads per thread
   {
     const int ld_last4 = a.ld - 4;
@@ -165,7 +192,7 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
 
   // ---- phase 1: conv1 (dilation d) on T1 columns
   zero_acc();
-  rbp_phase<K, NOCT>(acc, wq1, xs + half * XW + shift + wcol0 + col, XW, a.dil);
+  rbp_phase<K, NOCT, DIL>(acc, wq1, lane16, xs, half * XW + shift + wcol0 + col, XW, dil);
   {
     float bb[16];
 #pragma unroll
@@ -211,7 +238,7 @@ __device__ __forceinline__ void rbp_tile(const PairArgs& a, const int tile_x, co
   const bool interior = RBP_WIDE_STORES && !PREFETCH && j0 + T1 <= L;  // uniform: every column of the tile is inside the sequence
   if (PREFETCH) epi_loads();
   zero_acc();
-  rbp_phase<K, NOCT>(acc, wq2, xs + half * TW + wcol0 + col, TW, 1);
+  rbp_phase<K, NOCT, (DIL > 0 ? 1 : 0)>(acc, wq2, lane16, xs, half * TW + wcol0 + col, TW, 1);
   if (interior) {
     // The accumulator blocks go through LDS once ([32 rows][64 columns] per wave, over the dead parked tile) so that a lane
     // holds FOUR consecutive columns: 8 16-byte residual loads + 8 16-byte stores per lane instead of 32 + 32 dword ones.  A
@@ -311,10 +338,8 @@ __global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rb_pair_kernel(co
 }
 
 // the fused steps of the three MRF chains of a stage in ONE launch, longest member first (cf. pair_group_kernel)
-template <int K0, int K1, int K2, int CB>
-__global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rb_pair_group_kernel(const PairGroupArgs g) {
-  constexpr int L0 = RbPairGeom<K0, CB>::LDS, L1 = RbPairGeom<K1, CB>::LDS, L2 = RbPairGeom<K2, CB>::LDS;
-  __shared__ float xs[max3(L0, L1, L2)];
+template <int K0, int K1, int K2, int CB, int DIL>
+__device__ __forceinline__ void rbp_group_body(const PairGroupArgs& g, float* __restrict__ xs) {
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
   auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(tile_len(p.len, p.len_mul, p.len_const, b), t2) : gx_grid; };
@@ -325,21 +350,36 @@ __global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rb_pair_group_ker
     const int gx = tiles(g.p[0], g.gx[0], T1 - (K0 - 1));
     if (lin >= gx) return;
     xcd_tile_lin(lin, gx, 1, tx, ty);
-    rbp_tile<K0, CB>(g.p[0], tx, b, xs);
+    rbp_tile<K0, CB, DIL>(g.p[0], tx, b, xs);
   } else if (lin < g.off[2]) {
     const int l = lin - g.off[1];
     const int gx = tiles(g.p[1], g.gx[1], T1 - (K1 - 1));
     if (l >= gx) return;
     xcd_tile_lin(l, gx, 1, tx, ty);
-    rbp_tile<K1, CB>(g.p[1], tx, b, xs);
+    rbp_tile<K1, CB, DIL>(g.p[1], tx, b, xs);
   } else {
     const int l = lin - g.off[2];
     const int gx = tiles(g.p[2], g.gx[2], T1 - (K2 - 1));
     if (l >= gx) return;
     xcd_tile_lin(l, gx, 1, tx, ty);
-    rbp_tile<K2, CB>(g.p[2], tx, b, xs);
+    rbp_tile<K2, CB, DIL>(g.p[2], tx, b, xs);
   }
   CONV_WG_STAMP(lin, 1);
+}
+template <int K0, int K1, int K2, int CB>
+constexpr int rbp_group_lds_floats() { return max3(RbPairGeom<K0, CB>::LDS, RbPairGeom<K1, CB>::LDS, RbPairGeom<K2, CB>::LDS); }
+
+// conv1's dilation read from the arguments: the fallback for other dilations than 1 / 3 / 5, and what the tests compare with
+template <int K0, int K1, int K2, int CB>
+__global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rb_pair_group_kernel(const PairGroupArgs g) {
+  __shared__ float xs[rbp_group_lds_floats<K0, K1, K2, CB>()];
+  rbp_group_body<K0, K1, K2, CB, 0>(g, xs);
+}
+// every member's conv1 dilation = DIL (the host checks): one kernel per dilation
+template <int K0, int K1, int K2, int CB, int DIL>
+__global__ __launch_bounds__(256, CB == 2 ? 3 : RBP_LB32) void rbp_dil_group_kernel(const PairGroupArgs g) {
+  __shared__ float xs[rbp_group_lds_floats<K0, K1, K2, CB>()];
+  rbp_group_body<K0, K1, K2, CB, DIL>(g, xs);
 }
 
 }  // namespace mi355tts
