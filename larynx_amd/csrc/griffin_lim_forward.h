@@ -1,6 +1,6 @@
 // mi355tts host runtime — the Griffin-Lim vocoder's load and inference entry points (kernels: griffin_lim.h)
-// (one translation unit: included once by mi355tts.hip, after hifigan_forward.h for the row delivery it shares; the call frame,
-// the model table and context_table: host_call.h)
+// (one translation unit: included once by mi355tts.hip, after hifigan_forward.h; the call frame, the model table and
+// context_table: host_call.h; the row delivery: host_rows.h)
 #pragma once
 
 // window + twiddles in double precision, rounded once: tab[i] = np.hanning(1024)[i]; then (cos, -sin)(2 pi m / 1024) with the

@@ -1,9 +1,9 @@
 // mi355tts host runtime — mi355tts_hifigan_infer: the HiFi-GAN layer schedule (hifi_gan/models.py:186-202) and the denoiser
 // (one translation unit: included once by mi355tts.hip, after the kernel headers)
-// The call struct and the workspace layout; the row view of a call's outputs (OutRows); VocPass (what a pass shares); the stage
-// bookkeeping both precisions use (VocStage, StageCursor, chain_planes / step_dst, run_forked); the f32 / split-bf16 generator and
-// the fp16 generator, each a walk over pre / upsample / resblocks / post; the delivery (zero_outputs, stage_rows, scatter_rows and
-// deliver_rows, which Griffin-Lim and the resampler share); then hifigan_run: empty call, layout and bind, generate, denoise, deliver.
+// The call struct and the workspace layout; VocPass (what a pass shares); the stage bookkeeping both precisions use (VocStage,
+// StageCursor, chain_planes / step_dst, run_forked); the f32 / split-bf16 generator and the fp16 generator, each a walk over pre /
+// upsample / resblocks / post; then hifigan_run: empty call, layout and bind, generate, denoise, deliver.  The row view of a call's
+// outputs (OutRows) and the delivery (zero_outputs, deliver_rows) are host_rows.h's.
 // Every call runs on a CallFrame (host_call.h): it holds the worker and drains the streams when a call fails midway.
 #pragma once
 
@@ -17,12 +17,6 @@ extern "C" int mi355tts_hifigan_hop(mi355tts_ctx* ctx, int vocoder) {
 
 // One vocoder call's outputs: per row [pad_before zeros][frames[b]*hop samples][zeros up to wav_ld]
 // (the pads are the SSML pauses `_sentence_task` adds with np.pad, larynx/__init__.py:277-283).
-struct VocRow {  // one row's destinations when the rows of a call belong to different callers (host_join.h)
-  float* wav_f32 = nullptr;
-  int16_t* wav_i16 = nullptr;
-  int64_t wav_ld = 0;
-  int pad_before = 0, pad_after = 0;
-};
 struct VocCall {
   float denoiser_strength = 0.f;
   float* wav_f32 = nullptr;
@@ -102,44 +96,10 @@ static bool hifi_split_out(bool serial_branches, const mi355tts_hifigan_hparams&
   return !serial_branches && h.num_kernels >= 2 && h.num_kernels <= 3;
 }
 
-// ------------------------------------------------------------------ the rows of a call
-// One output row as the host-side code sees it: [pad_before zeros][n samples][zeros up to ld]; the int16 row travels with its
-// pauses (the kernels write them), n + pad_before + pad_after values.  A null pointer = no such output.
-struct OutRow {
-  float* f32;
-  int16_t* i16;
-  int64_t ld;
-  size_t pad_before, pad_after, n;
-};
-// The rows of a call: every caller's own destinations (`rows`: row b travels with its OWN length, its caller's buffer is sized for
-// its own frame count), or one [B][ld] buffer per form (every row travels with the longest row's `n` samples; the kernels zeroed
-// what lies behind a short row's).  An accessor, not an array: a whole-batch call may have more than VOC_MAX_ROWS rows.
-struct OutRows {
-  const VocRow* rows;
-  const int32_t* frames;  // with `rows`: samples of row b = frames[b] * hop
-  int hop;
-  OutRow all;  // without `rows`: row 0; row b lies b * ld behind it
-  OutRow operator()(int b) const {
-    if (rows) return {rows[b].wav_f32, rows[b].wav_i16, rows[b].wav_ld, (size_t)rows[b].pad_before, (size_t)rows[b].pad_after, (size_t)frames[b] * hop};
-    OutRow r = all;
-    if (r.f32) r.f32 += (size_t)b * r.ld;
-    if (r.i16) r.i16 += (size_t)b * r.ld;
-    return r;
-  }
-};
+// the rows of a vocoder call (host_rows.h)
 static OutRows call_rows(const VocCall& c, const mi355tts_mel* mel, int hop) {
   if (c.rows) return {c.rows, mel->frames.data(), hop, {}};
   return {nullptr, nullptr, 0, {c.wav_f32, c.wav_i16, c.wav_ld, (size_t)c.pad_before, (size_t)c.pad_after, (size_t)mel->max_frames * hop}};
-}
-
-// Where a call's host outputs wait in the worker's pinned staging, from byte `at` of it: the float rows [B][f_ld], the int16
-// rows [B][i_ld], then one extra block.  Sized before the call's first launch (CallFrame::reserve), read by deliver_rows.
-struct Staging {
-  size_t at = 0, f32_b = 0, i16_b = 0, extra_b = 0, f_ld = 0, i_ld = 0;
-  size_t end() const { return at + f32_b + i16_b + extra_b; }
-};
-static Staging host_staging(int B, bool f32, size_t f_ld, bool i16, size_t i_ld, size_t at = 0, size_t extra_b = 0) {
-  return {at, f32 ? sizeof(float) * (size_t)B * f_ld : 0, i16 ? sizeof(short) * (size_t)B * i_ld : 0, extra_b, f_ld, i_ld};
 }
 
 // ------------------------------------------------------------------ what one vocoder pass shares
@@ -746,95 +706,6 @@ static int hifigan_body_f16(VocPass& p) {
     CHECK(f16_resblocks(p, c, st));
   }
   return f16_post(p, c);
-}
-
-// ------------------------------------------------------------------ delivery
-// fills and copies into the caller's rows: in host memory, or queued on the stream for device memory.  Empty pieces are skipped.
-struct RowWriter {
-  bool dev;
-  hipStream_t s;
-  template <class T>
-  int zero(T* dst, size_t n) const {
-    if (n && dev) HIPCHECK(hipMemsetAsync(dst, 0, sizeof(T) * n, s));
-    if (n && !dev) std::memset(dst, 0, sizeof(T) * n);
-    return 0;
-  }
-  template <class T>
-  int copy(T* dst, const T* src, size_t n) const {
-    if (n && dev) HIPCHECK(hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyDeviceToDevice, s));
-    if (n && !dev) std::memcpy(dst, src, sizeof(T) * n);
-    return 0;
-  }
-};
-
-// an empty call: every output row all zeros (whole-batch rows lie back to back: one fill per form); ends the frame's work
-static int zero_outputs(CallFrame& f, const OutRows& rows, int B, bool dev) {
-  const RowWriter wr{dev, f.s};
-  const int nfill = rows.rows ? B : 1;
-  const size_t span = rows.rows ? 1 : (size_t)B;
-  for (int b = 0; b < nfill; ++b) {
-    const OutRow r = rows(b);
-    if (r.f32) CHECK(wr.zero(r.f32, span * (size_t)r.ld));
-    if (r.i16) CHECK(wr.zero(r.i16, span * (size_t)r.ld));
-  }
-  if (dev) HIPCHECK(f.wait());
-  f.done = true;
-  return 0;
-}
-
-// finished rows in staging memory: float rows [B][f_ld] of samples alone, int16 rows [B][i_ld] with their pauses
-struct WavRows {
-  float* f32;
-  size_t f_ld;
-  short* i16;
-  size_t i_ld;
-};
-// staging rows -> the caller's: pause | samples | zeros up to the row stride
-static int scatter_rows(const OutRows& rows, int B, const WavRows& src, const RowWriter& wr) {
-  for (int b = 0; b < B; ++b) {
-    const OutRow r = rows(b);
-    const size_t rl = r.pad_before + r.n + r.pad_after;
-    if (r.f32) {
-      float* dst = r.f32;
-      CHECK(wr.zero(dst, r.pad_before));
-      CHECK(wr.copy(dst + r.pad_before, src.f32 + (size_t)b * src.f_ld, r.n));
-      CHECK(wr.zero(dst + r.pad_before + r.n, (size_t)r.ld - r.pad_before - r.n));
-    }
-    if (r.i16) {
-      int16_t* dst = r.i16;
-      CHECK(wr.copy(dst, src.i16 + (size_t)b * src.i_ld, rl));
-      CHECK(wr.zero(dst + rl, (size_t)r.ld - rl));
-    }
-  }
-  return 0;
-}
-// device rows -> pinned rows of the same shape (async DMA): the part of every row that its caller receives
-static int stage_rows(const OutRows& rows, int B, const WavRows& dev, const WavRows& pin, hipStream_t s) {
-  for (int b = 0; b < B; ++b) {
-    const OutRow r = rows(b);
-    if (r.f32 && r.n) HIPCHECK(hipMemcpyAsync(pin.f32 + (size_t)b * pin.f_ld, dev.f32 + (size_t)b * dev.f_ld, sizeof(float) * r.n, hipMemcpyDeviceToHost, s));
-    if (r.i16) HIPCHECK(hipMemcpyAsync(pin.i16 + (size_t)b * pin.i_ld, dev.i16 + (size_t)b * dev.i_ld, sizeof(short) * (r.n + r.pad_before + r.pad_after), hipMemcpyDeviceToHost, s));
-  }
-  return 0;
-}
-
-// Host delivery: device rows -> the pinned staging `st` describes (async DMA) -> the end of the frame's device work -> the
-// caller's (pageable) rows.  `block`: the staging keeps the device rows' strides and each form goes in ONE copy; else row by
-// row, the part its caller receives.  `extra_src` (device, st.extra_b bytes) rides along to `extra_dst`.
-static int deliver_rows(CallFrame& f, const OutRows& rows, int B, const WavRows& dev, const Staging& st, bool block, void* extra_dst = nullptr,
-                        const void* extra_src = nullptr) {
-  char* pf = f.w->pinned_out + st.at;
-  char* pi = pf + st.f32_b;
-  char* px = pi + st.i16_b;
-  const WavRows pin = {(float*)pf, st.f_ld, (short*)pi, st.i_ld};
-  if (!block) CHECK(stage_rows(rows, B, dev, pin, f.s));
-  if (block && st.f32_b) HIPCHECK(hipMemcpyAsync(pf, dev.f32, st.f32_b, hipMemcpyDeviceToHost, f.s));
-  if (block && st.i16_b) HIPCHECK(hipMemcpyAsync(pi, dev.i16, st.i16_b, hipMemcpyDeviceToHost, f.s));
-  if (st.extra_b) HIPCHECK(hipMemcpyAsync(px, extra_src, st.extra_b, hipMemcpyDeviceToHost, f.s));
-  CHECK(f.finish());
-  CHECK(scatter_rows(rows, B, pin, RowWriter{false, f.s}));
-  if (st.extra_b) std::memcpy(extra_dst, px, st.extra_b);
-  return 0;
 }
 
 // ------------------------------------------------------------------ the stages of a call behind the generator

@@ -1,6 +1,7 @@
 // mi355tts host runtime — what every entry point shares around its device work: the call frame (device, worker, the drain on
-// failure), the context's model table (find_model / register_model), its build-once device tables and the waveform intake.
-// The delivery of finished rows to the host (deliver_rows) lives with the row types in hifigan_forward.h.
+// failure), the context's model table (find_model / register_model), a model's device tables (upload, pack_polyphase), the
+// context's build-once device tables and the waveform intake.  The delivery of finished rows to the host (deliver_rows), the
+// row types and the frame of a wave-in / wave-out call (WaveCall) follow in host_rows.h.
 // (one translation unit: included once by mi355tts.hip, after host_context.h)
 #pragma once
 
@@ -82,6 +83,30 @@ static int register_model(mi355tts_ctx* ctx, std::shared_ptr<Model> m, int* mode
   return 0;
 }
 
+// a model's device table: `v` into fresh device memory at `*dst` (the model's destructor frees it, also when a later step of the
+// load fails); the caller has set the device
+template <class T>
+static int upload(T** dst, const std::vector<T>& v, const char* what) {
+  if (hipMalloc(dst, v.size() * sizeof(T)) != hipSuccess) return fail(MI355TTS_ERR_NOMEM, "hipMalloc %s", what);
+  HIPCHECK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// The polyphase layout of a prototype of 2 half_len + 1 taps for interpolation by `up`: table[p][t] = taps[p + t * up], rows of
+// *Tp floats (*T = ceil((2 half_len + 1) / up) taps per phase, at most max_T, rounded up to 4 and zero-filled)
+static int pack_polyphase(const float* taps, int half_len, int up, int max_T, int* T, int* Tp, std::vector<float>& table) {
+  if (half_len < 0) return fail(MI355TTS_ERR_INVALID, "half_len %d < 0", half_len);
+  const long long ntaps = 2LL * half_len + 1, per = (ntaps + up - 1) / up;
+  if (per > max_T) return fail(MI355TTS_ERR_INVALID, "%lld taps per phase > %d", per, max_T);
+  for (long long j = 0; j < ntaps; ++j)
+    if (!std::isfinite(taps[j])) return fail(MI355TTS_ERR_INVALID, "tap %lld is not finite", j);
+  *T = (int)per;
+  *Tp = ((int)per + 3) & ~3;
+  table.assign((size_t)up * *Tp, 0.f);
+  for (long long j = 0; j < ntaps; ++j) table[(size_t)(j % up) * *Tp + (size_t)(j / up)] = taps[j];
+  return 0;
+}
+
 // a device table of the context (`*slot`, guarded by ctx->mu): built and uploaded by whichever load needs it first
 template <class Build>
 static int context_table(mi355tts_ctx* ctx, float** slot, const char* what, Build&& build) {
@@ -110,7 +135,7 @@ struct WaveIn {
   int B;
   int64_t ld;
   bool in_dev;
-  long long Nmax = 0;
+  long long Nmax = 0, total = 0;
   size_t esz = 0, Nld = 0, bytes = 0, o_n = 0, o_rows = 0;
   const void* d = nullptr;
   long long bs = 0;
@@ -122,6 +147,7 @@ struct WaveIn {
         return fail(MI355TTS_ERR_INVALID, "samples[%d]=%lld outside [0, %s=%lld]", b, (long long)samples[b], ld_name, (long long)ld);
       if (samples[b] > (1LL << cap_log2)) return fail(MI355TTS_ERR_INVALID, "samples[%d]=%lld > 2^%d", b, (long long)samples[b], cap_log2);
       Nmax = std::max(Nmax, (long long)samples[b]);
+      total += samples[b];
     }
     esz = f32 ? sizeof(float) : sizeof(int16_t);
     Nld = (size_t)((Nmax + 7) & ~7LL);
@@ -150,5 +176,13 @@ struct WaveIn {
     d = base + o_rows;
     bs = (long long)Nld;
     return 0;
+  }
+  // the four fields every stage's kernel arguments begin with
+  template <class Args>
+  void bind(Args& a) const {
+    a.in_f32 = f32 ? (const float*)d : nullptr;
+    a.in_i16 = i16 ? (const short*)d : nullptr;
+    a.in_bs = bs;
+    a.samples = d_samples;
   }
 };

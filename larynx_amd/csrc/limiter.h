@@ -36,6 +36,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wave_io.h"
+
 namespace mi355tts {
 
 constexpr int LM_TILE = 256;                      // samples per workgroup of the peak and apply kernels = threads
@@ -82,26 +84,6 @@ struct LimiterArgs {
 };
 
 template <bool I16>
-__device__ __forceinline__ float limiter_fetch(const LimiterArgs& a, long long row, int n, int N) {
-  if (n < 0 || n >= N) return 0.f;
-  if constexpr (I16) return (float)a.in_i16[row + n] * (1.0f / 32768);
-  else return a.in_f32[row + n];
-}
-
-// 256 -> 1 by max or min: result in pm[0 .. 3] combined by the caller's lane 0 (a barrier inside: uniform callers only)
-template <bool MIN>
-__device__ __forceinline__ float limiter_block_reduce(float m, float* pm, int tid) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const float o = __shfl_xor(m, s);
-    m = MIN ? fminf(m, o) : fmaxf(m, o);
-  }
-  if ((tid & 63) == 0) pm[tid >> 6] = m;
-  __syncthreads();
-  return MIN ? fminf(fminf(pm[0], pm[1]), fminf(pm[2], pm[3])) : fmaxf(fmaxf(pm[0], pm[1]), fmaxf(pm[2], pm[3]));
-}
-
-template <bool I16>
 __global__ __launch_bounds__(LM_TILE) void limiter_peak_kernel(const LimiterArgs a) {
   __shared__ float xs[LM_XSPAN];
   __shared__ float pm[LM_TILE / 64];
@@ -113,7 +95,7 @@ __global__ __launch_bounds__(LM_TILE) void limiter_peak_kernel(const LimiterArgs
   // xs[i] = x[lo + i], lo = n0 - (Tp - 1): term t of the lane's phase p reads xs[tid + dq(p) + Tp - 1 - t]
   const int lo = n0 - (a.Tp - 1);
 #pragma unroll
-  for (int e = 0; e < LM_XSPAN / LM_TILE; ++e) xs[tid + LM_TILE * e] = limiter_fetch<I16>(a, row, lo + tid + LM_TILE * e, N);
+  for (int e = 0; e < LM_XSPAN / LM_TILE; ++e) xs[tid + LM_TILE * e] = wave_load_row<I16>(a, row, lo + tid + LM_TILE * e, N);
   __syncthreads();
   float tp = fabsf(xs[tid + a.Tp - 1]);
   if (a.os > 1) {
@@ -131,7 +113,7 @@ __global__ __launch_bounds__(LM_TILE) void limiter_peak_kernel(const LimiterArgs
     const float t = tp * a.gain[b];
     a.c[(long long)b * a.c_bs + n] = t <= a.ceiling ? 1.f : a.ceiling / t;
   }
-  const float m = limiter_block_reduce<false>(tp, pm, tid);
+  const float m = block_extreme<false>(tp, pm, tid);
   if (tid == 0) a.tpeak[(long long)b * a.t_ld + blockIdx.x] = m;
 }
 
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(LM_THREADS) void limiter_reduce_kernel(const Limite
   const float* src = (MIN ? a.tmin : a.tpeak) + (long long)b * a.t_ld;
   float m = MIN ? 1.f : 0.f;
   for (int i = tid; i < tiles; i += LM_THREADS) m = MIN ? fminf(m, src[i]) : fmaxf(m, src[i]);
-  m = limiter_block_reduce<MIN>(m, pm, tid);
+  m = block_extreme<MIN>(m, pm, tid);
   if (tid == 0) a.res[2 * b + (MIN ? 1 : 0)] = m;
 }
 
@@ -275,12 +257,12 @@ __global__ __launch_bounds__(LM_TILE) void limiter_apply_kernel(const LimiterArg
   for (int j = 0; j <= a.la; ++j) acc = fmaf(a.win[j], dr[-j], acc);
   const bool live = n < N;
   const float s = live ? fmaxf(1.f - acc, 0.f) : 0.f;
-  const float xg = limiter_fetch<I16>(a, (long long)b * a.in_bs, (int)n, N) * a.gain[b];
+  const float xg = wave_load_row<I16>(a, (long long)b * a.in_bs, (int)n, N) * a.gain[b];
   const float v = live ? fminf(fmaxf(xg * s, -a.ceiling), a.ceiling) : 0.f;
   if (y && n < a.y_ld) y[n] = v;
-  if (pcm && n < a.pcm_ld) pcm[n] = (short)(int)fminf(fmaxf(rintf(v * 32768.0f), -32768.0f), 32767.0f);
+  if (pcm && n < a.pcm_ld) pcm[n] = wave_pcm(v);
   if (curve && n < a.curve_ld) curve[n] = s;
-  const float m = limiter_block_reduce<true>(live ? s : 1.f, pm, tid);
+  const float m = block_extreme<true>(live ? s : 1.f, pm, tid);
   if (tid == 0) a.tmin[(long long)b * a.t_ld + blockIdx.x] = m;
 }
 

@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wave_io.h"
+
 namespace mi355tts {
 
 constexpr int LD_CHUNK = 64;                    // samples per thread
@@ -62,21 +64,14 @@ struct LoudnessArgs {
   float* res;           // [B][3]: lufs, gain, max |x|
 };
 
-template <bool I16>
-__device__ __forceinline__ float loudness_fetch(const LoudnessArgs& a, long long row, long long n, int N) {
-  if (n < 0 || n >= N) return 0.f;
-  if constexpr (I16) return (float)a.in_i16[row + n] * (1.0f / 32768);
-  else return a.in_f32[row + n];
-}
-
 // xs[t * LD_ROW + i] = x[g0 + t * 64 + i] (zeros outside the row), hx = x[g0 - 2], x[g0 - 1]: 64 coalesced loads per lane
 template <bool I16>
 __device__ __forceinline__ void loudness_stage(const LoudnessArgs& a, float* xs, float* hx, long long row, long long g0, int N, int tid) {
   for (int e = 0; e < LD_CHUNK; ++e) {
     const int i = e * LD_THREADS + tid;
-    xs[(i >> 6) * LD_ROW + (i & 63)] = loudness_fetch<I16>(a, row, g0 + i, N);
+    xs[(i >> 6) * LD_ROW + (i & 63)] = wave_load_row<I16>(a, row, g0 + i, N);
   }
-  if (tid < 2) hx[tid] = loudness_fetch<I16>(a, row, g0 - 2 + tid, N);
+  if (tid < 2) hx[tid] = wave_load_row<I16>(a, row, g0 - 2 + tid, N);
 }
 
 // one chunk of the cascade from state s (in place); x1, x2 = x[n-1], x[n-2] before it.  WRITE: the f32 outputs replace the inputs
@@ -118,9 +113,8 @@ __global__ __launch_bounds__(LD_THREADS) void loudness_chunk_kernel(const Loudne
   loudness_run<false>(a, xc, tid ? (double)xc[-2] : (double)hx[1], tid ? (double)xc[-3] : (double)hx[0], s);
   float m = 0.f;
   for (int i = 0; i < LD_CHUNK; ++i) m = fmaxf(m, fabsf(xc[i]));
-#pragma unroll
-  for (int sh = 32; sh >= 1; sh >>= 1) m = fmaxf(m, __shfl_xor(m, sh));
-  if ((tid & 63) == 0) pm[tid >> 6] = m;
+  m = wave_max(m);
+  if ((tid & 63) == 0) pm[tid >> 6] = m;  // (read behind the scan's barriers)
   int cur = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) st[0][tid][i] = s[i];
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(LD_THREADS) void loudness_chunk_kernel(const Loudne
 #pragma unroll
     for (int i = 0; i < 4; ++i) gs[i] = s[i];
   }
-  if (tid == 0) a.gpeak[(long long)b * a.gmax + g] = fmaxf(fmaxf(pm[0], pm[1]), fmaxf(pm[2], pm[3]));
+  if (tid == 0) a.gpeak[(long long)b * a.gmax + g] = block_extreme_of<false>(pm);
 }
 
 // gstate[b][g]: Z_g -> S_g = Z_g + M^256 S_(g-1), in place
@@ -336,9 +330,9 @@ __global__ __launch_bounds__(256) void loudness_apply_kernel(const LoudnessArgs 
   const long long row = (long long)b * a.in_bs;
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < o_ld; i += step) {
-    const float y = i < N ? loudness_fetch<I16>(a, row, i, N) * g : 0.f;
+    const float y = i < N ? wave_load_row<I16>(a, row, i, N) * g : 0.f;
     if (out_f32) out_f32[(long long)b * o_bs + i] = y;
-    if (out_i16) out_i16[(long long)b * o_bs + i] = (short)(int)fminf(fmaxf(rintf(y * 32768.0f), -32768.0f), 32767.0f);
+    if (out_i16) out_i16[(long long)b * o_bs + i] = wave_pcm(y);
   }
 }
 

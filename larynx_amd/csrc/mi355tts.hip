@@ -56,6 +56,7 @@ using namespace mi355tts;
 #include "host_options.h"
 #include "host_context.h"
 #include "host_call.h"
+#include "host_rows.h"
 #include "host_group.h"
 #include "host_launch.h"
 #include "hifigan_f16.h"

@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wave_io.h"
+
 namespace mi355tts {
 
 constexpr int RS_TILE = 256;    // outputs per workgroup = threads
@@ -54,8 +56,7 @@ __device__ __forceinline__ long long resample_out_len(int N, int up, int down) {
 template <bool I16>
 __device__ __forceinline__ float resample_fetch(const ResampleArgs& a, long long in_row, int i, int N) {
   const int ic = i < 0 ? 0 : (i > N - 1 ? N - 1 : i);
-  if constexpr (I16) return (float)a.in_i16[in_row + ic] * (1.0f / 32768);
-  else return a.in_f32[in_row + ic];
+  return wave_load<I16>(a, in_row + ic);
 }
 
 // xs[j] = x[lo + j] for j < 256 NE, zeros outside [0, N): NE loads per lane requested back to back, then written
@@ -135,14 +136,10 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a)
   const bool live = n < nout;
   if (!live) acc = 0.f;  // the tile that holds the row's end: zeros behind it
   if (y && n < a.y_ld) y[n] = acc;
-  if (pcm && n < a.pcm_ld) pcm[n] = (short)(int)fminf(fmaxf(rintf(acc * 32768.0f), -32768.0f), 32767.0f);
+  if (pcm && n < a.pcm_ld) pcm[n] = wave_pcm(acc);
   if (a.peak) {  // (uniform per launch: the barrier is safe)
-    float m = fabsf(acc);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
-    if ((tid & 63) == 0) pm[tid >> 6] = m;
-    __syncthreads();
-    if (tid == 0) a.peak[(long long)b * a.peak_ld + blockIdx.x] = fmaxf(fmaxf(pm[0], pm[1]), fmaxf(pm[2], pm[3]));
+    const float m = block_extreme<false>(fabsf(acc), pm, tid);
+    if (tid == 0) a.peak[(long long)b * a.peak_ld + blockIdx.x] = m;
   }
 }
 
@@ -156,11 +153,7 @@ __global__ __launch_bounds__(256) void resample_pcm_kernel(const float* y, long 
   const long long np = (nout + RS_TILE - 1) / RS_TILE;
   float m = 0.f;
   for (long long i = threadIdx.x; i < np; i += blockDim.x) m = fmaxf(m, peak[(long long)b * peak_ld + i]);
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
-  if ((threadIdx.x & 63) == 0) pm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  const float g = 32767.0f / fmaxf(0.01f, fmaxf(fmaxf(pm[0], pm[1]), fmaxf(pm[2], pm[3])));
+  const float g = 32767.0f / fmaxf(0.01f, block_extreme<false>(m, pm, threadIdx.x));
   const float* src = y + (long long)b * y_bs;
   short* dst = out + (long long)b * o_bs;
   const long long step = (long long)gridDim.x * blockDim.x;

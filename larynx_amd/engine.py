@@ -103,6 +103,16 @@ class Engine:
         self._lock = threading.Lock()
         self._hops: typing.Dict[int, int] = {}
         self._live_mels: "weakref.WeakSet[MelBatch]" = weakref.WeakSet()
+        self._kept: dict = {}
+        self._kept_lock = threading.RLock()
+
+    def kept(self, kind: str, key, make):
+        """One object per (engine, kind, key), made by `make()` on first use and kept ON the engine: it lives and dies with
+        the context its model id belongs to (`get_resampler`, `get_loudness`, `get_limiter`)."""
+        with self._kept_lock:
+            if (kind, key) not in self._kept:
+                self._kept[kind, key] = make()
+            return self._kept[kind, key]
 
     def close(self):
         if self._ctx is not None:
@@ -599,21 +609,41 @@ class Engine:
         ffi.check(self.lib, self.lib.mi355tts_load_analysis(self._ctx, C.byref(p), basis.ctypes.data, C.byref(model)))
         return int(model.value)
 
-    def mel_from_audio(self, model: int, audio: np.ndarray, samples=None, audio_settings=None) -> MelBatch:
-        """`audio`: float32 (in [-1, 1]) or int16, [N] or [B, N], row b valid for `samples[b]` entries (default: all) -> the
-        `MelBatch` of the recording: plane "vocoder" feeds `hifigan_infer` / `griffin_lim_infer`, plane "raw" is the
-        GlowTTS domain `glow_align` expects.  `audio_settings` as everywhere; None leaves ln(max(amp, 1e-5)) in both."""
+    # ---- audio in, rows out ---------------------------------------------------------
+    @staticmethod
+    def _audio_in(audio, samples):
+        """What every call that reads audio does with it: float32 (any other type is converted) or int16, [N] or [B, N], and
+        `samples` (default: all N of every row) -> (the [B, N] contiguous array, whether it was 1-D, B, N, samples int64 [B],
+        the float32 pointer, the int16 pointer): exactly one pointer is set.  The pointers hold while the array is held."""
         audio = np.asarray(audio)
         if audio.dtype != np.int16:
             audio = audio.astype(np.float32, copy=False)
         audio = np.ascontiguousarray(audio)
-        if audio.ndim == 1:
+        flat = audio.ndim == 1
+        if flat:
             audio = audio[None]
         if audio.ndim != 2:
             raise ValueError("audio: [N] or [B, N]")
         B, N = audio.shape
-        f32, i16 = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
-        return self.mel_from_audio_raw(model, f32, i16, np.full(B, N, np.int64) if samples is None else samples, N, audio_settings)
+        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        if n.shape != (B,):
+            raise ValueError("samples: one count per row")
+        if N == 0:  # (an empty array has no address worth passing: one sample nobody reads stands in)
+            audio = np.zeros((B, 1), audio.dtype)
+        ptr = audio.ctypes.data
+        return (audio, flat, B, N, n, None, ptr) if audio.dtype == np.int16 else (audio, flat, B, N, n, ptr, None)
+
+    @staticmethod
+    def _rows_out(flat: bool, *rows):
+        """[B, N] output arrays (or None) in the shape of the call's audio: row 0 alone for a 1-D input."""
+        return tuple(None if r is None else r[0] for r in rows) if flat else rows
+
+    def mel_from_audio(self, model: int, audio: np.ndarray, samples=None, audio_settings=None) -> MelBatch:
+        """`audio`: float32 (in [-1, 1]) or int16, [N] or [B, N], row b valid for `samples[b]` entries (default: all) -> the
+        `MelBatch` of the recording: plane "vocoder" feeds `hifigan_infer` / `griffin_lim_infer`, plane "raw" is the
+        GlowTTS domain `glow_align` expects.  `audio_settings` as everywhere; None leaves ln(max(amp, 1e-5)) in both."""
+        audio, _, _, N, n, f_in, i_in = self._audio_in(audio, samples)
+        return self.mel_from_audio_raw(model, f_in, i_in, n, N, audio_settings)
 
     def mel_from_audio_raw(self, model: int, f32_ptr, i16_ptr, samples, wav_ld: int, audio_settings=None, flags: int = 0) -> MelBatch:
         """Pointer-level entry: exactly one of the two pointers, [B][wav_ld] (device memory with flags=ffi.IN_DEVICE)."""
@@ -649,30 +679,15 @@ class Engine:
         (f32 or None, i16 or None, samples_out int64 [B]); outputs are [B, max N_out] ([N_out] for a 1-D input), rows
         zero-filled behind their N_out = ceil(N * up / down).  int16: `normalize=False` saturates
         clamp(rint(y * 32768)); `normalize=True` is the reference's `audio_float_to_int16` on each resampled row."""
-        audio = np.asarray(audio)
-        if audio.dtype != np.int16:
-            audio = audio.astype(np.float32, copy=False)
-        audio = np.ascontiguousarray(audio)
-        flat = audio.ndim == 1
-        if flat:
-            audio = audio[None]
-        if audio.ndim != 2:
-            raise ValueError("audio: [N] or [B, N]")
+        audio, flat, B, N, n, f_in, i_in = self._audio_in(audio, samples)
         if not (want_float or want_int16):
             raise ValueError("nothing asked for: want_float and / or want_int16")
-        B, N = audio.shape
-        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
-        if n.shape != (B,):
-            raise ValueError("samples: one count per row")
         ld = max([self.resample_length(model, int(v)) for v in n if 0 <= v <= N] or [0])
         f32 = np.empty((B, ld), np.float32) if want_float else None
         i16 = np.empty((B, ld), np.int16) if want_int16 else None
-        f_in, i_in = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
         out = self.resample_raw(model, f_in, i_in, n, N, ffi.ptr(f32), ffi.ptr(i16), ld,
                                 ffi.PCM_NORMALIZE if normalize else ffi.PCM_SATURATE)
-        if flat:
-            f32, i16 = (None if f32 is None else f32[0]), (None if i16 is None else i16[0])
-        return f32, i16, out
+        return (*self._rows_out(flat, f32, i16), out)
 
     def resample_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, out_f32_ptr, out_i16_ptr, out_ld: int,
                      pcm_mode: int = 0, flags: int = 0) -> np.ndarray:
@@ -708,29 +723,13 @@ class Engine:
         """`audio`: float32 or int16 (read as s / 32768), [N] or [B, N], row b valid for `samples[b]` entries (default: all) ->
         {"lufs", "gain", "peak": float32 [B]; "f32", "i16", "weighted": [B, N] or None}.  `target` NaN measures only (gain 1);
         rows are zero-filled behind their samples.  A 1-D input gives 1-D rows (the three per-row results stay [1])."""
-        audio = np.asarray(audio)
-        if audio.dtype != np.int16:
-            audio = audio.astype(np.float32, copy=False)
-        audio = np.ascontiguousarray(audio)
-        flat = audio.ndim == 1
-        if flat:
-            audio = audio[None]
-        if audio.ndim != 2:
-            raise ValueError("audio: [N] or [B, N]")
-        B, N = audio.shape
-        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
-        if n.shape != (B,):
-            raise ValueError("samples: one count per row")
+        audio, flat, B, N, n, f_in, i_in = self._audio_in(audio, samples)
         f32 = np.empty((B, N), np.float32) if want_float else None
         i16 = np.empty((B, N), np.int16) if want_int16 else None
         wgt = np.empty((B, N), np.float32) if want_weighted else None
-        f_in, i_in = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
-        if N == 0:  # (an empty array has no address worth passing)
-            f_in, i_in = (None, np.zeros(1, np.int16).ctypes.data) if audio.dtype == np.int16 else (np.zeros(1, np.float32).ctypes.data, None)
         lufs, gain, peak = self.loudness_raw(model, f_in, i_in, n, N, target, ceiling, max_gain_db, ffi.ptr(f32), ffi.ptr(i16), N,
                                              ffi.ptr(wgt))
-        if flat:
-            f32, i16, wgt = (None if f32 is None else f32[0]), (None if i16 is None else i16[0]), (None if wgt is None else wgt[0])
+        f32, i16, wgt = self._rows_out(flat, f32, i16, wgt)
         return {"lufs": lufs, "gain": gain, "peak": peak, "f32": f32, "i16": i16, "weighted": wgt}
 
     def loudness_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, target: float, ceiling: float, max_gain_db: float,
@@ -772,31 +771,15 @@ class Engine:
         """`audio`: float32 or int16 (read as s / 32768), [N] or [B, N], row b valid for `samples[b]` entries (default: all);
         `gain`: one per row (default 1) -> {"true_peak", "min_gain": float32 [B]; "f32", "i16", "curve": [B, N] or None}.  With
         nothing asked for it is a meter call (`true_peak` of the input alone).  A 1-D input gives 1-D rows."""
-        audio = np.asarray(audio)
-        if audio.dtype != np.int16:
-            audio = audio.astype(np.float32, copy=False)
-        audio = np.ascontiguousarray(audio)
-        flat = audio.ndim == 1
-        if flat:
-            audio = audio[None]
-        if audio.ndim != 2:
-            raise ValueError("audio: [N] or [B, N]")
-        B, N = audio.shape
-        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
-        if n.shape != (B,):
-            raise ValueError("samples: one count per row")
+        audio, flat, B, N, n, f_in, i_in = self._audio_in(audio, samples)
         g = None
         if gain is not None:
             g = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, np.float32).reshape(-1), (B,)))
         f32 = np.empty((B, N), np.float32) if want_float else None
         i16 = np.empty((B, N), np.int16) if want_int16 else None
         crv = np.empty((B, N), np.float32) if want_curve else None
-        f_in, i_in = (None, audio.ctypes.data) if audio.dtype == np.int16 else (audio.ctypes.data, None)
-        if N == 0:  # (an empty array has no address worth passing)
-            f_in, i_in = (None, np.zeros(1, np.int16).ctypes.data) if audio.dtype == np.int16 else (np.zeros(1, np.float32).ctypes.data, None)
         tp, mg = self.limit_raw(model, f_in, i_in, n, N, g, ceiling, ffi.ptr(f32), ffi.ptr(i16), N, ffi.ptr(crv))
-        if flat:
-            f32, i16, crv = (None if f32 is None else f32[0]), (None if i16 is None else i16[0]), (None if crv is None else crv[0])
+        f32, i16, crv = self._rows_out(flat, f32, i16, crv)
         return {"true_peak": tp, "min_gain": mg, "f32": f32, "i16": i16, "curve": crv}
 
     def limit_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, gain, ceiling: float, out_f32_ptr=None, out_i16_ptr=None,

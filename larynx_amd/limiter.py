@@ -7,7 +7,6 @@ tables like any other."""
 from __future__ import annotations
 
 import math
-import threading
 import typing
 
 import numpy as np
@@ -73,15 +72,7 @@ class Limiter:
         return out["i16"] if int16 else out["f32"]
 
 
-_cache_lock = threading.Lock()
-
-
 def get_limiter(engine: Engine, sample_rate: int) -> Limiter:
     """One `Limiter` per (engine, rate), made on first use (the sentence path's `limiter=True`) and kept ON the engine, like
     `get_loudness`."""
-    key = int(sample_rate)
-    with _cache_lock:
-        cache = engine.__dict__.setdefault("_limiters", {})
-        if key not in cache:
-            cache[key] = Limiter(engine, key)
-        return cache[key]
+    return engine.kept("limiter", int(sample_rate), lambda: Limiter(engine, int(sample_rate)))

@@ -6,7 +6,6 @@ here; the library takes its ten coefficients like any other table."""
 from __future__ import annotations
 
 import math
-import threading
 import typing
 
 import numpy as np
@@ -99,15 +98,7 @@ class Loudness:
 
 LEVEL_TOLERANCE = 0.1  # LU: the meter tolerance of EBU Tech 3341, the project's bound on a delivered level
 
-_cache_lock = threading.Lock()
-
-
 def get_loudness(engine: Engine, sample_rate: int) -> Loudness:
-    """One `Loudness` per (engine, rate), made on first use (the sentence path's `loudness=`) and kept ON the engine: it lives
-    and dies with the context its model id belongs to."""
-    key = int(sample_rate)
-    with _cache_lock:
-        cache = engine.__dict__.setdefault("_loudness_meters", {})
-        if key not in cache:
-            cache[key] = Loudness(engine, key)
-        return cache[key]
+    """One `Loudness` per (engine, rate), made on first use (the sentence path's `loudness=`) and kept ON the engine
+    (`Engine.kept`): it lives and dies with the context its model id belongs to."""
+    return engine.kept("loudness", int(sample_rate), lambda: Loudness(engine, int(sample_rate)))

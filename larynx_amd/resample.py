@@ -5,7 +5,6 @@ lives here; the library takes the taps like any other table."""
 from __future__ import annotations
 
 import math
-import threading
 import typing
 
 import numpy as np
@@ -73,15 +72,7 @@ class Resampler:
         return i16 if normalize else f32
 
 
-_cache_lock = threading.Lock()
-
-
 def get_resampler(engine: Engine, rate_in: int, rate_out: int) -> Resampler:
-    """One `Resampler` per (engine, rate pair), made on first use (the sentence path's `sample_rate=`) and kept ON the engine:
-    it lives and dies with the context its model id belongs to."""
-    key = (int(rate_in), int(rate_out))
-    with _cache_lock:
-        cache = engine.__dict__.setdefault("_resamplers", {})
-        if key not in cache:
-            cache[key] = Resampler(engine, rate_in, rate_out)
-        return cache[key]
+    """One `Resampler` per (engine, rate pair), made on first use (the sentence path's `sample_rate=`) and kept ON the engine
+    (`Engine.kept`): it lives and dies with the context its model id belongs to."""
+    return engine.kept("resampler", (int(rate_in), int(rate_out)), lambda: Resampler(engine, rate_in, rate_out))

@@ -23,6 +23,7 @@ from larynx_amd.limiter import design_interpolator, get_limiter, release_coeffic
 from larynx_amd.loudness import get_loudness
 from tests import limiter_np as M
 from tests import loudness_np as L
+from tests.test_emu_resample import numpy_alloc
 
 FS = 22050
 TILE, CHUNK, GROUP = 256, 16, 4096  # LM_TILE, LM_CHUNK, LM_GROUP of csrc/limiter.h
@@ -434,6 +435,47 @@ def check_the_point(eng):
     return tp - CEILING
 
 
+def check_device_pointers(eng, alloc):
+    """MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE: device buffers (`alloc`: tests/test_emu_resample.py; float32 and int16 in, both
+    delivered forms and the curve out, row strides past the rows' samples, outputs pre-filled) give the host call's bits and zero
+    tails up to the strides.  Then a batch whose rows are all empty, to host and to device destinations: zero outputs, a zero
+    curve, true peak 0, gain 1."""
+    cfg = config(eng)
+    batch, gains = ragged_batch()
+    B = len(RAGGED)
+    i16 = np.round(batch * 32767).astype(np.int16)
+    in_ld, out_ld = batch.shape[1], batch.shape[1] + 21
+    flags = ffi.IN_DEVICE | ffi.OUT_DEVICE
+
+    def outputs(buffer):
+        return buffer(np.full((B, out_ld), 7.0, np.float32)), buffer(np.full((B, out_ld), 7, np.int16)), buffer(np.full((B, in_ld), 7.0, np.float32))
+
+    for src in (batch, i16):
+        host = eng.limit(cfg.model_id, src, RAGGED, gain=gains, ceiling=CEILING, want_float=True, want_int16=True, want_curve=True)
+        dev, keep = alloc(src)
+        ptrs = (None, dev) if src.dtype == np.int16 else (dev, None)
+        (pf, get_f), (pi, get_i), (pc, get_c) = outputs(alloc)
+        tp, mg = eng.limit_raw(cfg.model_id, ptrs[0], ptrs[1], RAGGED, in_ld, gains, CEILING, pf, pi, out_ld, pc, flags)
+        f, i, c = get_f(), get_i(), get_c()
+        assert np.array_equal(bits(tp), bits(host["true_peak"])) and np.array_equal(bits(mg), bits(host["min_gain"]))
+        assert np.array_equal(bits(f[:, :in_ld]), bits(host["f32"])) and not f[:, in_ld:].any()
+        assert np.array_equal(i[:, :in_ld], host["i16"]) and not i[:, in_ld:].any()
+        assert np.array_equal(bits(c), bits(host["curve"]))
+        for b, n in enumerate(RAGGED):
+            assert not f[b, n:].any() and not i[b, n:].any() and not c[b, n:].any()
+        # a meter call from device memory
+        tp2, mg2 = eng.limit_raw(cfg.model_id, ptrs[0], ptrs[1], RAGGED, in_ld, None, 1.0, flags=ffi.IN_DEVICE)
+        assert np.array_equal(bits(tp2), bits(tp)) and np.all(mg2 == 1.0)
+        # no sample in any row
+        h_ptrs = (None, src.ctypes.data) if src.dtype == np.int16 else (src.ctypes.data, None)
+        for in_ptrs, buffer, fl in ((h_ptrs, numpy_alloc, 0), (ptrs, alloc, flags)):
+            (pf, get_f), (pi, get_i), (pc, get_c) = outputs(buffer)
+            tp, mg = eng.limit_raw(cfg.model_id, in_ptrs[0], in_ptrs[1], (0, 0, 0), in_ld, gains[:3], CEILING, pf, pi, out_ld, pc, fl)
+            assert not tp.any() and np.all(mg == 1.0)
+            assert not get_f()[:3].any() and not get_i()[:3].any() and not get_c()[:3].any()
+        del keep
+
+
 def check_sentence_path(tts, voc, n_ids=(11, 4, 26)):
     """Item 9, on the TINY models."""
     import larynx_amd
@@ -562,6 +604,10 @@ def test_intersample_peak(emu_engine):
 
 def test_schedule(emu_engine):
     check_schedule(emu_engine)
+
+
+def test_device_pointers(emu_engine):
+    check_device_pointers(emu_engine, numpy_alloc)
 
 
 def test_refusals_and_unload(emu_engine):

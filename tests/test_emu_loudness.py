@@ -338,6 +338,52 @@ def check_refusals(eng):
         eng.load_loudness(c["shelf_b"][:2], c["shelf_a"], c["hp_b"], c["hp_a"], block, hop)
 
 
+def check_device_pointers(eng, alloc):
+    """MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE: device buffers (`alloc`: tests/test_emu_resample.py; float32 and int16 in, both
+    delivered forms and the weighted rows out, row strides past the rows' samples, outputs pre-filled) give the host call's bits
+    and zero tails up to the strides.  Then a batch whose rows are all empty, to host and to device destinations: zero outputs,
+    zero weighted rows, -inf LUFS, gain 1, peak 0."""
+    from tests.test_emu_resample import numpy_alloc
+
+    m = meter(eng).model_id
+    B = len(RAGGED)
+    batch = np.full((B, LONG + 40), 0.25, np.float32)
+    for b, n in enumerate(RAGGED):
+        batch[b, :n] = row(n)
+    i16 = np.round(batch * 32767).astype(np.int16)
+    in_ld, out_ld = batch.shape[1], LONG + 61
+    flags = ffi.IN_DEVICE | ffi.OUT_DEVICE
+
+    def outputs(buffer):
+        return buffer(np.full((B, out_ld), 7.0, np.float32)), buffer(np.full((B, out_ld), 7, np.int16)), buffer(np.full((B, in_ld), 7.0, np.float32))
+
+    for src in (batch, i16):
+        host = eng.loudness(m, src, RAGGED, target=-20.0, ceiling=CEILING, want_float=True, want_int16=True, want_weighted=True)
+        dev, keep = alloc(src)
+        ptrs = (None, dev) if src.dtype == np.int16 else (dev, None)
+        (pf, get_f), (pi, get_i), (pw, get_w) = outputs(alloc)
+        lufs, gain, peak = eng.loudness_raw(m, ptrs[0], ptrs[1], RAGGED, in_ld, -20.0, CEILING, 30.0, pf, pi, out_ld, pw, flags)
+        f, i, w = get_f(), get_i(), get_w()
+        for got, k in ((lufs, "lufs"), (gain, "gain"), (peak, "peak")):
+            assert np.array_equal(bits(got), bits(host[k])), k
+        assert np.array_equal(bits(f[:, :in_ld]), bits(host["f32"])) and not f[:, in_ld:].any()
+        assert np.array_equal(i[:, :in_ld], host["i16"]) and not i[:, in_ld:].any()
+        assert np.array_equal(bits(w), bits(host["weighted"]))
+        for b, n in enumerate(RAGGED):
+            assert not f[b, n:].any() and not i[b, n:].any() and not w[b, n:].any()
+        # measuring only, from device memory
+        lufs2, gain2, _ = eng.loudness_raw(m, ptrs[0], ptrs[1], RAGGED, in_ld, float("nan"), 1.0, 30.0, flags=ffi.IN_DEVICE)
+        assert np.array_equal(bits(lufs2), bits(lufs)) and np.all(gain2 == 1.0)
+        # no sample in any row
+        h_ptrs = (None, src.ctypes.data) if src.dtype == np.int16 else (src.ctypes.data, None)
+        for in_ptrs, buffer, fl in ((h_ptrs, numpy_alloc, 0), (ptrs, alloc, flags)):
+            (pf, get_f), (pi, get_i), (pw, get_w) = outputs(buffer)
+            lufs, gain, peak = eng.loudness_raw(m, in_ptrs[0], in_ptrs[1], (0, 0, 0), in_ld, -20.0, CEILING, 30.0, pf, pi, out_ld, pw, fl)
+            assert np.all(lufs == -np.inf) and np.all(gain == 1.0) and not peak.any()
+            assert not get_f()[:3].any() and not get_i()[:3].any() and not get_w()[:3].any()
+        del keep
+
+
 def check_sentence_path(tts, voc):
     import larynx_amd
     from larynx_amd.resample import get_resampler
@@ -471,6 +517,12 @@ def test_int16_input(emu_engine):
 
 def test_schedule(emu_engine):
     check_schedule(emu_engine)
+
+
+def test_device_pointers(emu_engine):
+    from tests.test_emu_resample import numpy_alloc
+
+    check_device_pointers(emu_engine, numpy_alloc)
 
 
 def test_refusals_and_unload(emu_engine):

@@ -297,6 +297,61 @@ def vocoder(library_path=None):
                              state_dict=synthetic.make_hifigan_state_dict(HP.TINY_HIFIGAN, seed=3), model_config=HP.TINY_HIFIGAN.to_config())
 
 
+def numpy_alloc(a):
+    """`alloc(array)` of the device-pointer checks -> (pointer, fetch) of a device buffer that starts as a copy of `array`;
+    `fetch()` gives its contents.  The emulator's device memory is the host's."""
+    a = np.array(a)
+    return a.ctypes.data, lambda: a
+
+
+def torch_alloc(a):
+    """The same on the GPU (the tensor lives as long as `fetch` does)."""
+    import torch
+
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    torch.cuda.synchronize()
+    return t.data_ptr(), lambda: t.cpu().numpy()
+
+
+def check_device_pointers(eng, alloc):
+    """MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE: device buffers (float32 and int16 in, all three output forms, row strides past the
+    rows' samples, outputs pre-filled) give the host call's bits and zero tails up to out_ld.  Then a batch whose rows are all
+    empty, to host and to device destinations: every output element zero, every length 0."""
+    up, down = 320, 441
+    m = model(eng, up, down)
+    samples = (700, 0, 257)
+    batch = np.full((3, 768), 0.25, np.float32)
+    for b, n in enumerate(samples):
+        batch[b, :n] = R.tone_noise(n, 10 + b)
+    i16 = np.round(batch * 32767).astype(np.int16)
+    ld = R.out_length(700, up, down) + 21
+    flags = ffi.IN_DEVICE | ffi.OUT_DEVICE
+    for src in (batch, i16):
+        host_f, host_sat, n_out = eng.resample(m, src, samples, want_int16=True)
+        _, host_nrm, _ = eng.resample(m, src, samples, want_float=False, want_int16=True, normalize=True)
+        dev, keep = alloc(src)
+        ptrs = (None, dev) if src.dtype == np.int16 else (dev, None)
+        for mode, host_i, with_float in ((ffi.PCM_SATURATE, host_sat, True), (ffi.PCM_NORMALIZE, host_nrm, True), (ffi.PCM_NORMALIZE, host_nrm, False)):
+            (pf, get_f), (pi, get_i) = alloc(np.full((3, ld), 7.0, np.float32)), alloc(np.full((3, ld), 7, np.int16))
+            got = eng.resample_raw(m, ptrs[0], ptrs[1], samples, 768, pf if with_float else None, pi, ld, mode, flags)
+            assert list(got) == list(n_out)
+            f, i = get_f(), get_i()
+            w = host_f.shape[1]
+            if with_float:
+                assert np.array_equal(bits(f[:, :w]), bits(host_f)) and not f[:, w:].any()
+            else:
+                assert np.all(f == 7.0)
+            assert np.array_equal(i[:, :w], host_i) and not i[:, w:].any()
+        # no sample in any row
+        host_src = np.ascontiguousarray(src)
+        h_ptrs = (None, host_src.ctypes.data) if src.dtype == np.int16 else (host_src.ctypes.data, None)
+        for in_ptrs, buffer, fl in ((h_ptrs, numpy_alloc, 0), (ptrs, alloc, flags)):
+            (pf, get_f), (pi, get_i) = buffer(np.full((3, ld), 7.0, np.float32)), buffer(np.full((3, ld), 7, np.int16))
+            got = eng.resample_raw(m, in_ptrs[0], in_ptrs[1], (0, 0, 0), 768, pf, pi, ld, ffi.PCM_SATURATE, fl)
+            assert not got.any() and not get_f().any() and not get_i().any()
+        del keep
+
+
 def check_sentence_path(tts, voc):
     import larynx_amd
     from larynx_amd.streaming import stream_raw_pcm
@@ -477,6 +532,10 @@ def test_refusals_and_unload(emu_engine):
 
 def test_unstaged_path(emu_engine):
     check_direct_path(emu_engine)
+
+
+def test_device_pointers(emu_engine):
+    check_device_pointers(emu_engine, numpy_alloc)
 
 
 def test_sentence_path(emu_library):

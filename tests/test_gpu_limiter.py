@@ -1,17 +1,17 @@
 """The true-peak meter and look-ahead limiter (csrc/limiter.h) on the MI355X: the check functions of tests/test_emu_limiter.py
 under the same rules — bit equality with the float32 restatement without release, the curve within 16 x the restatement's own
 error of the float64 oracle with it, the limiter property, batch rows and int16 input bit for bit —, the launches by kernel name,
-and what only the device has: device pointers, and a golden utterance end to end.  Every test prints what it measured."""
+device pointers as torch tensors, and what only the device has: a golden utterance end to end.  Every test prints what it measured."""
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from larynx_amd import ffi
 from larynx_amd import synthetic
-from tests.test_emu_limiter import (CEILING, FS, GAIN, LIMIT_KERNELS, LONG, METER_KERNELS, RAGGED, TILE, bits, check_exact, check_int16_input,
-                                    check_intersample, check_passthrough, check_ragged_batch, check_refusals, check_release,
-                                    check_schedule, check_sentence_path, check_the_point, config, ragged_batch, row)
+from tests.test_emu_limiter import (CEILING, FS, GAIN, LIMIT_KERNELS, LONG, METER_KERNELS, TILE, check_device_pointers, check_exact,
+                                    check_int16_input, check_intersample, check_passthrough, check_ragged_batch, check_refusals, check_release,
+                                    check_schedule, check_sentence_path, check_the_point, config, row)
+from tests.test_emu_resample import torch_alloc
 
 pytestmark = pytest.mark.gpu
 
@@ -69,35 +69,9 @@ def test_the_target_is_reached(gpu_engine):
 
 
 def test_device_pointers(gpu_engine):
-    """MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE: torch tensors (float32 and int16 in, both delivered forms and the curve out, row
-    strides past the rows' samples, outputs pre-filled) give the host call's bits and zero tails up to the strides."""
-    torch = pytest.importorskip("torch")
-    cfg = config(gpu_engine)
-    batch, gains = ragged_batch()
-    i16 = np.round(batch * 32767).astype(np.int16)
-    in_ld, out_ld = batch.shape[1], batch.shape[1] + 21
-    flags = ffi.IN_DEVICE | ffi.OUT_DEVICE
-    for src in (batch, i16):
-        host = gpu_engine.limit(cfg.model_id, src, RAGGED, gain=gains, ceiling=CEILING, want_float=True, want_int16=True, want_curve=True)
-        dev = torch.from_numpy(src).cuda().contiguous()
-        ptrs = (None, dev.data_ptr()) if src.dtype == np.int16 else (dev.data_ptr(), None)
-        of = torch.full((len(RAGGED), out_ld), 7.0, dtype=torch.float32, device="cuda")
-        oi = torch.full((len(RAGGED), out_ld), 7, dtype=torch.int16, device="cuda")
-        oc = torch.full((len(RAGGED), in_ld), 7.0, dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        tp, mg = gpu_engine.limit_raw(cfg.model_id, ptrs[0], ptrs[1], RAGGED, in_ld, gains, CEILING, of.data_ptr(), oi.data_ptr(), out_ld,
-                                      oc.data_ptr(), flags)
-        torch.cuda.synchronize()
-        f, i, c = of.cpu().numpy(), oi.cpu().numpy(), oc.cpu().numpy()
-        assert np.array_equal(bits(tp), bits(host["true_peak"])) and np.array_equal(bits(mg), bits(host["min_gain"]))
-        assert np.array_equal(bits(f[:, :in_ld]), bits(host["f32"])) and not f[:, in_ld:].any()
-        assert np.array_equal(i[:, :in_ld], host["i16"]) and not i[:, in_ld:].any()
-        assert np.array_equal(bits(c), bits(host["curve"]))
-        for b, n in enumerate(RAGGED):
-            assert not f[b, n:].any() and not i[b, n:].any() and not c[b, n:].any()
-        # a meter call from device memory
-        tp2, mg2 = gpu_engine.limit_raw(cfg.model_id, ptrs[0], ptrs[1], RAGGED, in_ld, None, 1.0, flags=ffi.IN_DEVICE)
-        assert np.array_equal(bits(tp2), bits(tp)) and np.all(mg2 == 1.0)
+    """MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE with torch tensors: tests/test_emu_limiter.py's check on the device's own memory."""
+    pytest.importorskip("torch")
+    check_device_pointers(gpu_engine, torch_alloc)
 
 
 def test_sentence_path(gpu_engine):

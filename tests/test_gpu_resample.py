@@ -1,15 +1,13 @@
 """Resampling (csrc/resample.h) on the MI355X: the check functions of tests/test_emu_resample.py under the same rules — impulses
-bit for bit, the device within 16 x the float32 restatement's own error and under the a-priori bound —, plus what only the device
-has: device pointers, and a row long enough that n * down passes 2^31.  Every test prints what it measured."""
+bit for bit, the device within 16 x the float32 restatement's own error and under the a-priori bound, device pointers
+as torch tensors —, plus what only the device has: a row long enough that n * down passes 2^31.  Every test prints what it measured."""
 import numpy as np
 import pytest
 
-from larynx_amd import ffi
 from tests import resample_np as R
-from tests.test_emu_resample import (RATES, bits, check_direct_path, check_impulses, check_int16_input, check_int16_output,
-                                     check_lengths, check_parity, check_ragged, check_refusals, check_schedule, check_sentence_path,
-                                     check_sentence_path_griffin_lim,
-                                     model, prototype, vocoder)
+from tests.test_emu_resample import (RATES, check_device_pointers, check_direct_path, check_impulses, check_int16_input,
+                                     check_int16_output, check_lengths, check_parity, check_ragged, check_refusals, check_schedule,
+                                     check_sentence_path, check_sentence_path_griffin_lim, model, prototype, torch_alloc, vocoder)
 
 pytestmark = pytest.mark.gpu
 
@@ -53,37 +51,9 @@ def test_unstaged_path(gpu_engine):
 
 
 def test_device_pointers(gpu_engine):
-    """MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE: torch tensors (float32 and int16 in, all three output forms, row strides past the
-    rows' samples, outputs pre-filled) give the host call's bits and zero tails up to out_ld."""
-    torch = pytest.importorskip("torch")
-    up, down = 320, 441
-    m = model(gpu_engine, up, down)
-    samples = (700, 0, 257)
-    batch = np.full((3, 768), 0.25, np.float32)
-    for b, n in enumerate(samples):
-        batch[b, :n] = R.tone_noise(n, 10 + b)
-    i16 = np.round(batch * 32767).astype(np.int16)
-    ld = R.out_length(700, up, down) + 21
-    flags = ffi.IN_DEVICE | ffi.OUT_DEVICE
-    for src in (batch, i16):
-        host_f, host_sat, n_out = gpu_engine.resample(m, src, samples, want_int16=True)
-        _, host_nrm, _ = gpu_engine.resample(m, src, samples, want_float=False, want_int16=True, normalize=True)
-        dev = torch.from_numpy(src).cuda().contiguous()
-        ptrs = (None, dev.data_ptr()) if src.dtype == np.int16 else (dev.data_ptr(), None)
-        for mode, host_i, with_float in ((ffi.PCM_SATURATE, host_sat, True), (ffi.PCM_NORMALIZE, host_nrm, True), (ffi.PCM_NORMALIZE, host_nrm, False)):
-            of = torch.full((3, ld), 7.0, dtype=torch.float32, device="cuda")
-            oi = torch.full((3, ld), 7, dtype=torch.int16, device="cuda")
-            torch.cuda.synchronize()
-            got = gpu_engine.resample_raw(m, ptrs[0], ptrs[1], samples, 768, of.data_ptr() if with_float else None, oi.data_ptr(), ld, mode, flags)
-            torch.cuda.synchronize()
-            assert list(got) == list(n_out)
-            f, i = of.cpu().numpy(), oi.cpu().numpy()
-            w = host_f.shape[1]
-            if with_float:
-                assert np.array_equal(bits(f[:, :w]), bits(host_f)) and not f[:, w:].any()
-            else:
-                assert np.all(f == 7.0)
-            assert np.array_equal(i[:, :w], host_i) and not i[:, w:].any()
+    """MI355TTS_IN_DEVICE | MI355TTS_OUT_DEVICE with torch tensors: tests/test_emu_resample.py's check on the device's own memory."""
+    pytest.importorskip("torch")
+    check_device_pointers(gpu_engine, torch_alloc)
 
 
 def test_positions_past_2_to_31(gpu_engine):
