@@ -520,6 +520,62 @@ int mi355tts_limit(mi355tts_ctx* ctx, int model, const float* in_f32, const int1
                    int64_t in_ld, const float* gain, float ceiling, float* out_f32, int16_t* out_i16, int64_t out_ld,
                    float* true_peak_out, float* min_gain_out, float* curve_out, uint32_t flags);
 
+/* ---- pitch: a YIN F0 tracker for the delivered rows, or any recording -----------
+ * Timing (mi355tts_mel_durations, mi355tts_glow_align) and level (mi355tts_loudness) can be read; this reads the third part of
+ * prosody: the fundamental frequency per frame, with how periodic the frame is and how loud.  YIN (de Cheveigne & Kawahara
+ * 2002) steps 1-5, without the best-local-estimate step; ONE launch per call, whatever N and B are (csrc/pitch.h).  The
+ * reference has no such step.
+ *   Parameters (fixed at load time): sample_rate; hop; window W, a multiple of 4 in [64, 2048]; the lag range 1 <= tau_min <=
+ *                  tau_max <= 1024 with W + tau_max <= 3072; threshold theta in (0, 1]; interpolate (0 / 1).
+ *   Frames:        a row of N samples has F = floor(N / hop) frames (none for N < hop); frame t starts at s = t hop - W / 2, so
+ *                  it is centred on hop t like a frame of mi355tts_mel_from_audio; x[i] = 0 for i outside [0, N); int16
+ *                  samples are s * 2^-15 (exact).  No state across calls.
+ *   1 Difference   d(tau) = sum_{j < W} (x[s + j] - x[s + j + tau])^2 for tau = 1 .. tau_max, in f32, in the DIFFERENCE FORM:
+ *                  one subtraction, then one fma per term (never r(0) - 2 r(tau)), so a signal with an integer period P has
+ *                  d(P) == 0 exactly.  Order: four accumulators from +0, accumulator m takes the terms j = m (mod 4) with j
+ *                  ascending; d = (a0 + a1) + (a2 + a3).
+ *   2 Level        r0 = sum_j x[s + j]^2: 256 accumulators from +0, accumulator i takes j = i, i + 256, .. ascending, one fma
+ *                  per term; the accumulators 64 w .. 64 w + 63 are summed by a butterfly (v[l] += v[l ^ m] for m = 32, 16, ..
+ *                  1), and r0 = (p0 + p1) + (p2 + p3) over the four results.  level_db = 10 log10f(r0 / W) where r0 / W >
+ *                  1e-10, else -100 (= 10 log10 of the floor 1e-10).
+ *   3 Normalise    c(tau) = sum_{k <= tau} d(k); d'(0) = 1; d'(tau) = c(tau) > 0 ? (d(tau) * tau) / c(tau) : 1 (one f32
+ *                  product, one correctly rounded f32 division).  Order of c: the lags 1 .. 1024 (d = 0 behind tau_max) in
+ *                  256 groups of four, l1 .. l4 the running sums inside a group in sequence; an inclusive Hillis-Steele scan
+ *                  of l4 over each 64 groups (v[i] += v[i - st] for i >= st, st = 1, 2, .. 32); the four scans' totals added in
+ *                  sequence, T0, T0 + T1, (T0 + T1) + T2; c = (offset of the 64 groups + the scan value of the group before,
+ *                  0 for the first) + l_m.
+ *   4 Pick         tau_p = the smallest tau in [tau_min, tau_max] with d'(tau) < theta, advanced while tau_p + 1 <= tau_max
+ *                  and d'(tau_p + 1) < d'(tau_p).  No such tau: the frame is UNVOICED, f0 = 0, and tau_p is the first
+ *                  minimiser of d' over the range.
+ *   5 Outputs      periodicity = max(0, 1 - d'(tau_p)).  Voiced: f0 = sample_rate / tau*, tau* = tau_p + (0.5 (a - c)) /
+ *                  ((a - 2 b) + c) on a, b, c = d'(tau_p - 1), d'(tau_p), d'(tau_p + 1) when interpolate is set, tau_p - 1 >=
+ *                  1, tau_p + 1 <= tau_max and the denominator is > 0; else tau* = tau_p.  All f32, in this order.
+ *   Outputs:       f0_out / periodicity_out / level_db_out [B][out_ld], each optional but at least one given; out_ld >= the
+ *                  longest row's frame count; entries behind a row's frames are written 0.  cmnd_out (optional) [B][out_ld]
+ *                  [tau_max + 1]: d' of every frame (zeros behind a row's frames), so that a test can see the whole kernel.
+ *                  Host, or device with MI355TTS_OUT_DEVICE; the input host, or device with MI355TTS_IN_DEVICE.
+ *   Arithmetic:    every order above is fixed by the frame alone.  No atomics.  Row b of a batch gives the bits of its own
+ *                  batch-1 call; int16 input gives the bits of the equal f32 input; host and device pointers give the same
+ *                  bits.  A batch whose rows all have no frame is valid, writes the zeros and launches nothing.
+ * mi355tts_load_pitch: checks and keeps the parameters; mi355tts_unload frees the model.  mi355tts_pitch_frames: floor(samples /
+ * hop).  mi355tts_pitch: exactly one of in_f32 / in_i16 [B][in_ld]; row b holds samples[b] <= in_ld samples (host array).  The
+ * workspace grows on demand (mi355tts_reserve does not cover this call).
+ * MI355TTS_ERR_INVALID with the reason (MI355TTS_ERR_NO_MODEL for an unknown id): null pointers; sample_rate < 1; hop outside
+ * [1, 4096]; window not a multiple of 4 in [64, 2048]; not 1 <= tau_min <= tau_max <= 1024; window + tau_max > 3072; threshold
+ * outside (0, 1]; both inputs or neither; no result plane; samples[b] outside [0, in_ld] or above 2^30; out_ld below the longest
+ * row's frame count.
+ * Added in ABI version 2 (additive: the version number is unchanged). */
+typedef struct {
+  int32_t sample_rate, hop, window, tau_min, tau_max;
+  float threshold;
+  int32_t interpolate;
+} mi355tts_pitch_params;
+int mi355tts_load_pitch(mi355tts_ctx* ctx, const mi355tts_pitch_params* params, int* model_out);
+int64_t mi355tts_pitch_frames(mi355tts_ctx* ctx, int model, int64_t samples);
+int mi355tts_pitch(mi355tts_ctx* ctx, int model, const float* in_f32, const int16_t* in_i16, const int64_t* samples, int B,
+                   int64_t in_ld, float* f0_out, float* periodicity_out, float* level_db_out, float* cmnd_out, int64_t out_ld,
+                   uint32_t flags);
+
 /* ---- fused call: replaces the model half of _sentence_task -------------------
  * (larynx/__init__.py:229-283: phonemes_to_mels -> mel transforms -> mels_to_audio -> pause
  * padding) with ONE call on one stream: arguments as in mi355tts_glow_infer +
@@ -681,8 +737,8 @@ int mi355tts_profile_kernels_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Launches per kernel NAME since the last mi355tts_profile_reset, {"rb_group_kernel": n, ...}; counted whether profiling is
  * on or not.  The class counters cannot tell a kernel from the fallback that would silently take its place (same launch count,
  * same bits by design): the device tests assert on these.  The first 44 keys and their order are fixed and always present,
- * zero or not; the names of later entry points (the six loudness_*_kernel, the five limiter_*_kernel) follow them once they have launched since the last
- * reset.  No reference counterpart (measurement only). */
+ * zero or not; the names of later entry points (the six loudness_*_kernel, the five limiter_*_kernel, pitch_kernel) follow them once they
+ * have launched since the last reset.  No reference counterpart (measurement only). */
 int mi355tts_kernel_counts_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Median elapsed time (microseconds) of `pairs` EMPTY event pairs on an idle stream: what the two hipEventRecord calls around a
  * profiled launch add to its event-timed duration (rocprofv3's kernel durations do not contain it). */

@@ -222,6 +222,16 @@ def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocode
     return audio, tts_mels, lead, resampler
 
 
+def _with_pitch(task, engine, sample_rate, aligned, *args):
+    """`task(*args)` with the YIN track of the audio it delivered (at `sample_rate`, pauses included) behind it, in the same pool
+    thread: (audio, spans or None, track, per-phoneme pitch or None)."""
+    from .pitch import get_pitch_tracker, pitch_per_span
+
+    audio, spans = task(*args) if aligned else (task(*args), None)
+    track = get_pitch_tracker(engine, sample_rate).track(np.ascontiguousarray(audio))
+    return audio, spans, track, (pitch_per_span(track, spans) if aligned else None)
+
+
 def _ensure_pool_workers(executor, *models):
     """One worker per pool thread (+ a spare) on the models' engine before the first sentence is submitted: the engine then knows
     which worker streams share a hardware queue and spreads the sentences' calls evenly (Engine.ensure_workers)."""
@@ -240,7 +250,7 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
                        executor: typing.Optional[Executor] = None, alignment: bool = False,
                        sample_rate: typing.Optional[int] = None,
                        loudness: typing.Optional[float] = None,
-                       limiter: typing.Optional[bool] = None) -> typing.Iterable[TextToSpeechResult]:
+                       limiter: typing.Optional[bool] = None, pitch: bool = False) -> typing.Iterable[TextToSpeechResult]:
     """`text_to_speech` (`larynx/__init__.py:47-190`) from the point where gruut /
     phonemes2ids have produced ids: one task per sentence on an executor, results
     yielded in submission order.  `alignment`: every result also carries `phoneme_spans`, the start and end sample
@@ -249,9 +259,13 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
     ceil(n * up / down) samples, spans scaled to match); `None` or the voice's rate changes nothing.  `loudness`: deliver
     every sentence at that many LUFS instead of with its peak on 32767 (`sentence_task_leveled`); `None` changes nothing.
     `limiter=True` (only together with `loudness`): through the true-peak limiter, so that the level is reached whatever the
-    sentence's peaks (`sentence_task_limited`); `None` or `False` changes nothing."""
+    sentence's peaks (`sentence_task_limited`); `None` or `False` changes nothing.  `pitch=True`: every result also carries
+    `pitch`, the YIN track of its delivered audio at the delivered rate, pauses included (`larynx_amd.pitch`), and, together
+    with `alignment`, `phoneme_pitch`, the median f0 and voiced share of every phoneme; the audio is the same either way."""
     if limiter and loudness is None:
         raise ValueError("limiter: valid only together with loudness")
+    if pitch and getattr(vocoder_model, "engine", None) is None:
+        raise ValueError("pitch: the vocoder has no HIP engine to track on")
     own = executor is None
     executor = executor or ThreadPoolExecutor()
     _ensure_pool_workers(executor, tts_model, vocoder_model)
@@ -267,12 +281,21 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
             if limiter:
                 task = (functools.partial(sentence_task_aligned, sample_rate=sr, loudness=float(loudness), limiter=True) if alignment
                         else functools.partial(sentence_task_limited, sample_rate=sr, loudness=float(loudness)))
+        if pitch:  # (a wrapper around whichever task the other switches chose; made here, once, before the pool needs it)
+            from .pitch import get_pitch_tracker
+
+            get_pitch_tracker(vocoder_model.engine, sr)
+            task = functools.partial(_with_pitch, task, vocoder_model.engine, sr, alignment)
         futures = []
         for text, ids in sentences:
             fut = executor.submit(task, text, np.asarray(ids, np.int64), audio_settings, tts_model, tts_settings,
                                   vocoder_model, vocoder_settings)
             futures.append((text, fut))
         for text, fut in futures:
+            if pitch:
+                audio, spans, track, per_phoneme = fut.result()
+                yield TextToSpeechResult(text=text, audio=audio, sample_rate=sr, phoneme_spans=spans, pitch=track, phoneme_pitch=per_phoneme)
+                continue
             audio, spans = fut.result() if alignment else (fut.result(), None)
             yield TextToSpeechResult(text=text, audio=audio, sample_rate=sr, phoneme_spans=spans)
     finally:

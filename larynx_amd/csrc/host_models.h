@@ -455,6 +455,12 @@ struct LimiterModel {
   }
 };
 
+// A pitch tracker (pitch.h) is its parameters alone: nothing lives on the device
+struct PitchModel {
+  static constexpr const char* missing = "no pitch tracker %d";
+  mi355tts_pitch_params p;
+};
+
 static std::vector<std::pair<std::string, int64_t>> glow_manifest(const mi355tts_glow_hparams& h) {
   std::vector<std::pair<std::string, int64_t>> m;
   auto add = [&](const std::string& n, int64_t e) { m.emplace_back(n, e); };

@@ -800,6 +800,45 @@ class Engine:
         )
         return res[0], res[1]
 
+    # ---- pitch ---------------------------------------------------------------------
+    def load_pitch(self, sample_rate: int, hop: int, window: int, tau_min: int, tau_max: int, threshold: float = 0.15,
+                   interpolate: bool = True) -> int:
+        """`mi355tts_load_pitch`: a YIN tracker from its rate, hop, window, lag range [tau_min, tau_max], threshold on d' and
+        interpolation switch (`larynx_amd.pitch.PitchTracker` derives them from a frequency range).  `unload` frees it."""
+        p = ffi.PitchParamsC(int(sample_rate), int(hop), int(window), int(tau_min), int(tau_max), float(threshold), int(bool(interpolate)))
+        model = C.c_int()
+        ffi.check(self.lib, self.lib.mi355tts_load_pitch(self._ctx, C.byref(p), C.byref(model)))
+        return int(model.value)
+
+    def pitch_frames(self, model: int, samples: int) -> int:
+        """`mi355tts_pitch_frames`: floor(samples / hop)."""
+        return int(ffi.check(self.lib, self.lib.mi355tts_pitch_frames(self._ctx, int(model), int(samples))))
+
+    def pitch(self, model: int, audio: np.ndarray, samples=None, want_cmnd: int = 0) -> dict:
+        """`audio`: float32 or int16 (read as s / 32768), [N] or [B, N], row b valid for `samples[b]` entries (default: all) ->
+        {"f0", "periodicity", "level_db": float32 [B, F]; "cmnd": [B, F, tau_max + 1] or None; "frames": int64 [B]}, F the
+        longest row's frame count, rows zero-filled behind their frames.  `want_cmnd`: tau_max + 1 of the model, to receive d'
+        of every frame.  A 1-D input gives 1-D rows."""
+        audio, flat, B, N, n, f_in, i_in = self._audio_in(audio, samples)
+        frames = np.array([self.pitch_frames(model, int(v)) if 0 <= v <= N else 0 for v in n], np.int64)
+        ld = int(frames.max(initial=0))
+        f0, per, lvl = (np.empty((B, ld), np.float32) for _ in range(3))
+        cmnd = np.empty((B, ld, int(want_cmnd)), np.float32) if want_cmnd else None
+        self.pitch_raw(model, f_in, i_in, n, N, ffi.ptr(f0), ffi.ptr(per), ffi.ptr(lvl), ffi.ptr(cmnd), ld)
+        f0, per, lvl, cmnd = self._rows_out(flat, f0, per, lvl, cmnd)
+        return {"f0": f0, "periodicity": per, "level_db": lvl, "cmnd": cmnd, "frames": frames}
+
+    def pitch_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, f0_ptr=None, periodicity_ptr=None, level_ptr=None,
+                  cmnd_ptr=None, out_ld: int = 0, flags: int = 0) -> None:
+        """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE); the planes [B][out_ld]
+        (at least one of the first three) and the d' rows [B][out_ld][tau_max + 1] (device memory with ffi.OUT_DEVICE)."""
+        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_pitch(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+                                    f0_ptr, periodicity_ptr, level_ptr, cmnd_ptr, int(out_ld), int(flags)),
+        )
+
     # ---- single operators ------------------------------------------------------
     def conv1d(self, x, w, bias=None, dilation=1, in_slope=1.0, out_act=0, lens=None) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

@@ -103,6 +103,13 @@ class LimiterParamsC(C.Structure):
     _fields_ = [("oversample", C.c_int32), ("half_len", C.c_int32), ("lookahead", C.c_int32), ("release", C.c_float)]
 
 
+class PitchParamsC(C.Structure):
+    """`mi355tts_pitch_params`: the rate, the hop, the window, the lag range, the threshold on d' and the interpolation switch."""
+
+    _fields_ = [("sample_rate", C.c_int32), ("hop", C.c_int32), ("window", C.c_int32), ("tau_min", C.c_int32), ("tau_max", C.c_int32),
+                ("threshold", C.c_float), ("interpolate", C.c_int32)]
+
+
 PCM_SATURATE = 0  # MI355TTS_PCM_*: clamp(rint(y * 32768)) / the reference's audio_float_to_int16 on the resampled row
 PCM_NORMALIZE = 1
 
@@ -203,6 +210,9 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
         C.c_int,
         [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, _VP, C.c_float, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_uint32],
     ),
+    "mi355tts_load_pitch": (C.c_int, [_VP, C.POINTER(PitchParamsC), C.POINTER(C.c_int)]),
+    "mi355tts_pitch_frames": (C.c_int64, [_VP, C.c_int, C.c_int64]),
+    "mi355tts_pitch": (C.c_int, [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, C.c_uint32]),
     "mi355tts_synthesize": (
         C.c_int,
         [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,

@@ -87,3 +87,7 @@ class TextToSpeechResult:
     # int64 [P, 2]: start and end sample of every phoneme id in `audio` (larynx_amd.alignment.phoneme_spans); only with
     # phonemes_to_speech(alignment=True).  Not in the reference's record.
     phoneme_spans: typing.Optional[np.ndarray] = None
+    # the YIN track of `audio` (larynx_amd.pitch.PitchTrack), only with phonemes_to_speech(pitch=True); with alignment too,
+    # float32 [P, 2]: the median f0 and the voiced share of every phoneme (larynx_amd.pitch.pitch_per_span)
+    pitch: typing.Optional[typing.Any] = None
+    phoneme_pitch: typing.Optional[np.ndarray] = None
