@@ -576,6 +576,67 @@ int mi355tts_pitch(mi355tts_ctx* ctx, int model, const float* in_f32, const int1
                    int64_t in_ld, float* f0_out, float* periodicity_out, float* level_db_out, float* cmnd_out, int64_t out_ld,
                    uint32_t flags);
 
+/* ---- pitch shift and tempo: a period-synchronous overlap-add stretch ------------
+ * Timing and level can be set (durations, id_length_scales; mi355tts_loudness, mi355tts_limit); this sets the third part of
+ * prosody.  A pitch shift by rho = up / down is a time stretch by rho followed by resampling by down / up; only the stretch is
+ * new: an overlap-add of windowed frames, each frame's read position moved by a whole number of local pitch periods (the period
+ * from mi355tts_pitch's f0 of the same row), so that overlapping frames stay in phase.  Time domain, no transcendental function;
+ * csrc/shift.h.  The reference has no such step.  This is resampling, NOT PSOLA: the formants move with the pitch, so the PITCH
+ * mode is meant for about +-4 semitones.  One ratio per model and per call.
+ *   Parameters (fixed at load time): up, down coprime, each in [1, 64]; window = N, a multiple of 4 in [64, 2048], Hs = N / 2; the
+ *                  window w[N], the caller's (finite values; larynx_amd.shift.ola_window: a periodic Hann whose halves sum to 1);
+ *                  pitch = the id of a loaded pitch model (its sample_rate, hop = hop_p and lag range are used); resampler = the
+ *                  id of a loaded resampler whose (up, down) is this model's (down, up), or 0.  A resampler gives the PITCH mode
+ *                  (same duration, pitch x up / down), 0 the TEMPO mode (duration x up / down, pitch unchanged).  The model pins
+ *                  both: unloading their ids later does not break it.
+ *   1 Periods      f0[j], j < Fp = floor(n / hop_p): exactly what mi355tts_pitch gives for the row (the same launch).
+ *   2 Positions    L = ceil(n up / down); K = L > 0 ? (L - 1) / Hs + 2 : 0 frames; for k < K: c_k = floor(k Hs down / up) (64-bit),
+ *                  a_k = c_k - Hs.  s_0 = a_0.  For k >= 1: j = min(Fp - 1, (c_k + hop_p / 2) / hop_p); Fp == 0 or f0[j] == 0
+ *                  (unvoiced): s_k = a_k; else T = (float)sample_rate / f0[j] (one correctly rounded f32 division), e = (s_(k-1)
+ *                  + Hs) - a_k, q = rintf((float)e / T), m = rintf(q * T) (one f32 product, nothing fused), s_k = a_k + (e -
+ *                  (int)m).  rintf rounds half to even.  Integers are 32-bit but c_k.
+ *   3 Overlap-add  for t in [0, L): k1 = t / Hs, i2 = t - k1 Hs, i1 = i2 + Hs,
+ *                  y[t] = rn(rn(w[i1] x[s_k1 + i1]) + rn(w[i2] x[s_(k1+1) + i2])): two f32 products and one f32 add, each rounded
+ *                  by itself, NO fused multiply-add; x[i] = 0 outside [0, n); int16 samples are s * 2^-15 (exact).
+ *   4 Delivery     TEMPO: y, L samples.  PITCH: the first n samples of what mi355tts_resample defines for y (a row of L samples)
+ *                  with the pinned resampler — it would yield ceil(L down / up) >= n; only n are computed — in mi355tts_resample's
+ *                  arithmetic and term order.
+ *   Outputs:       mi355tts_resample's: out_f32 and / or out_i16 [B][out_ld], pcm_mode MI355TTS_PCM_SATURATE or _NORMALIZE (the peak
+ *                  is that of the row's delivered samples); entries behind a row's samples are written 0; samples_out[b]
+ *                  (optional) = the row's delivered length.  positions_out (optional) int32 [B][pos_ld]: the s_k, zeros behind a
+ *                  row's K, so that a test can see the whole kernel; f0_out (optional) [B][f0_ld]: the plane of step 1.  Outputs
+ *                  are host, or device with MI355TTS_OUT_DEVICE; the input (and positions_in) host, or device with
+ *                  MI355TTS_IN_DEVICE.
+ *   positions_in   (optional) int32 [B][pos_ld]: replaces steps 1 and 2 by the caller's positions, any values (reads outside the
+ *                  row are zeros).  A call's own positions_out fed back reproduce its output bit for bit.  Not together with
+ *                  positions_out / f0_out.
+ *   Arithmetic:    every order above is fixed by the row alone.  No atomics.  Row b of a batch gives the bits of its own batch-1
+ *                  call; int16 input gives the bits of the equal f32 input; host and device pointers give the same bits.
+ *   Launches:      pitch_kernel, shift_mark_kernel (one wave per row: the recurrence is serial in k), shift_ola_kernel, then PITCH:
+ *                  the resampler's one launch, two with MI355TTS_PCM_NORMALIZE; TEMPO: that second launch alone with
+ *                  MI355TTS_PCM_NORMALIZE.  With positions_in the first two are not run; pitch_kernel is not run where no row holds a pitch
+ *                  frame (every n < hop_p).  A batch whose rows are all empty launches
+ *                  nothing and writes zeros.
+ * mi355tts_load_shift: checks the parameters, pins the two models, uploads the window; mi355tts_unload frees the model.
+ * mi355tts_shift_length: the delivered length of a row of `samples`: samples (PITCH) or ceil(samples up / down) (TEMPO), for 0 <=
+ * samples <= 2^24.  mi355tts_shift: exactly one of in_f32 / in_i16 [B][in_ld], at least one of out_f32 / out_i16.  The workspace
+ * grows on demand (mi355tts_reserve does not cover this call).
+ * MI355TTS_ERR_INVALID with the reason (MI355TTS_ERR_NO_MODEL for an unknown id): null pointers; up / down outside [1, 64] or not
+ * coprime; window not a multiple of 4 in [64, 2048]; a window value that is not finite; a resampler whose ratio is not (down, up);
+ * up == down together with a resampler; both inputs or neither; no output; an unknown pcm_mode; samples[b] outside [0, in_ld] or
+ * above 2^24; out_ld below the longest row's delivered length; pos_ld below the longest row's K (with positions_in or
+ * positions_out); f0_ld below the longest row's Fp (with f0_out); positions_in together with positions_out or f0_out.
+ * Added in ABI version 2 (additive: the version number is unchanged). */
+typedef struct {
+  int32_t up, down, window;
+  int32_t pitch, resampler; /* model ids; resampler 0 = TEMPO mode */
+} mi355tts_shift_params;
+int mi355tts_load_shift(mi355tts_ctx* ctx, const mi355tts_shift_params* params, const float* window, int* model_out);
+int64_t mi355tts_shift_length(mi355tts_ctx* ctx, int model, int64_t samples);
+int mi355tts_shift(mi355tts_ctx* ctx, int model, const float* in_f32, const int16_t* in_i16, const int64_t* samples, int B,
+                   int64_t in_ld, const int32_t* positions_in, float* out_f32, int16_t* out_i16, int64_t out_ld, int pcm_mode,
+                   int32_t* positions_out, int64_t pos_ld, float* f0_out, int64_t f0_ld, int64_t* samples_out, uint32_t flags);
+
 /* ---- fused call: replaces the model half of _sentence_task -------------------
  * (larynx/__init__.py:229-283: phonemes_to_mels -> mel transforms -> mels_to_audio -> pause
  * padding) with ONE call on one stream: arguments as in mi355tts_glow_infer +
@@ -737,8 +798,8 @@ int mi355tts_profile_kernels_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Launches per kernel NAME since the last mi355tts_profile_reset, {"rb_group_kernel": n, ...}; counted whether profiling is
  * on or not.  The class counters cannot tell a kernel from the fallback that would silently take its place (same launch count,
  * same bits by design): the device tests assert on these.  The first 44 keys and their order are fixed and always present,
- * zero or not; the names of later entry points (the six loudness_*_kernel, the five limiter_*_kernel, pitch_kernel) follow them once they
- * have launched since the last reset.  No reference counterpart (measurement only). */
+ * zero or not; the names of later entry points (the six loudness_*_kernel, the five limiter_*_kernel, pitch_kernel,
+ * shift_mark_kernel, shift_ola_kernel) follow them once they have launched since the last reset.  No reference counterpart (measurement only). */
 int mi355tts_kernel_counts_json(mi355tts_ctx* ctx, char* buf, int cap);
 /* Median elapsed time (microseconds) of `pairs` EMPTY event pairs on an idle stream: what the two hipEventRecord calls around a
  * profiled launch add to its event-timed duration (rocprofv3's kernel durations do not contain it). */

@@ -35,7 +35,7 @@ _LOGGER = logging.getLogger("larynx_amd")
 __all__ = [
     "AudioSettings", "InferenceBackend", "TextToSpeechResult", "load_tts_model", "load_vocoder_model",
     "sentence_task", "sentence_task_aligned", "sentence_task_at_rate", "sentence_task_leveled", "sentence_task_limited",
-    "phonemes_to_speech",
+    "sentence_task_shifted", "phonemes_to_speech",
 ]
 
 
@@ -120,12 +120,39 @@ def sentence_task_aligned(text: str, phoneme_ids, audio_settings, tts_model, tts
     Griffin-Lim vocoder the spans are nominal frame positions (hop 256), see `phoneme_spans`.  With `sample_rate` (see
     `sentence_task_at_rate`) the spans are positions in the delivered audio: both ends scaled by (s * up) // down.  `loudness`
     (see `sentence_task_leveled`; with `limiter`, `sentence_task_limited`) changes the level of the audio, not the spans."""
+    return _aligned(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
+                    pause_after_ms, sample_rate, loudness, limiter)
+
+
+def sentence_task_shifted(text: str, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                          pause_before_ms: int = 0, pause_after_ms: int = 0, sample_rate: typing.Optional[int] = None,
+                          loudness: typing.Optional[float] = None, limiter: typing.Optional[bool] = None,
+                          pitch_shift: typing.Optional[float] = None, alignment: bool = False):
+    """`sentence_task` with the voice's pitch moved by `pitch_shift` semitones (in [-12, 12]; meant for about +-4: the formants
+    move with the pitch): the vocoder's FLOAT row, SSML pauses included, goes through the period-synchronous pitch shifter on
+    the device at the voice's rate (`larynx_amd.shift`) BEFORE `sample_rate`, `loudness` and `limiter` act on it as in the
+    other tasks; with none of them the shifter's own normalised int16 is delivered (the peak lands on 32767 after the shift).
+    The duration is unchanged.  `alignment`: `(audio, spans)` as `sentence_task_aligned` gives them, the spans unchanged by
+    the shift.  `None` or 0 semitones is the task the other arguments name."""
+    shifter = _shifter_for(vocoder_model, audio_settings, pitch_shift)
+    if alignment:
+        return _aligned(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
+                        pause_after_ms, sample_rate, loudness, limiter, shifter)
+    if limiter and loudness is None:
+        raise ValueError("limiter: valid only together with loudness")
+    return _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings,
+                     pause_before_ms, pause_after_ms, sample_rate, loudness, bool(limiter), shifter)[0]
+
+
+def _aligned(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
+             pause_after_ms, sample_rate, loudness, limiter, shifter=None):
     if limiter and loudness is None:
         raise ValueError("limiter: valid only together with loudness")
     settings = dict(tts_settings or {})
     settings["alignment"] = True
     audio, mels, before, resampler = _sentence(text, phoneme_ids, audio_settings, tts_model, settings, vocoder_model,
-                                               vocoder_settings, pause_before_ms, pause_after_ms, sample_rate, loudness, bool(limiter))
+                                               vocoder_settings, pause_before_ms, pause_after_ms, sample_rate, loudness, bool(limiter),
+                                               shifter)
     from .alignment import phoneme_spans, scale_spans
 
     durations = getattr(mels, "durations", None)
@@ -150,6 +177,21 @@ def _resampler_for(vocoder_model, audio_settings, sample_rate):
     return get_resampler(engine, voice_rate, sample_rate)
 
 
+def _shifter_for(vocoder_model, audio_settings, pitch_shift):
+    """The cached `PitchShifter` at the voice's rate for `pitch_shift` semitones, or None for None / 0; outside [-12, 12]: a
+    ValueError."""
+    if pitch_shift is None:
+        return None
+    from .shift import check_semitones, get_pitch_shifter
+
+    if check_semitones(pitch_shift) == 0.0:
+        return None
+    engine = getattr(vocoder_model, "engine", None)
+    if engine is None:
+        raise ValueError("pitch_shift: the vocoder has no HIP engine to shift on")
+    return get_pitch_shifter(engine, audio_settings.sample_rate if audio_settings is not None else 22050, pitch_shift)
+
+
 def _float_row(vocoder_model, mels, vocoder_settings, before, after) -> np.ndarray:
     """The vocoder's float signal with the SSML pauses in it: what is resampled BEFORE the int16 normalisation."""
     padded = getattr(vocoder_model, "mels_to_float_padded", None)
@@ -162,9 +204,9 @@ def _float_row(vocoder_model, mels, vocoder_settings, before, after) -> np.ndarr
 
 
 def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocoder_model, vocoder_settings, pause_before_ms,
-              pause_after_ms, deliver_rate=None, deliver_lufs=None, limited=False):
+              pause_after_ms, deliver_rate=None, deliver_lufs=None, limited=False, shifter=None):
     """-> (audio, the mels the vocoder consumed, leading pause in samples at the voice's rate, the `Resampler` the audio went
-    through or None)"""
+    through or None).  `shifter` (a `PitchShifter` at the voice's rate): the float row goes through it first."""
     t0 = time.perf_counter()
     mels = tts_model.phonemes_to_mels(phoneme_ids, settings=tts_settings)
     tts_mels = mels
@@ -184,14 +226,23 @@ def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocode
     t2 = time.perf_counter()
     resampler = _resampler_for(vocoder_model, audio_settings, deliver_rate)
     padded = getattr(vocoder_model, "mels_to_audio_padded", None)
-    if deliver_lufs is not None:
+    shifted = None
+    if shifter is not None:
+        # the float row, pauses included, shifted at the voice's rate: what the delivery stages below then take, or — with none
+        # of them — the shifter's own normalised int16
+        shifted = shifter.shift(_float_row(vocoder_model, mels, vocoder_settings, before, after),
+                                normalize=deliver_lufs is None and resampler is None)
+    if shifted is not None and deliver_lufs is None and resampler is None:
+        audio = shifted
+        before = after = 0
+    elif deliver_lufs is not None:
         # a level target: the float row, pauses included, at the delivered rate; measured, scaled and made int16 on the device
         engine = getattr(vocoder_model, "engine", None)
         if engine is None:
             raise ValueError("loudness: the vocoder has no HIP engine to measure on")
         from .loudness import get_loudness
 
-        row = _float_row(vocoder_model, mels, vocoder_settings, before, after)
+        row = shifted if shifted is not None else _float_row(vocoder_model, mels, vocoder_settings, before, after)
         if resampler is not None:
             row = resampler.resample(row)
             sample_rate = resampler.rate_out
@@ -204,7 +255,8 @@ def _sentence(text, phoneme_ids, audio_settings, tts_model, tts_settings, vocode
         before = after = 0
     elif resampler is not None:
         # another rate: the float row, pauses included, resampled on the device and normalised to int16 there
-        audio = resampler.resample(_float_row(vocoder_model, mels, vocoder_settings, before, after), normalize=True)
+        row = shifted if shifted is not None else _float_row(vocoder_model, mels, vocoder_settings, before, after)
+        audio = resampler.resample(row, normalize=True)
         sample_rate = resampler.rate_out
         before = after = 0
     elif padded is not None and (before or after):
@@ -250,7 +302,8 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
                        executor: typing.Optional[Executor] = None, alignment: bool = False,
                        sample_rate: typing.Optional[int] = None,
                        loudness: typing.Optional[float] = None,
-                       limiter: typing.Optional[bool] = None, pitch: bool = False) -> typing.Iterable[TextToSpeechResult]:
+                       limiter: typing.Optional[bool] = None, pitch: bool = False,
+                       pitch_shift: typing.Optional[float] = None) -> typing.Iterable[TextToSpeechResult]:
     """`text_to_speech` (`larynx/__init__.py:47-190`) from the point where gruut /
     phonemes2ids have produced ids: one task per sentence on an executor, results
     yielded in submission order.  `alignment`: every result also carries `phoneme_spans`, the start and end sample
@@ -261,9 +314,13 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
     `limiter=True` (only together with `loudness`): through the true-peak limiter, so that the level is reached whatever the
     sentence's peaks (`sentence_task_limited`); `None` or `False` changes nothing.  `pitch=True`: every result also carries
     `pitch`, the YIN track of its delivered audio at the delivered rate, pauses included (`larynx_amd.pitch`), and, together
-    with `alignment`, `phoneme_pitch`, the median f0 and voiced share of every phoneme; the audio is the same either way."""
+    with `alignment`, `phoneme_pitch`, the median f0 and voiced share of every phoneme; the audio is the same either way.
+    `pitch_shift`: move the voice's pitch by that many semitones, in [-12, 12] (`sentence_task_shifted`: the float row is
+    shifted on the device at the voice's rate before `sample_rate`, `loudness` and `limiter` act; duration and `phoneme_spans`
+    unchanged; `pitch=True` then reads the shifted pitch); `None` or 0 changes nothing and runs nothing new."""
     if limiter and loudness is None:
         raise ValueError("limiter: valid only together with loudness")
+    shifting = _shifter_for(vocoder_model, getattr(tts_model, "audio_settings", None), pitch_shift) is not None  # (made here, once)
     if pitch and getattr(vocoder_model, "engine", None) is None:
         raise ValueError("pitch: the vocoder has no HIP engine to track on")
     own = executor is None
@@ -281,6 +338,9 @@ def phonemes_to_speech(sentences: typing.Iterable[typing.Tuple[str, typing.Seque
             if limiter:
                 task = (functools.partial(sentence_task_aligned, sample_rate=sr, loudness=float(loudness), limiter=True) if alignment
                         else functools.partial(sentence_task_limited, sample_rate=sr, loudness=float(loudness)))
+        if shifting:  # (the one task that takes every other switch)
+            task = functools.partial(sentence_task_shifted, sample_rate=sr, loudness=None if loudness is None else float(loudness),
+                                     limiter=bool(limiter), pitch_shift=float(pitch_shift), alignment=alignment)
         if pitch:  # (a wrapper around whichever task the other switches chose; made here, once, before the pool needs it)
             from .pitch import get_pitch_tracker
 

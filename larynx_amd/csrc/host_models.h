@@ -461,6 +461,21 @@ struct PitchModel {
   mi355tts_pitch_params p;
 };
 
+// A pitch shifter (shift.h): its overlap-add window [N] on the device, and the two models it runs, PINNED like a call pins its
+// models: unloading their ids does not take them from under it.  No resampler = the TEMPO mode.
+struct ShiftModel {
+  static constexpr const char* missing = "no pitch shifter %d";
+  mi355tts_shift_params p;
+  int device = 0;
+  float* win = nullptr;
+  std::shared_ptr<PitchModel> pitch;
+  std::shared_ptr<ResamplerModel> resampler;
+  ~ShiftModel() {
+    DeviceScope ds(device);
+    if (win) hipFree(win);
+  }
+};
+
 static std::vector<std::pair<std::string, int64_t>> glow_manifest(const mi355tts_glow_hparams& h) {
   std::vector<std::pair<std::string, int64_t>> m;
   auto add = [&](const std::string& n, int64_t e) { m.emplace_back(n, e); };

@@ -30,7 +30,8 @@
   X(KN_LOUD_CHUNK, "loudness_chunk_kernel") X(KN_LOUD_CARRY, "loudness_carry_kernel") X(KN_LOUD_WEIGHT, "loudness_weight_kernel") \
   X(KN_LOUD_SEGMENT, "loudness_segment_kernel") X(KN_LOUD_GATE, "loudness_gate_kernel") X(KN_LOUD_APPLY, "loudness_apply_kernel") \
   X(KN_LIM_PEAK, "limiter_peak_kernel") X(KN_LIM_REDUCE, "limiter_reduce_kernel") X(KN_LIM_HOLD, "limiter_hold_kernel") \
-  X(KN_LIM_CARRY, "limiter_carry_kernel") X(KN_LIM_APPLY, "limiter_apply_kernel") X(KN_PITCH, "pitch_kernel")
+  X(KN_LIM_CARRY, "limiter_carry_kernel") X(KN_LIM_APPLY, "limiter_apply_kernel") X(KN_PITCH, "pitch_kernel") \
+  X(KN_SHIFT_MARK, "shift_mark_kernel") X(KN_SHIFT_OLA, "shift_ola_kernel")
 // The first KN_PINNED names are always rendered by mi355tts_kernel_counts_json, zero or not: that key list and its order are
 // ABI.  A name behind them is rendered once it has launched since the last reset, so a caller that never uses the newer entry
 // points reads exactly the list it always read.
@@ -43,7 +44,7 @@ static const char* const kclass_name[KC_COUNT] = {MI355TTS_KCLASSES(MI355TTS_X_S
 static const char* const kname_name[KN_COUNT] = {MI355TTS_KNAMES(MI355TTS_X_STR)};
 #undef MI355TTS_X_ID
 #undef MI355TTS_X_STR
-static_assert(KC_COUNT == 7 && KN_COUNT == 56, "a new class or name goes at the END of its table (the JSON key order is ABI) and is counted here");
+static_assert(KC_COUNT == 7 && KN_COUNT == 58, "a new class or name goes at the END of its table (the JSON key order is ABI) and is counted here");
 
 // ------------------------------------------------------------------ what the scope works on
 struct ProfEvent {

@@ -157,6 +157,9 @@ struct WaveCall {
   // carve: the workspace stride of host-bound output rows, the takes, the staging (rows and results, then the side plane)
   size_t Nld = 0, o_y = 0, o_pcm = 0, o_side = 0, o_res = 0, side_host = 0;
   Staging st;
+  // a stage's own bytes of pinned staging behind all of that (at extra_at()), set before reserve: what else it sends or receives
+  size_t extra_host = 0;
+  size_t extra_at() const { return st.end() + side_host; }
   // reserve: what the kernels write, and at which row strides
   float *d_y = nullptr, *d_side = nullptr, *d_res = nullptr;
   short* d_pcm = nullptr;
@@ -211,7 +214,7 @@ struct WaveCall {
   }
   // the workspace `cv` ends at and the staging; queues the input's upload
   int reserve(const Carver& cv) {
-    CHECK(f.reserve(cv.pos, st.end() + side_host));
+    CHECK(f.reserve(cv.pos, st.end() + side_host + extra_host));
     char* base = f.w->arena;
     CHECK(in.upload(f, f.w->pinned));
     ld = out_dev ? (long long)out_ld : (long long)Nld;

@@ -46,6 +46,7 @@
 #include "loudness.h"
 #include "limiter.h"
 #include "pitch.h"
+#include "shift.h"
 #include "align.h"
 #include "conv_f16.h"
 #include "pair_f16.h"
@@ -435,6 +436,7 @@ extern "C" int mi355tts_mel_from_buffer(mi355tts_ctx* ctx, const float* mel, con
 #include "loudness_forward.h"
 #include "limiter_forward.h"
 #include "pitch_forward.h"
+#include "shift_forward.h"
 
 // ------------------------------------------------------------------ fused call + reservation
 // ids -> int16/f32 waveform in ONE call on ONE worker: GlowTTS and the vocoder are queued

@@ -38,6 +38,25 @@ static void pitch_launch(int nk, dim3 grid, hipStream_t s, const PitchArgs& a) {
   else hipLaunchKernelGGL(HIP_KERNEL_NAME(pitch_kernel<I16, 4>), grid, tb, 0, s, a);
 }
 
+// pitch_kernel on the rows `a` names (the input, the planes and their stride a.ld bound by the caller): ONE launch, a.ld columns
+// x B rows, `total` frames in all.  (shift_forward.h queues the same launch for the periods of its rows.)
+static void pitch_enqueue(mi355tts_ctx* ctx, Worker* w, hipStream_t s, const mi355tts_pitch_params& p, PitchArgs& a, bool in_i16, int B,
+                          long long total) {
+  a.hop = p.hop;
+  a.W = p.window;
+  a.tau_min = p.tau_min;
+  a.tau_max = p.tau_max;
+  a.interpolate = p.interpolate != 0;
+  a.sample_rate = (float)p.sample_rate;
+  a.theta = p.threshold;
+  ProfScope ps(ctx, w, KC_SMALL, 3.0 * (double)total * p.window * p.tau_max);
+  ps.kernel(KN_PITCH);
+  const dim3 grid((unsigned)a.ld, B);
+  const int nk = (p.tau_max + PT_THREADS - 1) / PT_THREADS;
+  if (in_i16) pitch_launch<true>(nk, grid, s, a);
+  else pitch_launch<false>(nk, grid, s, a);
+}
+
 extern "C" int mi355tts_pitch(mi355tts_ctx* ctx, int model, const float* in_f32, const int16_t* in_i16, const int64_t* samples, int B,
                               int64_t in_ld, float* f0_out, float* periodicity_out, float* level_db_out, float* cmnd_out, int64_t out_ld,
                               uint32_t flags) {
@@ -98,25 +117,11 @@ extern "C" int mi355tts_pitch(mi355tts_ctx* ctx, int model, const float* in_f32,
   PitchArgs a;
   std::memset(&a, 0, sizeof(a));
   in.bind(a);
-  a.hop = p.hop;
-  a.W = p.window;
-  a.tau_min = p.tau_min;
-  a.tau_max = p.tau_max;
-  a.interpolate = p.interpolate != 0;
-  a.sample_rate = (float)p.sample_rate;
-  a.theta = p.threshold;
   a.ld = (long long)ld;
   float** const dst[3] = {&a.f0, &a.per, &a.lvl};
   for (int k = 0; k < 3; ++k) *dst[k] = !planes[k] ? nullptr : out_dev ? planes[k] : (float*)(base + o_plane[k]);
   a.cmnd = !cmnd_out ? nullptr : out_dev ? cmnd_out : (float*)(base + o_cmnd);
-  {
-    ProfScope ps(ctx, w, KC_SMALL, 3.0 * (double)total * p.window * p.tau_max);
-    ps.kernel(KN_PITCH);
-    const dim3 grid((unsigned)ld, B);
-    const int nk = (p.tau_max + PT_THREADS - 1) / PT_THREADS;
-    if (in_i16) pitch_launch<true>(nk, grid, s, a);
-    else pitch_launch<false>(nk, grid, s, a);
-  }
+  pitch_enqueue(ctx, w, s, p, a, in_i16 != nullptr, B, total);
   if (out_dev) return f.finish();
   char* pin_out = w->pinned_out + in.bytes;
   size_t at = 0;

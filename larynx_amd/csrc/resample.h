@@ -48,6 +48,7 @@ struct ResampleArgs {
   long long pcm_bs, pcm_ld;
   float* peak;          // optional: max |y| of workgroup blockIdx.x at peak[b * peak_ld + blockIdx.x]
   long long peak_ld;
+  const int* out_n;     // optional [B]: the row's outputs end at out_n[b] <= N_out (shift.h delivers the first n); null: all N_out
 };
 
 __device__ __forceinline__ long long resample_out_len(int N, int up, int down) { return ((long long)N * up + down - 1) / down; }
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a)
   __shared__ float pm[RS_TILE / 64];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int N = a.samples[b];
-  const long long nout = resample_out_len(N, a.up, a.down);
+  const long long nout = a.out_n ? a.out_n[b] : resample_out_len(N, a.up, a.down);
   const long long n0 = (long long)blockIdx.x * RS_TILE, n = n0 + tid;
   float* const y = a.y ? a.y + (long long)b * a.y_bs : nullptr;
   short* const pcm = a.pcm ? a.pcm + (long long)b * a.pcm_bs : nullptr;
@@ -144,12 +145,13 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a)
 }
 
 // y [B][y_bs] float rows of N_out samples -> out [B][o_bs] int16 rows: N_out scaled samples | zeros up to o_ld
+// (out_n, optional [B]: the rows' lengths themselves, in place of N_out of samples / up / down)
 __global__ __launch_bounds__(256) void resample_pcm_kernel(const float* y, long long y_bs, const int* samples, int up, int down,
                                                             const float* peak, long long peak_ld, short* out, long long o_bs,
-                                                            long long o_ld) {
+                                                            long long o_ld, const int* out_n) {
   __shared__ float pm[4];
   const int b = blockIdx.y;
-  const long long nout = resample_out_len(samples[b], up, down);
+  const long long nout = out_n ? out_n[b] : resample_out_len(samples[b], up, down);
   const long long np = (nout + RS_TILE - 1) / RS_TILE;
   float m = 0.f;
   for (long long i = threadIdx.x; i < np; i += blockDim.x) m = fmaxf(m, peak[(long long)b * peak_ld + i]);

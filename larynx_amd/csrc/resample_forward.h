@@ -36,6 +36,81 @@ extern "C" int64_t mi355tts_resample_length(mi355tts_ctx* ctx, int model, int64_
   return resample_len(pin.get(), samples);
 }
 
+// ------------------------------------------------------------------ the launches, on an open wave call
+// (shift_forward.h queues the same two behind its own kernels)
+// What a stage's last float rows go through on their way out, the plan of mi355tts_resample: the f32 rows and / or the saturating
+// int16 rows straight from the stage's kernel, or — normalised int16 — its float rows (in the workspace when nobody receives
+// them) and the max |y| of every RS_TILE outputs, which resample_pcm_kernel turns into the int16 rows in a second launch.
+struct WaveOutPlan {
+  bool f32, i16, normalize, y_ws;
+  long long tiles;
+};
+struct WaveOutTakes {
+  size_t o_y, o_peak;
+};
+static WaveOutPlan wave_out_plan(const float* out_f32, const int16_t* out_i16, bool normalize, long long Omax) {
+  return {out_f32 != nullptr, out_i16 != nullptr, normalize, !out_f32 && normalize, (Omax + RS_TILE - 1) / RS_TILE};
+}
+static WaveOutTakes wave_out_carve(Carver& cv, const WaveCall& wc, const WaveOutPlan& p) {
+  WaveOutTakes t;
+  t.o_y = cv.take(p.y_ws ? sizeof(float) * (size_t)wc.in.B * wc.Nld : 0);
+  t.o_peak = cv.take(p.normalize ? sizeof(float) * (size_t)wc.in.B * p.tiles : 0);
+  return t;
+}
+// y / pcm / peak of a stage's kernel arguments (ResampleArgs, ShiftOlaArgs), behind wc.reserve
+template <class Args>
+static void wave_out_bind(Args& a, const WaveCall& wc, const WaveOutPlan& p, const WaveOutTakes& t) {
+  char* base = wc.f.w->arena;
+  if (p.f32) {
+    a.y = wc.d_y;
+    a.y_bs = a.y_ld = wc.ld;
+  } else if (p.y_ws) {  // float rows nobody receives: in the workspace, for the second launch only
+    a.y = (float*)(base + t.o_y);
+    a.y_bs = a.y_ld = (long long)wc.Nld;
+  }
+  if (p.i16 && !p.normalize) {  // (else the second launch leaves the int16 rows there)
+    a.pcm = wc.d_pcm;
+    a.pcm_bs = a.pcm_ld = wc.ld;
+  }
+  if (p.normalize) {
+    a.peak = (float*)(base + t.o_peak);
+    a.peak_ld = p.tiles;
+  }
+}
+// resample_kernel on the rows `a` names (input and outputs bound by the caller): Omax outputs in the longest row, `total` in all
+static void resample_launch(mi355tts_ctx* ctx, Worker* w, hipStream_t s, const ResamplerModel* rm, ResampleArgs& a, bool in_i16, long long Omax,
+                            long long total, int B) {
+  a.table = rm->table;
+  a.up = rm->p.up;
+  a.down = rm->p.down;
+  a.half_len = rm->p.half_len;
+  a.Tp = rm->Tp;
+  // the widest row the launch writes, zero tails included (never narrower than the longest row's outputs)
+  const long long span = std::max(std::max(a.y ? a.y_ld : 0LL, a.pcm ? a.pcm_ld : 0LL), Omax);
+  const dim3 grid((unsigned)((span + RS_TILE - 1) / RS_TILE), B);
+  // the last lane's inputs end (up - 1 + 255 down) div up + Tp behind the tile's first staged one, at most
+  const long long need = ((long long)a.up - 1 + (long long)(RS_TILE - 1) * a.down) / a.up + a.Tp;
+  const bool staged = need <= RS_SPAN;
+  a.stage_rounds = staged ? (int)((need + RS_TILE - 1) / RS_TILE) : 0;
+  ProfScope ps(ctx, w, KC_SMALL, 2.0 * (double)total * rm->T);  // no counted kernel name: filed under "-" 
+  if (in_i16 && staged) hipLaunchKernelGGL((resample_kernel<true, true>), grid, dim3(RS_TILE), 0, s, a);
+  else if (in_i16) hipLaunchKernelGGL((resample_kernel<true, false>), grid, dim3(RS_TILE), 0, s, a);
+  else if (staged) hipLaunchKernelGGL((resample_kernel<false, true>), grid, dim3(RS_TILE), 0, s, a);
+  else hipLaunchKernelGGL((resample_kernel<false, false>), grid, dim3(RS_TILE), 0, s, a);
+}
+// resample_pcm_kernel: the float rows and tile peaks `a` names -> the call's normalised int16 rows
+template <class Args>
+static void resample_pcm_launch(mi355tts_ctx* ctx, Worker* w, hipStream_t s, const Args& a, const WaveCall& wc, int B, int up, int down,
+                                const int* out_n) {
+  const unsigned gx = (unsigned)std::min<long long>(std::max<long long>((wc.ld + 1023) / 1024, 1), 256);
+  ProfScope ps(ctx, w, KC_SMALL, 0);
+  hipLaunchKernelGGL(resample_pcm_kernel, dim3(gx, B), dim3(256), 0, s, a.y, a.y_bs, a.samples, up, down, a.peak, a.peak_ld, wc.d_pcm, wc.ld,
+                     wc.ld, out_n);
+}
+static void resample_pcm_launch(mi355tts_ctx* ctx, Worker* w, hipStream_t s, const ResampleArgs& a, const WaveCall& wc, int B) {
+  resample_pcm_launch(ctx, w, s, a, wc, B, a.up, a.down, a.out_n);
+}
+
 extern "C" int mi355tts_resample(mi355tts_ctx* ctx, int model, const float* in_f32, const int16_t* in_i16, const int64_t* samples, int B,
                                  int64_t in_ld, float* out_f32, int16_t* out_i16, int64_t out_ld, int pcm_mode, int64_t* samples_out,
                                  uint32_t flags) {
@@ -63,55 +138,15 @@ extern "C" int mi355tts_resample(mi355tts_ctx* ctx, int model, const float* in_f
   if (Omax == 0) return wc.empty({});
   CHECK(wc.f.pinned_ints(B));
   // host rows travel through the workspace at strides in.Nld (in) and wc.Nld (out); device rows are read and written in place
-  const long long tiles = (Omax + RS_TILE - 1) / RS_TILE;
-  const bool y_ws = !out_f32 && normalize;  // float rows nobody receives: in the workspace, for the second launch only
+  const WaveOutPlan plan = wave_out_plan(out_f32, out_i16, normalize, Omax);
   Carver cv = wc.carve();
-  const size_t o_y = cv.take(y_ws ? sizeof(float) * (size_t)B * wc.Nld : 0);
-  const size_t o_peak = cv.take(normalize ? sizeof(float) * (size_t)B * tiles : 0);
+  const WaveOutTakes tk = wave_out_carve(cv, wc, plan);
   CHECK(wc.reserve(cv));
-  char* base = w->arena;
   ResampleArgs a;
   std::memset(&a, 0, sizeof(a));
   wc.in.bind(a);
-  a.table = rm->table;
-  a.up = rm->p.up;
-  a.down = rm->p.down;
-  a.half_len = rm->p.half_len;
-  a.Tp = rm->Tp;
-  if (out_f32) {
-    a.y = wc.d_y;
-    a.y_bs = a.y_ld = wc.ld;
-  } else if (y_ws) {
-    a.y = (float*)(base + o_y);
-    a.y_bs = a.y_ld = (long long)wc.Nld;
-  }
-  if (out_i16 && !normalize) {  // (else the second launch leaves the int16 rows there)
-    a.pcm = wc.d_pcm;
-    a.pcm_bs = a.pcm_ld = wc.ld;
-  }
-  if (normalize) {
-    a.peak = (float*)(base + o_peak);
-    a.peak_ld = tiles;
-  }
-  {
-    // the widest row the launch writes, zero tails included (never narrower than the longest row's outputs)
-    const long long span = std::max(std::max(a.y ? a.y_ld : 0LL, a.pcm ? a.pcm_ld : 0LL), Omax);
-    const dim3 grid((unsigned)((span + RS_TILE - 1) / RS_TILE), B);
-    // the last lane's inputs end (up - 1 + 255 down) div up + Tp behind the tile's first staged one, at most
-    const long long need = ((long long)a.up - 1 + (long long)(RS_TILE - 1) * a.down) / a.up + a.Tp;
-    const bool staged = need <= RS_SPAN;
-    a.stage_rounds = staged ? (int)((need + RS_TILE - 1) / RS_TILE) : 0;
-    ProfScope ps(ctx, w, KC_SMALL, 2.0 * (double)total * rm->T);  // no counted kernel name: filed under "-" 
-    if (in_i16 && staged) hipLaunchKernelGGL((resample_kernel<true, true>), grid, dim3(RS_TILE), 0, s, a);
-    else if (in_i16) hipLaunchKernelGGL((resample_kernel<true, false>), grid, dim3(RS_TILE), 0, s, a);
-    else if (staged) hipLaunchKernelGGL((resample_kernel<false, true>), grid, dim3(RS_TILE), 0, s, a);
-    else hipLaunchKernelGGL((resample_kernel<false, false>), grid, dim3(RS_TILE), 0, s, a);
-  }
-  if (normalize) {
-    const unsigned gx = (unsigned)std::min<long long>(std::max<long long>((wc.ld + 1023) / 1024, 1), 256);
-    ProfScope ps(ctx, w, KC_SMALL, 0);
-    hipLaunchKernelGGL(resample_pcm_kernel, dim3(gx, B), dim3(256), 0, s, a.y, a.y_bs, a.samples, a.up, a.down, a.peak, a.peak_ld, wc.d_pcm,
-                       wc.ld, wc.ld);
-  }
+  wave_out_bind(a, wc, plan, tk);
+  resample_launch(ctx, w, s, rm, a, in_i16 != nullptr, Omax, total, B);
+  if (normalize) resample_pcm_launch(ctx, w, s, a, wc, B);
   return wc.end();
 }

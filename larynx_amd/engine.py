@@ -839,6 +839,63 @@ class Engine:
                                     f0_ptr, periodicity_ptr, level_ptr, cmnd_ptr, int(out_ld), int(flags)),
         )
 
+    # ---- pitch shift and tempo ------------------------------------------------------
+    def load_shift(self, up: int, down: int, window: np.ndarray, pitch: int, resampler: int = 0) -> int:
+        """`mi355tts_load_shift`: a period-synchronous overlap-add stretch by `up / down` with the window `window` [N]
+        (`larynx_amd.shift.ola_window`), the periods from the pitch model `pitch`; `resampler`, a resampler model by `down / up`,
+        plays the stretch back at the input's duration (the PITCH mode), 0 delivers the stretch (the TEMPO mode).  The model keeps
+        both alive; `unload` frees it."""
+        window = np.ascontiguousarray(window, np.float32).reshape(-1)
+        p = ffi.ShiftParamsC(int(up), int(down), len(window), int(pitch), int(resampler))
+        model = C.c_int()
+        ffi.check(self.lib, self.lib.mi355tts_load_shift(self._ctx, C.byref(p), window.ctypes.data, C.byref(model)))
+        return int(model.value)
+
+    def shift_length(self, model: int, samples: int) -> int:
+        """`mi355tts_shift_length`: a row's delivered length: `samples` (PITCH mode) or ceil(samples * up / down) (TEMPO)."""
+        return int(ffi.check(self.lib, self.lib.mi355tts_shift_length(self._ctx, int(model), int(samples))))
+
+    def shift(self, model: int, audio: np.ndarray, samples=None, want_float: bool = True, want_int16: bool = False,
+              normalize: bool = False, positions_in=None, want_positions: typing.Optional[int] = None,
+              want_f0: typing.Optional[int] = None) -> dict:
+        """`audio`: float32 or int16 (read as s / 32768), [N] or [B, N], row b valid for `samples[b]` entries (default: all) ->
+        {"f32", "i16": [B, longest delivered row] or None; "samples": int64 [B]; "positions": int32 [B, want_positions] or None;
+        "f0": float32 [B, want_f0] or None}, rows zero-filled behind their entries; a 1-D input gives 1-D rows.
+        `want_positions` / `want_f0`: the width of that output (at least the longest row's frames / pitch frames), None: not
+        wanted.  `positions_in` (int32 [B, K] or [K]) replaces the tracked positions."""
+        audio, flat, B, N, n, f_in, i_in = self._audio_in(audio, samples)
+        if not (want_float or want_int16):
+            raise ValueError("nothing asked for: want_float and / or want_int16")
+        ld = max([self.shift_length(model, int(v)) for v in n if 0 <= v <= N] or [0])
+        f32 = np.empty((B, ld), np.float32) if want_float else None
+        i16 = np.empty((B, ld), np.int16) if want_int16 else None
+        pos = np.empty((B, int(want_positions)), np.int32) if want_positions is not None else None
+        f0 = np.empty((B, int(want_f0)), np.float32) if want_f0 is not None else None
+        pos_ld = int(want_positions or 0)
+        if positions_in is not None:
+            positions_in = np.ascontiguousarray(np.asarray(positions_in, np.int32).reshape(B, -1))
+            pos_ld = positions_in.shape[1]
+        out = self.shift_raw(model, f_in, i_in, n, N, ffi.ptr(f32), ffi.ptr(i16), ld, ffi.PCM_NORMALIZE if normalize else ffi.PCM_SATURATE,
+                             positions_in_ptr=ffi.ptr(positions_in), positions_ptr=ffi.ptr(pos), pos_ld=pos_ld, f0_ptr=ffi.ptr(f0),
+                             f0_ld=int(want_f0 or 0))
+        f32, i16, pos, f0 = self._rows_out(flat, f32, i16, pos, f0)
+        return {"f32": f32, "i16": i16, "samples": out, "positions": pos, "f0": f0}
+
+    def shift_raw(self, model: int, f32_ptr, i16_ptr, samples, in_ld: int, out_f32_ptr, out_i16_ptr, out_ld: int, pcm_mode: int = 0,
+                  positions_in_ptr=None, positions_ptr=None, pos_ld: int = 0, f0_ptr=None, f0_ld: int = 0, flags: int = 0) -> np.ndarray:
+        """Pointer-level entry: exactly one input pointer [B][in_ld] and optionally positions_in int32 [B][pos_ld] (device memory
+        with ffi.IN_DEVICE); at least one output pointer [B][out_ld], optionally positions int32 [B][pos_ld] and f0 [B][f0_ld]
+        (device memory with ffi.OUT_DEVICE); returns the rows' delivered lengths, int64 [B]."""
+        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        out = np.zeros(len(n), np.int64)
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_shift(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+                                    positions_in_ptr, out_f32_ptr, out_i16_ptr, int(out_ld), int(pcm_mode), positions_ptr, int(pos_ld),
+                                    f0_ptr, int(f0_ld), out.ctypes.data_as(C.POINTER(C.c_int64)), int(flags)),
+        )
+        return out
+
     # ---- single operators ------------------------------------------------------
     def conv1d(self, x, w, bias=None, dilation=1, in_slope=1.0, out_act=0, lens=None) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

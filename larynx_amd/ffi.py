@@ -110,6 +110,13 @@ class PitchParamsC(C.Structure):
                 ("threshold", C.c_float), ("interpolate", C.c_int32)]
 
 
+class ShiftParamsC(C.Structure):
+    """`mi355tts_shift_params`: the ratio up / down, the overlap-add window's length, and the ids of the pitch model and of the
+    resampler (0: the TEMPO mode)."""
+
+    _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("window", C.c_int32), ("pitch", C.c_int32), ("resampler", C.c_int32)]
+
+
 PCM_SATURATE = 0  # MI355TTS_PCM_*: clamp(rint(y * 32768)) / the reference's audio_float_to_int16 on the resampled row
 PCM_NORMALIZE = 1
 
@@ -213,6 +220,13 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
     "mi355tts_load_pitch": (C.c_int, [_VP, C.POINTER(PitchParamsC), C.POINTER(C.c_int)]),
     "mi355tts_pitch_frames": (C.c_int64, [_VP, C.c_int, C.c_int64]),
     "mi355tts_pitch": (C.c_int, [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, C.c_uint32]),
+    "mi355tts_load_shift": (C.c_int, [_VP, C.POINTER(ShiftParamsC), _VP, C.POINTER(C.c_int)]),
+    "mi355tts_shift_length": (C.c_int64, [_VP, C.c_int, C.c_int64]),
+    "mi355tts_shift": (
+        C.c_int,
+        [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int64), C.c_int, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_int64, _VP, C.c_int64,
+         C.POINTER(C.c_int64), C.c_uint32],
+    ),
     "mi355tts_synthesize": (
         C.c_int,
         [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,

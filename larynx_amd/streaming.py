@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import sentence_task, sentence_task_at_rate, sentence_task_leveled, sentence_task_limited
+from . import _shifter_for, sentence_task, sentence_task_at_rate, sentence_task_leveled, sentence_task_limited, sentence_task_shifted
 
 Sentence = typing.Union[typing.Tuple[str, typing.Sequence[int]], typing.Tuple[str, typing.Sequence[int], int, int]]
 
@@ -35,7 +35,7 @@ def stream_raw_pcm(sentences: typing.Iterable[Sentence], tts_model, vocoder_mode
                    tts_settings=None, vocoder_settings=None, max_thread_workers: int = 2,
                    raw_stream_queue_size: int = 5, max_pending: typing.Optional[int] = None,
                    sample_rate: typing.Optional[int] = None, loudness: typing.Optional[float] = None,
-                   limiter: typing.Optional[bool] = None) -> RawStreamStats:
+                   limiter: typing.Optional[bool] = None, pitch_shift: typing.Optional[float] = None) -> RawStreamStats:
     """Synthesise `sentences` — `(text, phoneme_ids)` or `(text, phoneme_ids,
     pause_before_ms, pause_after_ms)` — and write 16-bit mono PCM to `sink` in
     sentence order.  `max_thread_workers=2` is the reference's raw-stream default
@@ -45,10 +45,13 @@ def stream_raw_pcm(sentences: typing.Iterable[Sentence], tts_model, vocoder_mode
     A failed sentence re-raises here after the writer has been shut down.  `sample_rate`: write the PCM at that rate instead
     of the voice's own (`sentence_task_at_rate`); `None` or the voice's rate changes nothing.  `loudness`: write every sentence
     at that many LUFS instead of with its peak on 32767 (`sentence_task_leveled`); `None` changes nothing.  `limiter=True`
-    (only together with `loudness`): through the true-peak limiter (`sentence_task_limited`); `None` or `False` changes nothing."""
+    (only together with `loudness`): through the true-peak limiter (`sentence_task_limited`); `None` or `False` changes nothing.
+    `pitch_shift`: the voice's pitch moved by that many semitones, in [-12, 12], before the other switches act
+    (`sentence_task_shifted`); `None` or 0 changes nothing."""
     if limiter and loudness is None:
         raise ValueError("limiter: valid only together with loudness")
     audio_settings = getattr(tts_model, "audio_settings", None)
+    shifting = _shifter_for(vocoder_model, audio_settings, pitch_shift) is not None  # (made here, once, before the pool needs it)
     max_pending = max_pending or (max_thread_workers + raw_stream_queue_size)
     voice_rate = audio_settings.sample_rate if audio_settings is not None else 22050
     at_rate = sample_rate is not None and int(sample_rate) != int(voice_rate)
@@ -95,7 +98,11 @@ def stream_raw_pcm(sentences: typing.Iterable[Sentence], tts_model, vocoder_mode
             for item in sentences:
                 text, ids = item[0], np.asarray(item[1], np.int64)
                 before, after = (int(item[2]), int(item[3])) if len(item) >= 4 else (0, 0)
-                if loudness is not None:
+                if shifting:
+                    pending.append(pool.submit(sentence_task_shifted, text, ids, audio_settings, tts_model, tts_settings, vocoder_model,
+                                               vocoder_settings, before, after, int(sample_rate) if at_rate else None,
+                                               None if loudness is None else float(loudness), bool(limiter), float(pitch_shift)))
+                elif loudness is not None:
                     pending.append(pool.submit(sentence_task_limited if limiter else sentence_task_leveled, text, ids, audio_settings, tts_model, tts_settings, vocoder_model,
                                                vocoder_settings, before, after, int(sample_rate) if at_rate else None, float(loudness)))
                 elif at_rate:
