@@ -716,6 +716,23 @@ int mi355tts_op_gauss_noise(mi355tts_ctx* ctx, uint64_t seed, int B, int C, int 
 int mi355tts_op_maximum_path(mi355tts_ctx* ctx, const float* value, int B, int P_ld, int F_ld, const int32_t* id_lens,
                              const int32_t* frames, int32_t* durations_out, int dur_ld, float* score_out);
 
+/* Test seam: the activation planes of ONE vocoder call.  Runs the generator once on `mel` in the precision the model is switched
+ * to and with the context's options, without the denoiser, and writes the float rows wav_f32[B][wav_ld] as
+ * mi355tts_hifigan_infer does (same launches, same bits).  A copy of every plane the schedule wrote to memory is taken in
+ * stream order right behind the launch that wrote it and kept by the context until the next such call.  `json` receives the
+ * taps in launch order: [{"name", "channels", "ld", "len": [valid columns per row], "f16": 0 | 1, "kernel": the name the launch
+ * was counted under}, ...].  Names: "mel" (the generator's input as the first conv reads it: the packed plane in fp16), "pre",
+ * "up{i}", "rb{i}.{j}.{d}.t" (conv1's stored output, where the schedule materialises it), "rb{i}.{j}.{d}", "stage{i}" (where a
+ * kernel writes the MRF average; "stage{i}.sum{m}": the two partial sums of the one-launch narrow stages), "wav".  Refused with a
+ * reason when the copies would exceed 256 MB, and for the forked schedule ("mrf_group" = 0 outside fp16), whose side streams a
+ * copy cannot be ordered behind.  The other entry points pay host-side tests of a null pointer for this (one where a launch is
+ * named, one where a plane would be copied) and nothing on the device. */
+int mi355tts_hifigan_infer_taps(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, float* wav_f32, int64_t wav_ld, char* json,
+                                int cap);
+/* Tap `index` of the last mi355tts_hifigan_infer_taps as float32 dst[B][channels][ld] (host, `cap` floats); fp16 octet planes are
+ * un-permuted and widened, which is exact. */
+int mi355tts_voc_tap_copy(mi355tts_ctx* ctx, int index, float* dst, int64_t cap);
+
 /* Kernel micro-benchmark: `iters` back-to-back launches of the conv kernel on
  * device-resident random data of the given geometry (tile_shape -1 = the
  * launcher's own choice, 0/1/2 = pinned), timed with HIP events on the launch

@@ -29,6 +29,7 @@ struct VocCall {
   // The model's precision for this call: read ONCE, by the call's first hifigan_precheck (mi355tts_model_set_precision may run on
   // another thread meanwhile); the bias pass, the generator and the denoiser's bias slot all follow this value.
   int precision = -1;
+  VocTaps* taps = nullptr;  // mi355tts_hifigan_infer_taps: keep a copy of every plane the schedule writes (voc_tap); else null
 };
 
 static int ensure_denoiser_bias(mi355tts_ctx* ctx, HifiModel* hm, int vocoder, int precision);
@@ -137,12 +138,13 @@ struct VocPass {
   long long peak_ld = 0;
   const float* bias_spec = nullptr;
   Staging staged;  // host outputs: rows of the samples alone / of samples + pauses (nothing for MI355TTS_OUT_DEVICE)
+  VocTaps* taps;   // the test seam (voc_tap): null in every call but mi355tts_hifigan_infer_taps'
 
   VocPass(CallFrame& f, HifiModel* hm_, const mi355tts_mel* mel_, const VocCall& call)
       : frame(f), ctx(f.ctx), w(f.w), hm(hm_), mel(mel_), s(f.s), B(mel_->B), F(mel_->max_frames), hop(hm_->hop), d_frames(mel_->frames_dev),
         voc_host_len(mel_->B == 1 ? mel_->frames[0] : -1), opt(f.w->opt), prec(call.precision), f16(call.precision == MI355TTS_PRECISION_F16),
         denoiser_strength(call.denoiser_strength), denoise(call.denoiser_strength > 0.f && mel_->max_frames > 0),
-        out_dev((call.flags & MI355TTS_OUT_DEVICE) != 0) {}
+        out_dev((call.flags & MI355TTS_OUT_DEVICE) != 0), taps(call.taps) {}
 
   RowLen rows(int mul) const { return row_len(B, voc_host_len, d_frames, mul); }
   template <class P>
@@ -181,6 +183,39 @@ struct VocPass {
     return 0;
   }
 };
+
+// ------------------------------------------------------------------ the test seam: the planes of one call
+// A copy of the plane the last launch on `p.s` wrote — `ch` channels at row stride `ld`, rows of frames x `mul` columns, fp16 octet
+// planes or f32 rows — queued on the same stream right behind that launch: the schedule reuses its planes, so a copy at the end
+// of the call would be too late.  Filed under the kernel name that launch was counted under.  Callers test `p.taps` first: with
+// ProfScope::kernel's test of `kn_out`, all a plain call pays for the seam.
+static std::string tap_name(const char* fmt, ...) {
+  char tmp[64];
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(tmp, sizeof(tmp), fmt, ap);
+  va_end(ap);
+  return tmp;
+}
+static int voc_tap(VocPass& p, const std::string& name, const void* x, bool f16, int ch, int ld, int mul) {
+  VocTaps& T = *p.taps;
+  VocTap t;
+  t.name = name;
+  t.kn = T.last_kn;
+  t.f16 = f16;
+  t.B = p.B;
+  t.ch = ch;
+  t.ld = ld;
+  for (int b = 0; b < p.B; ++b) t.len.push_back((int)std::min<long long>((long long)p.mel->frames[b] * mul, ld));
+  t.bytes = f16 ? (size_t)p.B * (size_t)((ch + 7) / 8) * (size_t)ld * 16 : sizeof(float) * (size_t)p.B * (size_t)ch * (size_t)ld;
+  if (T.bytes + t.bytes > VocTaps::MAX_BYTES)
+    return fail(MI355TTS_ERR_NOMEM, "the planes of this call exceed %zu MB of tap copies (at '%s'): fewer frames or rows", VocTaps::MAX_BYTES >> 20, name.c_str());
+  HIPCHECK(hipMalloc(&t.dev, t.bytes));
+  T.bytes += t.bytes;
+  T.taps.push_back(t);  // (owned from here on: ~VocTaps frees it)
+  HIPCHECK(hipMemcpyAsync(t.dev, x, t.bytes, hipMemcpyDeviceToDevice, p.s));
+  return 0;
+}
 
 // ------------------------------------------------------------------ stage bookkeeping, shared by both precisions
 // Stage i as its upsampler writes it and its ResBlocks keep it: `cout` channels, `Lout` columns at row stride `ldo`, `bs` plane
@@ -305,6 +340,8 @@ static int f32_schedule(const VocPass& p, F32Schedule& sc) {
   const bool busy = opt.adaptive_schedule && p.ctx->active_calls.load(std::memory_order_relaxed) > 1;
   sc.grouped = sc.split_out && h.num_kernels == 3 && opt.mrf_group && !busy;
   sc.concurrent = sc.split_out && !opt.mrf_group && !busy;
+  if (p.taps && sc.concurrent)
+    return fail(MI355TTS_ERR_INVALID, "taps: the forked schedule (\"mrf_group\" = 0) runs its chains on side streams a copy cannot be ordered behind");
   if (sc.concurrent && !w->aux[0]) {
     for (int i = 0; i < 2; ++i) {
       HIPCHECK(hipStreamCreateWithFlags(&w->aux[i], hipStreamNonBlocking));
@@ -327,7 +364,10 @@ static int f32_pre(VocPass& p, StageCursor<float>& c) {  // conv_pre (models.py:
   c.Lin = p.F;
   c.ldin = Fp;
   ConvArgs a = base_args(p.mel->voc, (long long)p.mel->M * p.mel->ld, p.mel->ld, p.d_frames, 1, c.cur[0], (long long)C0 * Fp, Fp, p.d_frames, 1, 1, 3);
-  return launch_conv(p.ctx, p.w, p.hm->pre, a, EPI_LINEAR, p.B, p.F, KC_VOC_IO, nullptr, 1024, p.voc_host_len);
+  if (p.taps) CHECK(voc_tap(p, "mel", p.mel->voc, false, p.mel->M, p.mel->ld, 1));
+  CHECK(launch_conv(p.ctx, p.w, p.hm->pre, a, EPI_LINEAR, p.B, p.F, KC_VOC_IO, nullptr, 1024, p.voc_host_len));
+  if (p.taps) CHECK(voc_tap(p, "pre", c.cur[0], false, C0, Fp, 1));
+  return 0;
 }
 
 static int f32_upsample(VocPass& p, const StageCursor<float>& c, const VocStage& st) {  // x = ups[i](leaky_relu(x, 0.1))  (models.py:189-190)
@@ -336,7 +376,9 @@ static int f32_upsample(VocPass& p, const StageCursor<float>& c, const VocStage&
   a.in_slope = 0.1f;
   a.up = st.u;
   a.up_pad = (st.ku - st.u) / 2;
-  return launch_conv(p.ctx, p.w, p.hm->ups[st.i], a, EPI_UPSAMPLE, p.B, c.Lin + st.ku / st.u - 1, KC_UPSAMPLE, nullptr, 1024, p.voc_host_len, p.prec);
+  CHECK(launch_conv(p.ctx, p.w, p.hm->ups[st.i], a, EPI_UPSAMPLE, p.B, c.Lin + st.ku / st.u - 1, KC_UPSAMPLE, nullptr, 1024, p.voc_host_len, p.prec));
+  if (p.taps) CHECK(voc_tap(p, tap_name("up%d", st.i), p.buf[1], false, st.cout, st.ldo, st.mul));
+  return 0;
 }
 
 // One dilation step of one MRF chain, planned: the fused pair if its geometry is covered, else conv1 (+ conv2)
@@ -423,6 +465,14 @@ struct F32Chains {
     }
     return 0;
   }
+  // the planes step d of chain j left: conv1's output where the step materialised it, and the step's own output (the serial
+  // form's last steps accumulate into the stage's average instead: tapped as "stage{i}" once the last chain has added its share)
+  int tap_step(int j, int d, const VocStep& sp) const {
+    const bool fold = d == nd - 1 && !sc.split_out;
+    if (!sp.pair.ok && !sp.c2.empty) CHECK(voc_tap(p, tap_name("rb%d.%d.%d.t", st.i, j, d), pl[j].t, false, st.cout, st.ldo, st.mul));
+    if (!fold) return voc_tap(p, tap_name("rb%d.%d.%d", st.i, j, d), sp.dst, false, st.cout, st.ldo, st.mul);
+    return j == nk - 1 ? voc_tap(p, tap_name("stage%d", st.i), sp.dst, false, st.cout, st.ldo, st.mul) : 0;
+  }
   int run_step_alone(int j, const VocStep& sp) const {
     if (sp.pair.ok) return run_pair(p.ctx, p.w, sp.pair, stream[j]);
     CHECK(run_plan(p.ctx, p.w, sp.c1, stream[j]));
@@ -444,6 +494,8 @@ struct F32Chains {
       if (rc < 0) return rc;
       if (rc == 1)
         for (int j = 0; j < nk; ++j) CHECK(run_step_alone(j, sp[j]));
+      if (p.taps)
+        for (int j = 0; j < nk; ++j) CHECK(tap_step(j, d, sp[j]));
       for (int j = 0; j < nk; ++j) rin[j] = sp[j].dst;
     }
     return 0;
@@ -455,6 +507,7 @@ struct F32Chains {
         VocStep sp;
         CHECK(plan_step(j, d, sp));
         CHECK(run_step_alone(j, sp));
+        if (p.taps) CHECK(tap_step(j, d, sp));
         rin[j] = sp.dst;
       }
     return 0;
@@ -470,6 +523,8 @@ static int f32_resblocks(VocPass& p, const F32Schedule& sc, StageCursor<float>& 
     // the previous stage's chain outputs are dead once the upsampler has read them.
     float* sums[2] = {p.buf[0], p.buf[2]};
     CHECK(run_mrf_small(p.ctx, p.w, hm->mrf[st.i], hm->arena, p.buf[1], sums[0], sums[1], st.bs, st.ldo, p.d_frames, st.mul, p.B, st.Lout, p.voc_host_len, p.s));
+    if (p.taps)  // the launch keeps its chains in LDS: only the two sums reach memory
+      for (int m = 0; m < 2; ++m) CHECK(voc_tap(p, tap_name("stage%d.sum%d", st.i, m), sums[m], false, st.cout, st.ldo, st.mul));
     c.advance(st, sums, 2, (float)nk, false);
     return 0;
   }
@@ -513,17 +568,22 @@ static int f32_post(VocPass& p, const StageCursor<float>& c) {  // x = tanh(conv
     c.inputs(a);
     a.in_slope = 0.01f;
     a.out_act = ACT_TANH;
-    return launch_conv(p.ctx, p.w, p.hm->post, a, EPI_LINEAR, p.B, c.Lin, KC_VOC_IO, nullptr, 1024, p.voc_host_len);
+    CHECK(launch_conv(p.ctx, p.w, p.hm->post, a, EPI_LINEAR, p.B, c.Lin, KC_VOC_IO, nullptr, 1024, p.voc_host_len));
+    if (p.taps) CHECK(voc_tap(p, "wav", p.wav, false, 1, (int)p.Nld, c.mul));
+    return 0;
   }
   PostArgs a = post_args<PostArgs>(p, c, (long long)c.ch * c.ldin);
   if (p.peak) {
     a.peak = p.peak;
     a.peak_ld = p.peak_ld;
   }
-  ProfScope ps(p.ctx, p.w, KC_VOC_IO, 2.0 * (double)c.ch * 7 * (double)c.Lin * p.B);
-  ps.kernel(KN_POST_CONV);
-  const dim3 pg((c.Lin + POST_TW - 1) / POST_TW, p.B);
-  switch_const<1, 2, 3>(c.ncur, [&](auto n) { hipLaunchKernelGGL(HIP_KERNEL_NAME(post_conv_kernel<7, decltype(n)::value>), pg, dim3(256), 0, p.s, a); });
+  {
+    ProfScope ps(p.ctx, p.w, KC_VOC_IO, 2.0 * (double)c.ch * 7 * (double)c.Lin * p.B);
+    ps.kernel(KN_POST_CONV);
+    const dim3 pg((c.Lin + POST_TW - 1) / POST_TW, p.B);
+    switch_const<1, 2, 3>(c.ncur, [&](auto n) { hipLaunchKernelGGL(HIP_KERNEL_NAME(post_conv_kernel<7, decltype(n)::value>), pg, dim3(256), 0, p.s, a); });
+  }
+  if (p.taps) CHECK(voc_tap(p, "wav", p.wav, false, 1, (int)p.Nld, c.mul));
   return 0;
 }
 
@@ -581,12 +641,15 @@ static int f16_pre(VocPass& p, StageCursor<uint4>& c) {
     hipLaunchKernelGGL(pack_octets_kernel, dim3((F + 255) / 256, moct, B), dim3(256), 0, p.s, mel->voc, (long long)mel->M * mel->ld, mel->ld, M, p.d_frames, 1,
                        melh, (long long)moct * F, F);
   }
+  if (p.taps) CHECK(voc_tap(p, "mel", melh, true, 8 * moct, F, 1));
   c.cur[0] = p.plane<uint4>(0);
   c.ch = C0;
   c.Lin = c.ldin = F;
   const HConvArgs a = f16_conv_args(p, {melh, 8 * moct, F, 1}, {c.cur[0], C0, F, 1}, 1, 3);  // conv_pre (models.py:187)
   const HPlan pl = plan_f16(p.hm->h_pre, a, EPI_LINEAR, B, F, 2.0 * C0 * M * 7 * (double)F * B);
-  return run_plan_f16(p.ctx, p.w, pl, KC_VOC_IO, p.s);
+  CHECK(run_plan_f16(p.ctx, p.w, pl, KC_VOC_IO, p.s));
+  if (p.taps) CHECK(voc_tap(p, "pre", c.cur[0], true, C0, F, 1));
+  return 0;
 }
 
 // x = ups[i](leaky_relu(x, 0.1))  (models.py:189-190); the MRF average of the previous stage is taken on load
@@ -598,7 +661,9 @@ static int f16_upsample(VocPass& p, const StageCursor<uint4>& c, const VocStage&
   a.up_pad = st.u / 2;
   HPlan pl = plan_f16(p.hm->h_ups[st.i], a, EPI_UPSAMPLE, p.B, c.Lin + 1, 2.0 * c.ch * st.cout * (2.0 * st.u) * (double)c.Lin * p.B);
   pl.mrf = c.ncur > 1;
-  return run_plan_f16(p.ctx, p.w, pl, KC_UPSAMPLE, p.s);
+  CHECK(run_plan_f16(p.ctx, p.w, pl, KC_UPSAMPLE, p.s));
+  if (p.taps) CHECK(voc_tap(p, tap_name("up%d", st.i), p.plane<uint4>(1), true, st.cout, st.ldo, st.mul));
+  return 0;
 }
 
 // the fused form of a ResBlock1 step (pair_f16.h)
@@ -668,6 +733,8 @@ static int f16_resblocks(VocPass& p, StageCursor<uint4>& c, const VocStage& st) 
     if (use_pair) {
       fused = run_pair_group_f16(p.ctx, p.w, pp, nk, ch, B, Lout, p.s);
       if (fused < 0) return fused;
+      if (fused == 0 && p.taps)
+        for (int j = 0; j < nk; ++j) CHECK(voc_tap(p, tap_name("rb%d.%d.%d", st.i, j, d), dst[j], true, ch, st.ldo, st.mul));
     }
     for (int pass = 0; fused != 0 && pass < (h.resblock_type == 1 ? 2 : 1); ++pass) {
       const HPlan* plans = pass ? c2 : c1;
@@ -675,6 +742,11 @@ static int f16_resblocks(VocPass& p, StageCursor<uint4>& c, const VocStage& st) 
       if (rc < 0) return rc;
       if (rc == 1)
         for (int j = 0; j < nk; ++j) CHECK(run_plan_f16(p.ctx, p.w, plans[j], KC_RESBLOCK, p.s));
+      if (p.taps) {  // pass 0 of a ResBlock1 step leaves conv1's stored output, every other pass the step's own
+        const bool t_plane = h.resblock_type == 1 && pass == 0;
+        for (int j = 0; j < nk; ++j)
+          CHECK(voc_tap(p, tap_name(t_plane ? "rb%d.%d.%d.t" : "rb%d.%d.%d", st.i, j, d), t_plane ? pl[j].t : dst[j], true, ch, st.ldo, st.mul));
+      }
     }
     for (int j = 0; j < nk; ++j) rin[j] = dst[j];
   }
@@ -688,10 +760,13 @@ static int f16_post(VocPass& p, const StageCursor<uint4>& c) {  // x = tanh(conv
   HPostArgs a = post_args<HPostArgs>(p, c, (long long)(c.ch / 8) * c.ldin);
   a.peak = p.peak;
   a.peak_ld = p.peak_ld;
-  ProfScope ps(p.ctx, p.w, KC_VOC_IO, 2.0 * (double)c.ch * 7 * (double)c.Lin * p.B, p.s);
-  ps.kernel(KN_POST_F16);
-  const dim3 pg((c.Lin + HPOST_TW - 1) / HPOST_TW, p.B);
-  switch_const<1, 2, 3>(c.ncur, [&](auto n) { hipLaunchKernelGGL(HIP_KERNEL_NAME(post_f16_kernel<7, decltype(n)::value>), pg, dim3(256), 0, p.s, a); });
+  {
+    ProfScope ps(p.ctx, p.w, KC_VOC_IO, 2.0 * (double)c.ch * 7 * (double)c.Lin * p.B, p.s);
+    ps.kernel(KN_POST_F16);
+    const dim3 pg((c.Lin + HPOST_TW - 1) / HPOST_TW, p.B);
+    switch_const<1, 2, 3>(c.ncur, [&](auto n) { hipLaunchKernelGGL(HIP_KERNEL_NAME(post_f16_kernel<7, decltype(n)::value>), pg, dim3(256), 0, p.s, a); });
+  }
+  if (p.taps) CHECK(voc_tap(p, "wav", p.wav, false, 1, (int)p.Nld, c.mul));
   return 0;
 }
 
@@ -801,6 +876,11 @@ static int hifigan_run(CallFrame& f, HifiModel* hm, const mi355tts_mel* mel, con
   f.w->flop_scale = (double)sum / ((double)mel->B * mel->max_frames);
   VocPass p(f, hm, mel, call);
   CHECK(p.bind(call, rows));
+  struct KnOut {  // a tapped call learns its launches' names through the worker; the worker forgets the address on every way out
+    Worker* w;
+    ~KnOut() { w->kn_out = nullptr; }
+  } kn_out{f.w};
+  if (p.taps) f.w->kn_out = &p.taps->last_kn;
   CHECK(p.f16 ? hifigan_body_f16(p) : hifigan_body_f32(p));
   return voc_deliver(p, call, rows, voc_denoise(p));
 }
@@ -880,6 +960,66 @@ extern "C" int mi355tts_hifigan_infer_padded(mi355tts_ctx* ctx, int vocoder, con
   c.pad_before = pad_before;
   c.pad_after = pad_after;
   return hifigan_call(ctx, vocoder, mel, c);
+}
+
+// ------------------------------------------------------------------ the test seam's two entry points
+// [{"name": "up0", "channels": 64, "ld": 140, "len": [140, 18], "f16": 1, "kernel": "conv_f16_kernel"}, ...] in launch order
+static std::string voc_taps_json(const VocTaps& T) {
+  std::string s = "[";
+  for (size_t i = 0; i < T.taps.size(); ++i) {
+    const VocTap& t = T.taps[i];
+    char tmp[256];
+    std::snprintf(tmp, sizeof(tmp), "%s{\"name\": \"%s\", \"channels\": %d, \"ld\": %d, \"len\": [", i ? ", " : "", t.name.c_str(), t.ch, t.ld);
+    s += tmp;
+    for (size_t b = 0; b < t.len.size(); ++b) s += (b ? ", " : "") + std::to_string(t.len[b]);
+    std::snprintf(tmp, sizeof(tmp), "], \"f16\": %d, \"kernel\": \"%s\"}", t.f16 ? 1 : 0, t.kn >= 0 && t.kn < KN_COUNT ? kname_name[t.kn] : "-");
+    s += tmp;
+  }
+  return s + "]";
+}
+
+extern "C" int mi355tts_hifigan_infer_taps(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, float* wav_f32, int64_t wav_ld,
+                                           char* json, int cap) {
+  if (!ctx || !mel || !wav_f32 || !json) return fail(MI355TTS_ERR_INVALID, "null argument");
+  auto taps = std::make_shared<VocTaps>();
+  VocCall c;
+  c.wav_f32 = wav_f32;
+  c.wav_ld = wav_ld;
+  c.taps = taps.get();
+  CHECK(hifigan_call(ctx, vocoder, mel, c));  // (ends with the stream synchronised: the copies are complete)
+  const std::string s = voc_taps_json(*taps);
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->voc_taps = taps;
+  }
+  return copy_json(s, json, cap, "tap list buffer too small");
+}
+
+extern "C" int mi355tts_voc_tap_copy(mi355tts_ctx* ctx, int index, float* dst, int64_t cap) {
+  if (!ctx || !dst) return fail(MI355TTS_ERR_INVALID, "null argument");
+  std::shared_ptr<VocTaps> taps;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    taps = ctx->voc_taps;
+  }
+  if (!taps || index < 0 || (size_t)index >= taps->taps.size()) return fail(MI355TTS_ERR_INVALID, "no tap %d (mi355tts_hifigan_infer_taps first)", index);
+  const VocTap& t = taps->taps[(size_t)index];
+  const size_t n = (size_t)t.B * t.ch * t.ld;
+  if ((size_t)std::max<int64_t>(cap, 0) < n) return fail(MI355TTS_ERR_TOO_SMALL, "tap %d holds %zu floats", index, n);
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (!t.f16) {
+    HIPCHECK(hipMemcpy(dst, t.dev, t.bytes, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // octet planes [B][ch / 8][ld][8] halves -> [B][ch][ld] floats (every half is a float: exact)
+  std::vector<_Float16> h(t.bytes / sizeof(_Float16));
+  HIPCHECK(hipMemcpy(h.data(), t.dev, t.bytes, hipMemcpyDeviceToHost));
+  const size_t noct = (size_t)t.ch / 8, ld = (size_t)t.ld;
+  for (size_t b = 0; b < (size_t)t.B; ++b)
+    for (size_t o = 0; o < noct; ++o)
+      for (size_t col = 0; col < ld; ++col)
+        for (size_t e = 0; e < 8; ++e) dst[(b * t.ch + 8 * o + e) * ld + col] = (float)h[((b * noct + o) * ld + col) * 8 + e];
+  return 0;
 }
 
 extern "C" int mi355tts_hifigan_infer(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, float denoiser_strength,

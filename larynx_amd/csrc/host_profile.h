@@ -74,6 +74,8 @@ struct ProfLane {
   // this worker's launches are neither timed nor counted per kernel name (the dispatch self-check's own launches are not a
   // caller's: a worker-local switch, so concurrent calls on the context keep their samples and counts)
   bool quiet = false;
+  // where a tapped vocoder call (mi355tts_hifigan_infer_taps) learns the name its last launch was counted under; null otherwise
+  int* kn_out = nullptr;
 };
 
 // ------------------------------------------------------------------ the scope
@@ -111,6 +113,7 @@ struct ProfScope {
     ev.kn = k;
     ev.sub = sub;
     if (!w->quiet) sums->kn[k].fetch_add(1, std::memory_order_relaxed);
+    if (w->kn_out) *w->kn_out = k;
   }
   ~ProfScope() {
     if (!on) return;

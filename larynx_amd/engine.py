@@ -547,6 +547,22 @@ class Engine:
         )
         return f32, i16
 
+    def hifigan_infer_taps(self, vocoder: int, mel: MelBatch):
+        """Test seam (`mi355tts_hifigan_infer_taps` + `mi355tts_voc_tap_copy`): one vocoder call without the denoiser ->
+        (wav_f32 [B, N], taps).  `taps` lists, in launch order, every activation plane the schedule wrote to memory: dicts with
+        "name", "channels", "ld", "len" (valid columns per row), "f16", "kernel" (the name the launch was counted under) and
+        "x", the plane as float32 [B, channels, ld] (fp16 planes widened: exact)."""
+        n = mel.max_frames * self.hop(vocoder)
+        f32 = np.empty((mel.batch, n), np.float32)
+        buf = C.create_string_buffer(1 << 16)
+        ffi.check(self.lib, self.lib.mi355tts_hifigan_infer_taps(self._ctx, vocoder, mel.handle, ffi.ptr(f32), n, buf, 1 << 16))
+        taps = json.loads(buf.value.decode("ascii"))
+        for i, t in enumerate(taps):
+            x = np.empty((mel.batch, t["channels"], t["ld"]), np.float32)
+            ffi.check(self.lib, self.lib.mi355tts_voc_tap_copy(self._ctx, i, ffi.ptr(x), x.size))
+            t["x"] = x
+        return f32, taps
+
     # ---- Griffin-Lim -----------------------------------------------------------
     def load_griffin_lim(self, mel_basis: np.ndarray, mel_scaling: float = 1000.0, iterations: int = 60) -> int:
         """`mi355tts_load_griffin_lim`: the weight-free vocoder (`larynx/griffin_lim.py:22-38`); `mel_basis` is

@@ -256,6 +256,8 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
         C.c_int,
         [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP],
     ),
+    "mi355tts_hifigan_infer_taps": (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_int64, C.c_char_p, C.c_int]),
+    "mi355tts_voc_tap_copy": (C.c_int, [_VP, C.c_int, _VP, C.c_int64]),
     "mi355tts_bench_conv1d": (C.c_int, [_VP] + [C.c_int] * 8 + [C.POINTER(C.c_float)]),
     "mi355tts_set_profiling": (C.c_int, [_VP, C.c_int]),
     "mi355tts_set_option": (C.c_int, [_VP, C.c_char_p, C.c_int]),

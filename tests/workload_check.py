@@ -628,7 +628,9 @@ def vocoder_reach(hp, denoise=False):
 def blind_tiles(hp, precision="f32"):
     """What check_hop_periodic cannot see: a seam that recurs at the same phase of every period shows the same error at t and
     t + hop.  That is every tile of vocoder_tiles(hp, precision) whose width in samples (width * rest, rest = samples per column of
-    its stage) divides hop -> [(label, stage, width)].  ("bf16" = both bf16 modes.)"""
+    its stage) divides hop -> [(label, stage, width)].  ("bf16" = both bf16 modes.)  The list is a fact about the periodic check;
+    its fp16 / bf16 last-stage entries (HPOST_TW / POST_TW and the last stage's conv tiles) are bounded by check_layers, which
+    compares every launch with float64 from its own input plane."""
     hop = hp.hop
     out = []
     for label, stage, width, _ in vocoder_tiles(hp, precision):
@@ -859,3 +861,208 @@ def check_waves_end_to_end(eng, g, v, gsd, vsd, ghp, vhp, rows, length_scale, se
             compare_wave(wb[b], ib[b], refs[i], F * hop, bounds, f"{label} utterance {i} (F={F}) row {b} of B={len(grp)}")
         mel.free()
     return refs
+
+
+# ---- layer by layer: every launch of one vocoder call against float64, from that launch's own input plane --------------------
+# The planes of one call (`Engine.hifigan_infer_taps`) against tests/voc_layers_np.py: the reference of a layer is computed from
+# the planes its launch READ, so no error is carried from layer to layer and every bound is derived (voc_layers_np's `delta`, half
+# an fp16 ulp) or calibrated on the reference alone (the flip share).  This bounds what check_hop_periodic cannot see: the seams
+# blind_tiles lists for the fp16 / bf16 last stages, and an error all tiles share.
+LAYER_PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2, "f16": 3}  # ffi.PRECISION_*
+F16_KERNELS = ("conv_f16_kernel", "conv_f16_group_kernel", "pair_f16_group_kernel")
+# Kernels that keep a whole stage's chains on chip and write no plane of a single conv or pair: check_layers' callers switch them
+# off ("mrf_small" = 0) and they stay outside the layer check (their own tests: the tile-edge sweep and the periodic check).
+LAYER_BLIND_KERNELS = ("mrf_small_kernel", "mrf8_kernel")
+
+
+def layer_mode(kernel, precision):
+    """The operand format of the launch counted under `kernel` in a model switched to `precision`."""
+    if kernel in F16_KERNELS:
+        return "f16"
+    if kernel.startswith("conv_bf16") or kernel.startswith("pair_bf16"):
+        assert precision in ("bf16x3", "bf16"), (kernel, precision)
+        return precision
+    return "f32"
+
+
+def layer_frames(hp, tile_class):
+    """The smallest frame count at which every tile of vocoder_tiles(hp, tile_class) has at least two interior seams inside a row
+    (three tiles: that covers the three HPOST_TW / POST_TW tiles too) and a ragged last tile — wherever a frame count can make it
+    ragged at all (a tile whose width divides the stage's columns per frame is full at every F)."""
+    tiles = vocoder_tiles(hp, tile_class)
+    axis = vocoder_axis(hp)
+    assert tiles, (hp, tile_class)
+    F = 1
+    while not all(-(-axis(F, stage) // width) >= 3 and (axis(F, stage) % width or axis(1, stage) % width == 0) for _, stage, width, _ in tiles):
+        F += 1
+        assert F < 4096, (hp, tile_class)
+    return F
+
+
+def layer_mel(num_mels, rows):
+    """[B, num_mels, max(rows)]: 2 * randn seeded by the row's length, 0 behind a row's frames."""
+    mel = np.zeros((len(rows), num_mels, max(rows)), F32)
+    for b, F in enumerate(rows):
+        mel[b, :, :F] = (2 * np.random.default_rng(3000 + F + 7 * b).standard_normal((num_mels, F))).astype(F32)
+    return mel
+
+
+def check_layers(engine, hp, precision, frames, options=None, *, v, sd, label="", only=None):
+    """One tapped vocoder call of model `v` (weights `sd`) in `precision` on rows of `frames` frames, under `options`
+    ({name: (value, default)}).  Asserts: the tapped call returns the plain call's rows bit for bit and launches the same kernels;
+    the `wav` tap is those rows; and for every tap after `mel`, on the valid columns of every row, |plane - ref64| within the
+    derived bound (voc_layers_np.bound_fp16 / bound_f32), ref64 built from the taps the launch read.  For fp16 planes also: the
+    elements that differ from fp16(ref64) at all are at most 4 times as many as in the layers' float32 restatements in another tap
+    order (floor: 8 per plane), counted over all the planes a kernel wrote in this call: one restatement of one plane is one draw
+    of the share it estimates, and in a fused pair one flipped element of the intermediate moves K * C sums at once, so single
+    planes scatter widely; the pool is fixed here, before any kernel's count is looked at.  A schedule whose stages write no plane
+    of a single conv or pair (LAYER_BLIND_KERNELS, the serial form's "stage{i}") is refused: switch that fusion off.
+    `only`: the tap names to compare (a long call whose point is the seams of a few launches); every tap still exists and the
+    rows are still compared.  Returns (rows of {"name", "kernel", "mode", "ratio", "flips", "restated", "n"}, kernel names)."""
+    from larynx_amd import weights
+    from tests import voc_layers_np as V
+
+    rows = [int(f) for f in np.atleast_1d(frames)]
+    options = dict(options or {})
+    nk, nd = len(hp.resblock_kernel_sizes), len(hp.resblock_dilation_sizes[0])
+    rb1 = hp.resblock == "1"
+    W_ = lambda name: weights.resolve_tensor(sd, name + ".weight")
+    B_ = lambda name: weights.resolve_tensor(sd, name + ".bias")
+    mel = layer_mel(hp.num_mels, rows)
+    mb = engine.mel_from_numpy(mel, np.array(rows, np.int32))
+    for k, (val, _) in options.items():
+        engine.set_option(k, val)
+    try:
+        engine.set_precision(v, LAYER_PRECISIONS[precision])
+        engine.profile_reset()
+        plain, _ = engine.hifigan_infer(v, mb, want_int16=False)
+        c_plain = engine.kernel_counts()
+        engine.profile_reset()
+        wav, taps = engine.hifigan_infer_taps(v, mb)
+        c_taps = engine.kernel_counts()
+    finally:
+        engine.set_precision(v, LAYER_PRECISIONS["f32"])
+        for k, (_, default) in options.items():
+            engine.set_option(k, default)
+        mb.free()
+    tag = f"{label} {precision} rows {rows}"
+    # (every layer is walked before anything fails: a kernel that leaves a column unwritten shows here first, and the walk below
+    # names the layer)
+    failures = [] if np.array_equal(wav, plain) else [(tag, "the tapped call's rows differ from the plain call's")]
+    assert c_taps == c_plain, (tag, "the seam changed what runs", c_taps, c_plain)
+    by = {t["name"]: t for t in taps}
+    assert len(by) == len(taps) and taps[0]["name"] == "mel" and taps[-1]["name"] == "wav", (tag, [t["name"] for t in taps])
+    for b, F in enumerate(rows):
+        n = F * hp.hop
+        if not (by["wav"]["len"][b] == n and np.array_equal(by["wav"]["x"][b, 0, :n], wav[b, :n])):
+            failures.append((tag, "the wav tap is not the returned row", b))
+    kernels = {t["kernel"] for t in taps}
+    if precision == "f32":
+        assert not failures, failures
+        return [], kernels
+
+    def plane(name, b):
+        t = by[name]
+        return t["x"][b, :, : t["len"][b]]
+
+    report = []
+    cur = ["pre"]  # the planes the next upsampler (or conv_post) averages on load
+    outs = {}
+    for t in taps:
+        name, kernel = t["name"], t["kernel"]
+        mode = layer_mode(kernel, precision)
+        if name == "mel":
+            for b, F in enumerate(rows):  # the generator's input as the first conv reads it: exact
+                want = V.fp16(mel[b, :, :F]) if t["f16"] else mel[b, :, :F]
+                assert np.array_equal(plane("mel", b)[: hp.num_mels], want) and not np.any(plane("mel", b)[hp.num_mels :]), (tag, "mel", b)
+            continue
+        assert kernel not in LAYER_BLIND_KERNELS and not name.startswith("stage"), (tag, name, kernel, "no plane of a single conv or pair: switch this fusion off")
+        if only is not None and name not in only:
+            if name.startswith("rb") and name.count(".") == 2 and int(name.split(".")[2]) == nd - 1:
+                outs.setdefault(int(name[2:].split(".")[0]), []).append(name)
+                if len(outs[int(name[2:].split(".")[0])]) == nk:
+                    cur = outs[int(name[2:].split(".")[0])]
+            continue
+        stage = (lambda planes, slope: V.stage_f16(planes, slope)) if mode == "f16" else (lambda planes, slope: V.stage_f32(planes, slope))
+        worst, flips, restated, count = (0.0, None), 0, 0, 0
+        for b in range(len(rows)):
+            got = plane(name, b).astype(np.float64)
+            ref32 = None
+            if name == "pre":
+                x = stage([plane("mel", b)[: hp.num_mels] if not t["f16"] else plane("mel", b)], 1.0)
+                w = W_("conv_pre")
+                if t["f16"]:  # the packed plane's zero channels past num_mels meet zero weights
+                    w = np.concatenate([w, np.zeros((w.shape[0], x.shape[0] - w.shape[1], w.shape[2]), F32)], axis=1)
+                args = (mode, w, B_("conv_pre"), x)
+                ref, delta = V.conv_layer(*args)
+                if mode == "f16":
+                    ref32 = V.conv_layer32(*args)
+            elif name.startswith("up"):
+                i = int(name[2:])
+                x = stage([plane(c, b) for c in cur], V.SLOPE)
+                u = hp.upsample_rates[i]
+                ref, delta = V.upsample_layer(mode, W_(f"ups.{i}"), B_(f"ups.{i}"), x, u)
+                if mode == "f16":
+                    ref32 = V.conv_layer32(mode, W_(f"ups.{i}"), B_(f"ups.{i}"), x, transposed_u=u)
+            elif name.startswith("rb"):
+                parts = name[2:].split(".")
+                i, j, d = int(parts[0]), int(parts[1]), int(parts[2])
+                is_t = len(parts) == 4
+                K, dil = hp.resblock_kernel_sizes[j], hp.resblock_dilation_sizes[j][d]
+                rin = f"rb{i}.{j}.{d - 1}" if d else f"up{i}"
+                xin = plane(rin, b)
+                pre_ = f"resblocks.{i * nk + j}"
+                if not rb1:
+                    args = (mode, W_(f"{pre_}.convs.{d}"), B_(f"{pre_}.convs.{d}"), stage([xin], V.SLOPE), dil, xin)
+                    ref, delta = V.conv_layer(*args)
+                    ref32 = V.conv_layer32(*args) if mode == "f16" else None
+                elif is_t:  # conv1's stored output: activated before its rounding in fp16, raw in the f32 planes
+                    args = (mode, W_(f"{pre_}.convs1.{d}"), B_(f"{pre_}.convs1.{d}"), stage([xin], V.SLOPE), dil, None, V.SLOPE if mode == "f16" else 1.0)
+                    ref, delta = V.conv_layer(*args)
+                    ref32 = V.conv_layer32(*args) if mode == "f16" else None
+                elif name + ".t" in by:
+                    tin = stage([plane(name + ".t", b)], 1.0 if by[name + ".t"]["f16"] else V.SLOPE)
+                    args = (mode, W_(f"{pre_}.convs2.{d}"), B_(f"{pre_}.convs2.{d}"), tin, 1, xin)
+                    ref, delta = V.conv_layer(*args)
+                    ref32 = V.conv_layer32(*args) if mode == "f16" else None
+                else:
+                    args = (mode, W_(f"{pre_}.convs1.{d}"), B_(f"{pre_}.convs1.{d}"), W_(f"{pre_}.convs2.{d}"), B_(f"{pre_}.convs2.{d}"),
+                            stage([xin], V.SLOPE), xin, dil)
+                    ref, delta = V.pair_layer(*args)
+                    ref32 = V.pair_layer32(*args) if mode == "f16" else None
+                if d == nd - 1 and not is_t and b == 0:
+                    outs.setdefault(i, []).append(name)
+                    if len(outs[i]) == nk:
+                        cur = outs[i]
+            else:
+                assert name == "wav", (tag, name)
+                x = V.stage_f32([plane(c, b) for c in cur], V.SLOPE_POST, by_reciprocal=kernel == "post_f16_kernel")
+                ref, delta = V.post_layer(W_("conv_post"), B_("conv_post"), x)
+            assert ref.shape == got.shape, (tag, name, b, ref.shape, got.shape)
+            stored16 = bool(t["f16"])
+            bound = V.bound_fp16(ref, delta) if stored16 else V.bound_f32(ref, delta)
+            ratio = np.where(np.isfinite(got), np.abs(got - ref) / bound, np.inf)  # (an element never written is no number)
+            at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+            if float(ratio[at]) > worst[0]:
+                worst = (float(ratio[at]), (b, int(at[0]), int(at[1])))
+            if stored16:
+                r16 = V.fp16(ref)
+                flips += int(np.count_nonzero(got.astype(F32) != r16))
+                restated += int(np.count_nonzero(V.fp16(ref32) != r16))
+            count += got.size
+        report.append(dict(name=name, kernel=kernel, mode=mode, ratio=worst[0], flips=flips, restated=restated, n=count))
+        share = f" differing from fp16(ref64): {flips} ({100.0 * flips / count:.3f} %), float32 restatement {restated} ({100.0 * restated / count:.3f} %)" if t["f16"] else ""
+        print(f"{tag} {name} [{kernel}, {mode}]: worst err / bound {worst[0]:.3f} at (row, channel, column) {worst[1]} of {count}{share}")
+        if not worst[0] <= 1.0:
+            failures.append((tag, name, kernel, "outside the derived bound at (row, channel, column)", worst))
+    for kernel in sorted({r["kernel"] for r in report if r["mode"] == "f16"}):
+        mine = [r for r in report if r["kernel"] == kernel and r["mode"] == "f16"]
+        flips, restated, count = (sum(r[k] for r in mine) for k in ("flips", "restated", "n"))
+        most = max(mine, key=lambda r: r["flips"] / r["n"])
+        print(f"{tag} {kernel}: {len(mine)} planes, {flips} of {count} elements differ from fp16(ref64) ({100.0 * flips / count:.3f} %), float32 "
+              f"restatement {restated} ({100.0 * restated / count:.3f} %); the plane with the largest share: {most['name']} {most['flips']} of {most['n']}")
+        if flips > max(4 * restated, 8 * len(mine)):
+            failures.append((tag, kernel, "more elements differ from the correctly rounded result than the f32 summation order explains", flips, restated, count,
+                             "largest share: " + most["name"]))
+    assert not failures, failures
+    return report, kernels
