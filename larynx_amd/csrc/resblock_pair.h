@@ -319,28 +319,13 @@ __global__ __launch_bounds__(512, CB == 2 ? 4 : 1) void pair_group_kernel(const 
   float* const ts = xs + PairGeom<K0, CB, NB>::RED;
   const int lin = blockIdx.x;
   const int b = blockIdx.z;
-  // ragged batch: a row deals only its own tiles (tile_grid.h, row_tiles)
-  auto tiles = [&](const PairArgs& p, int gx_grid, int t2) { return gridDim.z > 1 ? row_tiles(tile_len(p.len, p.len_mul, p.len_const, b), t2) : gx_grid; };
-  constexpr int T1 = PairGeom<K0, CB, NB>::T1;
-  int tx, ty;
-  if (lin < g.off[1]) {
-    const int gx = tiles(g.p[0], g.gx[0], T1 - (K0 - 1));
-    if (lin >= gx) return;
-    xcd_tile_lin(lin, gx, 1, tx, ty);
-    pair_tile<K0, CB, NB>(g.p[0], tx, b, xs, ts);
-  } else if (lin < g.off[2]) {
-    const int l = lin - g.off[1];
-    const int gx = tiles(g.p[1], g.gx[1], T1 - (K1 - 1));
-    if (l >= gx) return;
-    xcd_tile_lin(l, gx, 1, tx, ty);
-    pair_tile<K1, CB, NB>(g.p[1], tx, b, xs, ts);
-  } else {
-    const int l = lin - g.off[2];
-    const int gx = tiles(g.p[2], g.gx[2], T1 - (K2 - 1));
-    if (l >= gx) return;
-    xcd_tile_lin(l, gx, 1, tx, ty);
-    pair_tile<K2, CB, NB>(g.p[2], tx, b, xs, ts);
-  }
+  group_member(g.off, lin, [&](auto m, int l) __attribute__((always_inline)) {
+    constexpr int K = pick3<m, K0, K1, K2>;
+    const PairArgs& p = g.p[m];
+    auto row_len = [&]() __attribute__((always_inline)) { return tile_len(p.len, p.len_mul, p.len_const, b); };
+    int tx, ty;
+    if (member_tile(l, g.gx[m], 1, PairGeom<K0, CB, NB>::T1 - (K - 1), row_len, tx, ty)) pair_tile<K, CB, NB>(p, tx, b, xs, ts);
+  });
 }
 
 }  // namespace mi355tts

@@ -1,5 +1,7 @@
-// What the tile kernels share ahead of their tile functions: the XCD-aware workgroup -> tile order, the ragged-batch rule,
-// a batch row's length and the accumulator row map of the 32x32 MFMA blocks.  Included by conv_mfma.h, and so by every tile.
+// What the tile kernels share ahead of their tile functions: the XCD-aware workgroup -> tile order, the ragged-batch rule
+// (row_tiles; row_gx and member_tile apply it to a member of a grouped launch), the member dispatch of a grouped launch
+// (group_member, pick3), a batch row's length and the accumulator row map of the 32x32 MFMA blocks.  Included by conv_mfma.h,
+// and so by every tile.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,5 +58,39 @@ __device__ __forceinline__ void xcd_tile(int gx, int gy, int& tx, int& ty, int r
 // So a row deals only ITS OWN tiles: the first gx_row * gy workgroups of the row's grid slice take them (spread
 // evenly over the XCDs by the dispatcher's round-robin), the rest exit.
 __device__ __forceinline__ int row_tiles(int n_len, int tile) { return (n_len + tile - 1) / tile; }
+
+// The ragged rule, in the one place every tile kernel takes it from.  Time tiles of this workgroup's batch row: the row's own
+// (`tile` columns each) when the launch has rows of different lengths, else the count the grid was sized with.  `row_len` is a
+// callable (forced inline, like every callback here), so a launch of one row never reads the length array.
+template <class L>
+__device__ __forceinline__ int row_gx(int gx_grid, int tile, L&& row_len) { return gridDim.z > 1 ? row_tiles(row_len(), tile) : gx_grid; }
+
+// Workgroup l of a member of a grouped launch (below; a gx x gy tile grid in a range padded to a multiple of 8): false past the
+// row's own tiles, else its tile in the XCD-aware order.  The fused pairs have time tiles only: gy = 1, ty unused.
+template <class L>
+__device__ __forceinline__ bool member_tile(int l, int gx_grid, int gy, int tile, L&& row_len, int& tx, int& ty) {
+  const int gx = row_gx(gx_grid, tile, row_len);
+  if (l >= gx * gy) return false;
+  xcd_tile_lin(l, gx, gy, tx, ty);
+  return true;
+}
+
+// Grouped launches (conv_mfma.h, conv_group_kernel): the three MRF chains' same-geometry tiles in one 1-D grid, member 0's
+// first.  What differs between the members is compile-time (taps, halo), so the member index reaches the callback as an
+// int_c: f(int_c<m>{}, l) with l the workgroup's index inside member m; pick3<m, K0, K1, K2> is then that member's value.
+// Callbacks are lambdas marked __attribute__((always_inline)): a tile body behind a real call would lose its registers.
+// In use by pair_group_kernel (resblock_pair.h), whose code it leaves byte-identical.  The other seven grouped kernels and
+// the kernels of one conv per launch keep the rule and the ladder written out: the helper form moves their code generation,
+// and their launch times left the written-out form's own spread when measured (profiles/NOTES.md, tools/isa_diff.py).
+template <int M, int V0, int V1, int V2>
+constexpr int pick3 = M == 0 ? V0 : M == 1 ? V1 : V2;
+
+// the plain longest-first order: workgroups off[m] .. off[m + 1] are member m's
+template <class F>
+__device__ __forceinline__ void group_member(const int (&off)[4], int lin, F&& f) {
+  if (lin < off[1]) f(int_c<0>{}, lin);
+  else if (lin < off[2]) f(int_c<1>{}, lin - off[1]);
+  else f(int_c<2>{}, lin - off[2]);
+}
 
 }  // namespace mi355tts

@@ -113,14 +113,14 @@ def test_constant_mel_is_hop_periodic(emu_engine, name, prec):
 
 @pytest.mark.parametrize("name", list(GEOMETRIES))
 def test_ragged_batch_is_hop_periodic_per_row(emu_engine, name):
-    """Three rows of different lengths, each its own column: every row periodic over its own interior, its tail 0 — in f32 and in
-    fp16 (the ragged grids deal a row its own tiles)."""
+    """Three rows of different lengths, each its own column: every row periodic over its own interior, its tail 0 — in f32, in
+    split bf16 and in fp16 (the ragged grids deal a row its own tiles)."""
     hp, v = _model(emu_engine, name)
     try:
-        for prec in ("f32", "f16"):
+        for prec in ("f32", "bf16x3", "f16"):
             assert emu_engine.set_precision(v, PRECISIONS[prec]) == 0
             sig = W.check_hop_periodic(emu_engine, v, hp, 0, rows=RAGGED, label=f"{name} {prec} ragged")
-            _need(sig, NEED[(name, prec)], f"{name} {prec} ragged")
+            _need(sig, NEED[(name, "bf16" if prec == "bf16x3" else prec)], f"{name} {prec} ragged")
     finally:
         emu_engine.set_precision(v, ffi.PRECISION_F32)
 
