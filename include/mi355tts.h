@@ -732,6 +732,23 @@ int mi355tts_hifigan_infer_taps(mi355tts_ctx* ctx, int vocoder, const mi355tts_m
 /* Tap `index` of the last mi355tts_hifigan_infer_taps as float32 dst[B][channels][ld] (host, `cap` floats); fp16 octet planes are
  * un-permuted and widened, which is exact. */
 int mi355tts_voc_tap_copy(mi355tts_ctx* ctx, int index, float* dst, int64_t cap);
+/* The acoustic model's twin of that seam: ONE GlowTTS call with the arguments of mi355tts_glow_infer_prosody (same launches, same
+ * bits, same mel) that keeps a copy of every f32 plane [B][channels][ld] its schedule wrote, each queued right behind the launch
+ * that wrote it — the passes rewrite their planes in place, so every launch's input is some earlier tap.  `json` as above ("f16" is
+ * always 0; "kernel" is "-" for a launch counted under no name); mi355tts_voc_tap_copy then serves this call's taps (it serves
+ * whichever call tapped last).  A launch that writes two planes leaves two taps.  Names, in launch order: "emb", "pre.{i}",
+ * "pre.proj", per encoder layer "enc{l}.qkv" (and "enc{l}.x0", the stored normalised input, from the second layer on),
+ * "enc{l}.att", "enc{l}.x1", "enc{l}.ffn", "enc{l}.t1", then "enc.out", "xm", ("dp.spk",) "dp.1", "dp.2", "logw", "z0", per flow
+ * block in reverse order "blk{b}.h" (its start conv), "blk{b}.acts{j}", "blk{b}.h{j}" / "blk{b}.skip{j}", "blk{b}.z", and "mel"
+ * (the raw mel).  The un-fused forms ("glow_fuse" = 0) file the same names where the same tensor exists and their extra
+ * intermediates as "{name}.ln" (a separate LayerNorm's output), "enc{l}.o", "logw.ln", "blk{b}.zc" (the coupling before the
+ * mix).  Integer results (frames, durations) are the mel's.  Refused with a reason when the copies would exceed 256 MB; the rows
+ * of a coalesced pass are never tapped (only the fused synthesize calls coalesce).  The other entry points pay a host-side test
+ * of a null pointer per launch for this and nothing on the device. */
+int mi355tts_glow_infer_taps(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
+                             float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
+                             const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
+                             uint32_t flags, const mi355tts_prosody* prosody, mi355tts_mel** out, char* json, int cap);
 
 /* Kernel micro-benchmark: `iters` back-to-back launches of the conv kernel on
  * device-resident random data of the given geometry (tile_shape -1 = the

@@ -8,6 +8,32 @@
 // ------------------------------------------------------------------ GlowTTS forward
 static bool glow_fuse_on(const Worker* w) { return !w->opt.env.glow_fuse_off && w->opt.glow_fuse; }
 
+// ------------------------------------------------------------------ the test seam: the planes of one call
+// (mi355tts_glow_infer_taps; the vocoder's twin, its name helper and the list's rendering are in hifigan_forward.h)
+static std::string tap_name(const char* fmt, ...);
+static std::string voc_taps_json(const VocTaps& T);
+// A copy of one f32 plane [B][ch][ld] with `len[b]` valid columns per row into the call's store (host_context.h: VocTaps), queued
+// on stream `s` behind whatever wrote the plane.  `same_launch`: the second plane of the launch that wrote the previous tap.
+static int glow_tap(VocTaps& T, hipStream_t s, const std::string& name, const float* x, int B, int ch, int ld, const int* len, bool same_launch = false) {
+  VocTap t;
+  t.name = name;
+  t.kn = same_launch && !T.taps.empty() ? T.taps.back().kn : T.last_kn;
+  T.last_kn = -1;  // (most small GlowTTS launches are counted under no name: the next tap must not inherit this one's)
+  t.B = B;
+  t.ch = ch;
+  t.ld = ld;
+  for (int b = 0; b < B; ++b) t.len.push_back(std::min(len[b], ld));
+  t.bytes = sizeof(float) * (size_t)B * (size_t)ch * (size_t)ld;
+  if (T.bytes + t.bytes > VocTaps::MAX_BYTES)
+    return fail(MI355TTS_ERR_NOMEM, "the planes of this call exceed %zu MB of tap copies (at '%s'): fewer ids, frames or rows", VocTaps::MAX_BYTES >> 20,
+                name.c_str());
+  HIPCHECK(hipMalloc(&t.dev, t.bytes));
+  T.bytes += t.bytes;
+  T.taps.push_back(t);  // (owned from here on: ~VocTaps frees it)
+  HIPCHECK(hipMemcpyAsync(t.dev, x, t.bytes, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
 // What is constant over a run of GlowTTS launches; one instance serves the encoder, one the decoder.  A launch helper then
 // takes only what differs per launch: the conv, its ConvArgs, the norm's parameters.
 struct GlowPass {
@@ -24,6 +50,16 @@ struct GlowPass {
   // the launches of its own batch-1 call.  No caller sets it (profiles/NOTES.md, open items).
   bool solo_tiles;
   int cls;  // profile class: KC_GLOW_ENC_CONV / KC_GLOW_DEC_CONV
+  // the test seam (mi355tts_glow_infer_taps): where a copy of every plane this pass writes is kept, and the rows' valid columns on
+  // the host [B]; null in every other call
+  VocTaps* taps = nullptr;
+  const int* tap_len = nullptr;
+
+  // A copy of plane `x` [B][ch][ld], queued right behind the launch that wrote it (the passes rewrite their planes in place) and
+  // filed under the kernel name that launch was counted under ("-": a launch without one).  Callers test `taps` first.
+  int tap(const std::string& name, const float* x, int ch, bool same_launch = false) const {
+    return glow_tap(*taps, s, name, x, B, ch, ld, tap_len, same_launch);
+  }
 
   RowLen rows() const { return row_len(B, host_len, d_len); }
   ProfScope small() const { return ProfScope(ctx, w, KC_SMALL, 0); }
@@ -58,12 +94,22 @@ struct GlowPass {
   // otherwise the LayerNorm launch (raw -> normed) and the conv on its output.  a.x is the raw tensor; ln.out (where the
   // normalised tensor is also stored) may be nullptr when nothing else reads it AND the fused form is taken; the fallback needs
   // a buffer: `scratch`.
-  int ln_conv(const DevConv& c, ConvArgs a, const Lin16Ln& ln, float* scratch) const {
-    if (!w->opt.env.lin16_no_ln && glow_fuse_on(w) && lin16(c, a, &ln) == 0) return 0;
+  // Taps: the conv's output under the name `fmt` gives with `idx`, the stored normalised tensor under `ln_fmt`'s — in the fallback
+  // the LayerNorm launch's output, that name + ".ln" where ln.out is null.  (The names are built only where `taps` is set.)
+  int ln_conv(const DevConv& c, ConvArgs a, const Lin16Ln& ln, float* scratch, const char* fmt, int idx = 0, const char* ln_fmt = nullptr) const {
+    if (!w->opt.env.lin16_no_ln && glow_fuse_on(w) && lin16(c, a, &ln) == 0) {
+      if (taps) {
+        CHECK(tap(tap_name(fmt, idx), a.y, c.Cout));
+        if (ln.out) CHECK(tap(tap_name(ln_fmt, idx), ln.out, c.Cin, true));
+      }
+      return 0;
+    }
     float* dst = ln.out ? ln.out : scratch;
     layernorm(a.x, ln.gamma, ln.beta, dst, c.Cin, a.x_bs, ln.relu);
+    if (taps) CHECK(tap(ln.out ? tap_name(ln_fmt, idx) : tap_name(fmt, idx) + ".ln", dst, c.Cin));
     a.x = dst;
-    return enc_conv(c, a);
+    CHECK(enc_conv(c, a));
+    return taps ? tap(tap_name(fmt, idx), a.y, c.Cout) : 0;
   }
 };
 
@@ -102,6 +148,7 @@ struct GlowCall {
     want_durations = keep || p->durations_out;
   }
   bool has_prosody() const { return id_scales || durations_in || want_durations; }
+  VocTaps* taps = nullptr;  // mi355tts_glow_infer_taps: keep a copy of every plane the schedule writes (GlowPass::tap); else null
 };
 
 static int glow_precheck(const GlowModel* gm, const GlowCall& c, int* Pmax_out) {
@@ -244,8 +291,8 @@ struct GlowRun {
   GlowEncLayout el;
   GlowEncView ev;
   mi355tts_mel* mel;
-  GlowPass pass(int n_max, int ld, const int* d_len, int host_len, int cls) const {
-    return {ctx, w, gm, gm->arena, w->stream, call.B, n_max, ld, d_len, host_len, glow_tiles, call.solo_tiles, cls};
+  GlowPass pass(int n_max, int ld, const int* d_len, int host_len, int cls, const int* tap_len = nullptr) const {
+    return {ctx, w, gm, gm->arena, w->stream, call.B, n_max, ld, d_len, host_len, glow_tiles, call.solo_tiles, cls, call.taps, tap_len};
   }
 };
 
@@ -406,15 +453,17 @@ static int glow_prenet(const GlowPass& p, const GlowEncView& v) {
   const int pad = h.prenet_kernel_size / 2;
   float* raw = v.t1;
   CHECK(p.enc_conv(gm->pre_conv[0], p.args(v.x, bsH, raw, bsH, 1, pad)));
+  if (p.taps) CHECK(p.tap("pre.0", raw, h.hidden_channels));
   for (int i = 1; i < h.prenet_layers; ++i) {
     float* out = raw == v.t1 ? v.t2 : v.t1;
-    CHECK(p.ln_conv(gm->pre_conv[i], p.args(raw, bsH, out, bsH, 1, pad), {p.A + gm->pre_g[i - 1], p.A + gm->pre_b[i - 1], 1, nullptr}, v.qkv));
+    CHECK(p.ln_conv(gm->pre_conv[i], p.args(raw, bsH, out, bsH, 1, pad), {p.A + gm->pre_g[i - 1], p.A + gm->pre_b[i - 1], 1, nullptr}, v.qkv,
+                    "pre.%d", i));
     raw = out;
   }
   ConvArgs a = p.args(raw, bsH, v.x, bsH);
   a.res = v.x;
   const int last = h.prenet_layers - 1;
-  return p.ln_conv(gm->pre_proj, a, {p.A + gm->pre_g[last], p.A + gm->pre_b[last], 1, nullptr}, v.qkv);
+  return p.ln_conv(gm->pre_proj, a, {p.A + gm->pre_g[last], p.A + gm->pre_b[last], 1, nullptr}, v.qkv, "pre.proj");
 }
 
 // Encoder layer l (Encoder.forward, attentions.py:62-74).  Its norm_layers_2 rides in the next layer's qkv conv: `prev` is the
@@ -426,24 +475,35 @@ static int glow_enc_layer(const GlowPass& p, const GlowEncView& v, int att_rows,
   const int H = h.hidden_channels, Fc = h.filter_channels, k = h.kernel_size;
   const long long bsH = (long long)H * p.ld, bsF = (long long)Fc * p.ld;
   if (prev)  // x = LayerNorm(t1) on the way in; stored too: it is the residual of this layer's conv_o and FFN
-    CHECK(p.ln_conv(L.qkv, p.args(v.t1, bsH, v.qkv, 3 * bsH), {p.A + prev->g2, p.A + prev->b2, 0, v.x}, nullptr));
-  else
+    CHECK(p.ln_conv(L.qkv, p.args(v.t1, bsH, v.qkv, 3 * bsH), {p.A + prev->g2, p.A + prev->b2, 0, v.x}, nullptr, "enc%d.qkv", l,
+                    "enc%d.x0"));
+  else {
     CHECK(p.enc_conv(L.qkv, p.args(v.x, bsH, v.qkv, 3 * bsH)));
+    if (p.taps) CHECK(p.tap(tap_name("enc%d.qkv", l), v.qkv, 3 * H));
+  }
   launch_attention(p, L, v, att_rows);
+  if (p.taps) CHECK(p.tap(tap_name("enc%d.att", l), v.t2, H));
   if (run_oproj_ln(p, L, v.t2, v.x)) {
     ConvArgs a = p.args(v.t2, bsH, v.t1, bsH);
     a.res = v.x;
     CHECK(p.conv(L.o, a));
+    if (p.taps) CHECK(p.tap(tap_name("enc%d.o", l), v.t1, H));
     p.layernorm(v.t1, p.A + L.g1, p.A + L.b1, v.x, H, bsH, 0);
   }
+  if (p.taps) CHECK(p.tap(tap_name("enc%d.x1", l), v.x, H));
   // FFN, attentions.py:375-383
   ConvArgs a = p.args(v.x, bsH, v.ffn, bsF, 1, k / 2);
   a.out_act = ACT_RELU;
   CHECK(p.enc_conv(L.ffn1, a));
+  if (p.taps) CHECK(p.tap(tap_name("enc%d.ffn", l), v.ffn, Fc));
   ConvArgs c = p.args(v.ffn, bsF, v.t1, bsH, 1, k / 2);
   c.res = v.x;
   CHECK(p.enc_conv(L.ffn2, c));
-  if (l + 1 == h.n_layers_enc) p.layernorm(v.t1, p.A + L.g2, p.A + L.b2, v.x, H, bsH, 0);
+  if (p.taps) CHECK(p.tap(tap_name("enc%d.t1", l), v.t1, H));
+  if (l + 1 == h.n_layers_enc) {
+    p.layernorm(v.t1, p.A + L.g2, p.A + L.b2, v.x, H, bsH, 0);
+    if (p.taps) CHECK(p.tap("enc.out", v.x, H));
+  }
   return 0;
 }
 
@@ -455,6 +515,7 @@ static int glow_proj_durations(const GlowPass& p, const GlowEncView& v) {
   const int H = h.hidden_channels, Fd = h.filter_channels_dp, M = h.mel_channels, k = h.kernel_size, P = p.ld, B = p.B;
   const long long bsH = (long long)H * P, bsD = (long long)Fd * P;
   CHECK(p.enc_conv(gm->proj_m, p.args(v.x, bsH, v.xm, (long long)M * P)));
+  if (p.taps) CHECK(p.tap("xm", v.xm, M));
   float* d1 = v.ffn;
   float* d2 = v.ffn + (size_t)B * Fd * P;
   float* d3 = v.ffn + (size_t)2 * B * Fd * P;
@@ -463,23 +524,31 @@ static int glow_proj_durations(const GlowPass& p, const GlowEncView& v) {
   if (gm->gin()) {
     // conv_1 over [x ; g repeated along time] (models.py:128-132) = conv_1's encoder half over x + a plane that depends only
     // on the speaker and on where the row's zero padding starts: d3 is free until conv_2's fallback may use it
-    ProfScope ps = p.small();
-    hipLaunchKernelGGL(speaker_dp_plane_kernel, dim3((P + 255) / 256, Fd, B), dim3(256), 0, p.s, v.dps, Fd, k, k / 2, p.d_len, d3, bsD, P);
+    {
+      ProfScope ps = p.small();
+      hipLaunchKernelGGL(speaker_dp_plane_kernel, dim3((P + 255) / 256, Fd, B), dim3(256), 0, p.s, v.dps, Fd, k, k / 2, p.d_len, d3, bsD, P);
+    }
     c1.res = d3;
+    if (p.taps) CHECK(p.tap("dp.spk", d3, Fd));
   }
   CHECK(p.enc_conv(gm->dp1, c1));
+  if (p.taps) CHECK(p.tap("dp.1", d1, Fd));
   // norm_1 inside conv_2 (ln_conv): d1 -> d2; d3 is the fallback's scratch
   ConvArgs c2 = p.args(d1, bsD, d2, bsD, 1, k / 2);
   c2.out_act = ACT_RELU;
-  CHECK(p.ln_conv(gm->dp2, c2, {A + gm->dg1, A + gm->db1, 0, nullptr}, d3));
+  CHECK(p.ln_conv(gm->dp2, c2, {A + gm->dg1, A + gm->db1, 0, nullptr}, d3, "dp.2"));
   if (glow_fuse_on(p.w) && Fd <= 256) {  // norm_2 and proj (1 x 1, Fd -> 1) in one launch
-    ProfScope ps = p.small();
-    hipLaunchKernelGGL(layernorm16_kernel, dim3((p.n_max + 15) / 16, B), dim3(256), 0, p.s, d2, (const float*)nullptr, A + gm->dg2,
-                       A + gm->db2, d1, Fd, bsD, P, p.d_len, 0, 0, 1e-4f, A + gm->dpp_w, A + gm->dpp_b, v.logw, (long long)P);
-    return 0;
+    {
+      ProfScope ps = p.small();
+      hipLaunchKernelGGL(layernorm16_kernel, dim3((p.n_max + 15) / 16, B), dim3(256), 0, p.s, d2, (const float*)nullptr, A + gm->dg2,
+                         A + gm->db2, d1, Fd, bsD, P, p.d_len, 0, 0, 1e-4f, A + gm->dpp_w, A + gm->dpp_b, v.logw, (long long)P);
+    }
+    return p.taps ? p.tap("logw", v.logw, 1) : 0;
   }
   p.layernorm(d2, A + gm->dg2, A + gm->db2, d1, Fd, bsD, 0);
-  return p.conv(gm->dpp, p.args(d1, bsD, v.logw, P));
+  if (p.taps) CHECK(p.tap("logw.ln", d1, Fd));
+  CHECK(p.conv(gm->dpp, p.args(d1, bsD, v.logw, P)));
+  return p.taps ? p.tap("logw", v.logw, 1) : 0;
 }
 
 static int glow_encoder(GlowRun& r) {
@@ -491,12 +560,13 @@ static int glow_encoder(GlowRun& r) {
   r.w->flop_scale = Pmax > 0 ? (double)sum / ((double)B * Pmax) : 1.0;  // ragged batch: count the rows' real ids
   CHECK(glow_enc_upload(r));
   const GlowEncView& v = r.ev;
-  const GlowPass p = r.pass(Pmax, P, v.len, B == 1 ? call.id_lens[0] : -1, KC_GLOW_ENC_CONV);
+  const GlowPass p = r.pass(Pmax, P, v.len, B == 1 ? call.id_lens[0] : -1, KC_GLOW_ENC_CONV, call.id_lens);
   {
     ProfScope ps = p.small();
     hipLaunchKernelGGL(embed_kernel, dim3((Pmax + 63) / 64, 8, B), dim3(256), 0, p.s, v.ids, call.ids_ld, v.len, p.A + r.gm->emb,
                        h.num_symbols, H, std::sqrt((float)H), v.x, (long long)H * P, P);
   }
+  if (p.taps) CHECK(p.tap("emb", v.x, H));
   if (h.prenet) CHECK(glow_prenet(p, v));
   for (int l = 0; l < h.n_layers_enc; ++l) CHECK(glow_enc_layer(p, v, r.el.att_rows, l));
   return glow_proj_durations(p, v);
@@ -605,10 +675,10 @@ static int glow_wn_gate(const GlowPass& p, const GlowDecView& dv, const float* s
   const int g16 = p.gate16(Bk.in[j], a);
   if (g16 < 0) return g16;
   if (g16 == 1) CHECK(p.conv(Bk.in[j], a, EPI_GATE));
-  return 0;
+  return p.taps ? p.tap(tap_name("blk%d.acts%d", blk, j), dv.acts, H) : 0;
 }
 // layer j's res_skip: h += its first half (not for the last layer, which is all skip), skip (+)= the rest
-static int glow_wn_res_skip(const GlowPass& p, const GlowDecView& dv, const GlowBlock& Bk, int j) {
+static int glow_wn_res_skip(const GlowPass& p, const GlowDecView& dv, const GlowBlock& Bk, int j, int blk = -1) {
   const int H = p.gm->hp.hidden_channels;
   const bool last = j == p.gm->hp.n_block_layers - 1;
   const long long bsD = (long long)H * p.ld;
@@ -617,6 +687,10 @@ static int glow_wn_res_skip(const GlowPass& p, const GlowDecView& dv, const Glow
   if (!last) r.res = dv.h;  // x = x + res_skip[:H]
   r.y2 = dv.skip; r.y2_bs = bsD; r.y2_ld = p.ld; r.accum2 = j > 0;
   if (p.lin16(Bk.rs[j], r) != 0) CHECK(p.conv(Bk.rs[j], r));
+  if (p.taps) {  // one launch, two planes (the last layer: the skip sum only)
+    if (!last) CHECK(p.tap(tap_name("blk%d.h%d", blk, j), dv.h, H));
+    CHECK(p.tap(tap_name("blk%d.skip%d", blk, j), dv.skip, H, !last));
+  }
   return 0;
 }
 
@@ -633,20 +707,31 @@ static int glow_flow_block(const GlowPass& p, const GlowDecView& dv, const float
   const int H = h.hidden_channels, C = h.mel_channels * h.n_sqz, half = C / 2, F2 = p.ld, n = h.n_block_layers;
   const long long bsZ = (long long)C * F2, bsD = (long long)H * F2;
   float* const hcur = dv.h;  // the WaveNet's hidden state
-  if (!*start_done) CHECK(p.conv(Bk.start, p.args(dv.z, bsZ, hcur, bsD)));  // h = start(x0)
+  if (!*start_done) {
+    CHECK(p.conv(Bk.start, p.args(dv.z, bsZ, hcur, bsD)));  // h = start(x0)
+    if (p.taps) CHECK(p.tap(tap_name("blk%d.h", blk), hcur, H));
+  }
   *start_done = false;
   int dil = 1;
   // the fp16 mode: layers 0 .. n - 1 up to the last gated tile in ONE launch (wn_f16.h); the loop then runs the last layer's tail
   const bool wn16 = glow_f16 && run_wn_f16(p, dv, Bk) == 0;
+  if (wn16 && p.taps) {  // the launch keeps the layers between in LDS: the last layer's gated activations and the skip sum before it
+    CHECK(p.tap(tap_name("blk%d.acts%d", blk, n - 1), dv.acts, H));
+    if (n > 1) CHECK(p.tap(tap_name("blk%d.skip%d", blk, n - 2), dv.skip, H, true));
+  }
   for (int j = wn16 ? n - 1 : 0; j < n; ++j) {
     const bool last = j == n - 1;
     if (!wn16) CHECK(glow_wn_gate(p, dv, spk_cond, blk, j, dil));
     if (last) {
       const GlowBlock* next = blk > 0 ? &p.gm->blocks[blk - 1] : nullptr;
       *start_done = run_glow_tail(p, dv, Bk, next) == 0;
+      if (*start_done && p.taps) {
+        CHECK(p.tap(tap_name("blk%d.z", blk), dv.z, C));
+        if (next) CHECK(p.tap(tap_name("blk%d.h", blk - 1), dv.h, H, true));
+      }
       if (*start_done) return 0;
     }
-    CHECK(glow_wn_res_skip(p, dv, Bk, j));
+    CHECK(glow_wn_res_skip(p, dv, Bk, j, blk));
     dil *= h.dilation_rate;
   }
   // m, logs = end(wn_out);  z1 = (x1 - m) * exp(-logs)
@@ -659,11 +744,14 @@ static int glow_flow_block(const GlowPass& p, const GlowDecView& dv, const float
     a.mix_x0 = dv.z; a.mix_w = p.A + Bk.winv; a.mix_bias = p.A + Bk.an_bias; a.mix_scale = p.A + Bk.an_scale;
   }
   CHECK(p.conv(Bk.end, a, EPI_COUPLING));
-  if (fuse_mix) return 0;
-  ProfScope ps = p.small();
-  hipLaunchKernelGGL(invconv_actnorm_kernel, dim3((p.n_max + 255) / 256, std::min(C / h.n_split, 16), p.B), dim3(256), 0, p.s, dv.z, bsZ, F2,
-                     p.d_len, 1, C, h.n_split, p.A + Bk.winv, p.A + Bk.an_bias, p.A + Bk.an_scale);
-  return 0;
+  if (fuse_mix) return p.taps ? p.tap(tap_name("blk%d.z", blk), dv.z, C) : 0;
+  if (p.taps) CHECK(p.tap(tap_name("blk%d.zc", blk), dv.z, C));
+  {
+    ProfScope ps = p.small();
+    hipLaunchKernelGGL(invconv_actnorm_kernel, dim3((p.n_max + 255) / 256, std::min(C / h.n_split, 16), p.B), dim3(256), 0, p.s, dv.z, bsZ, F2,
+                       p.d_len, 1, C, h.n_split, p.A + Bk.winv, p.A + Bk.an_bias, p.A + Bk.an_scale);
+  }
+  return p.taps ? p.tap(tap_name("blk%d.z", blk), dv.z, C) : 0;
 }
 
 static int glow_decoder(GlowRun& r) {
@@ -695,16 +783,20 @@ static int glow_decoder(GlowRun& r) {
   int* d_f2 = v.len;
   for (int b = 0; b < B; ++b) w->pinned[b] = mel->frames[b] / nsq;
   HIPCHECK(hipMemcpyAsync(d_f2, w->pinned, sizeof(int) * B, hipMemcpyHostToDevice, s));
-  const GlowPass p = r.pass(F2max, F2, d_f2, B == 1 ? mel->frames[0] / nsq : -1, KC_GLOW_DEC_CONV);
+  // (w->pinned holds the rows' decoder lengths until the end of the pass: nothing below stages through it)
+  const GlowPass p = r.pass(F2max, F2, d_f2, B == 1 ? mel->frames[0] / nsq : -1, KC_GLOW_DEC_CONV, w->pinned);
+  if (p.taps) CHECK(p.tap("z0", dv.z, M * nsq));
   // the `half` switch as this call saw it: the decoder's WaveNets in fp16 (wn_f16.h)
   const bool glow_f16 = r.gm->f16_ok && r.gm->precision.load() == MI355TTS_PRECISION_F16;
   bool start_done = false;
   for (int blk = h.n_blocks_dec - 1; blk >= 0; --blk)
     CHECK(glow_flow_block(p, dv, r.gm->gin() ? v.cond : nullptr, glow_f16, blk, &start_done));
-  ProfScope ps(r.ctx, w, KC_SMALL, 0);
-  hipLaunchKernelGGL(mel_finalize_kernel, dim3((Fld + 255) / 256, std::min(M, 16), B), dim3(256), 0, s, dv.z, bsZ, F2, mel->frames_dev, M,
-                     nsq, mel->raw, mel->voc, (long long)M * Fld, Fld, to_mt(call.audio), call.audio ? 1 : 0);
-  return 0;
+  {
+    ProfScope ps(r.ctx, w, KC_SMALL, 0);
+    hipLaunchKernelGGL(mel_finalize_kernel, dim3((Fld + 255) / 256, std::min(M, 16), B), dim3(256), 0, s, dv.z, bsZ, F2, mel->frames_dev, M,
+                       nsq, mel->raw, mel->voc, (long long)M * Fld, Fld, to_mt(call.audio), call.audio ? 1 : 0);
+  }
+  return p.taps ? glow_tap(*p.taps, s, "mel", mel->raw, B, M, Fld, mel->frames.data()) : 0;
 }
 
 // The forward pass on frame `f`, which holds the mel (f.mel) from the moment it exists.  With `final_sync` false the mel's last
@@ -714,6 +806,14 @@ static int glow_run(CallFrame& f, const GlowModel* gm, const GlowCall& call, int
   Worker* w = f.w;
   const int glow_tiles = call.solo_tiles ? (1 << 30) : w->opt.env.glow_tiles > 0 ? w->opt.env.glow_tiles : 1024;
   GlowRun r{f.ctx, w, gm, call, Pmax, glow_tiles, glow_enc_layout(gm->hp, call.B, call.ids_ld, Pmax), {}, nullptr};
+  struct KnOut {  // a tapped call learns its launches' names through the worker; the worker forgets the address on every way out
+    Worker* w;
+    ~KnOut() { w->kn_out = nullptr; }
+  } kn_out{w};
+  if (call.taps) {
+    if (call.row_ids || call.solo_tiles) return fail(MI355TTS_ERR_INVALID, "the rows of a coalesced pass cannot be tapped: a call of its own");
+    w->kn_out = &call.taps->last_kn;
+  }
   CHECK(glow_encoder(r));
   CHECK(glow_durations(r, f));
   if (r.mel->max_frames == 0) f.done = true;  // nothing to decode, and glow_durations has waited for all there was
@@ -778,4 +878,30 @@ extern "C" int mi355tts_glow_infer_prosody(mi355tts_ctx* ctx, int glow, const in
   c.speaker_ids = speaker_ids;
   c.set_prosody(prosody, true);  // the two-call form: the mel always keeps the durations
   return glow_infer_impl(ctx, glow, c, out);
+}
+
+// ------------------------------------------------------------------ the test seam's entry point (the vocoder's twin: hifigan_forward.h)
+extern "C" int mi355tts_glow_infer_taps(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
+                                        float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
+                                        const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
+                                        uint32_t flags, const mi355tts_prosody* prosody, mi355tts_mel** out, char* json, int cap) {
+  if (!json) return fail(MI355TTS_ERR_INVALID, "null argument");
+  auto taps = std::make_shared<VocTaps>();
+  GlowCall c = glow_call(ids, id_lens, B, ids_ld, noise_scale, length_scale, noise, noise_ld, seed, audio, flags);
+  c.row_seeds = row_seeds;
+  c.speaker_ids = speaker_ids;
+  c.set_prosody(prosody, true);
+  c.taps = taps.get();
+  CHECK(glow_infer_impl(ctx, glow, c, out));  // (ends with the stream synchronised: the copies are complete)
+  const std::string s = voc_taps_json(*taps);
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->voc_taps = taps;  // mi355tts_voc_tap_copy serves whichever call tapped last
+  }
+  const int rc = copy_json(s, json, cap, "tap list buffer too small");
+  if (rc) {
+    mel_destroy(*out);
+    *out = nullptr;
+  }
+  return rc;
 }

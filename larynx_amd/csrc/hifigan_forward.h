@@ -1002,7 +1002,7 @@ extern "C" int mi355tts_voc_tap_copy(mi355tts_ctx* ctx, int index, float* dst, i
     std::lock_guard<std::mutex> lk(ctx->mu);
     taps = ctx->voc_taps;
   }
-  if (!taps || index < 0 || (size_t)index >= taps->taps.size()) return fail(MI355TTS_ERR_INVALID, "no tap %d (mi355tts_hifigan_infer_taps first)", index);
+  if (!taps || index < 0 || (size_t)index >= taps->taps.size()) return fail(MI355TTS_ERR_INVALID, "no tap %d (mi355tts_hifigan_infer_taps or mi355tts_glow_infer_taps first)", index);
   const VocTap& t = taps->taps[(size_t)index];
   const size_t n = (size_t)t.B * t.ch * t.ld;
   if ((size_t)std::max<int64_t>(cap, 0) < n) return fail(MI355TTS_ERR_TOO_SMALL, "tap %d holds %zu floats", index, n);

@@ -82,9 +82,9 @@ struct Worker : ProfLane {  // (its stream, event pairs, flop_scale and `quiet`:
   CallOptions opt;  // what selects this call's kernels, tiles and schedule: filled when the worker is checked out (acquire_worker)
 };
 
-// The activation planes of ONE vocoder call (mi355tts_hifigan_infer_taps, a test seam): a device copy of every plane the schedule
-// wrote, taken in stream order right behind the launch that wrote it (hifigan_forward.h: voc_tap).  Owned by the context and
-// replaced by the next such call.
+// The activation planes of ONE tapped call (mi355tts_hifigan_infer_taps / mi355tts_glow_infer_taps, the test seams): a device copy
+// of every plane the schedule wrote, taken in stream order right behind the launch that wrote it (hifigan_forward.h: voc_tap;
+// glow_forward.h: glow_tap).  Owned by the context and replaced by the next such call of either kind.
 struct VocTap {
   std::string name;
   int kn = -1;       // the kernel name the writing launch was counted under (KName; -1: none)

@@ -74,7 +74,7 @@ struct ProfLane {
   // this worker's launches are neither timed nor counted per kernel name (the dispatch self-check's own launches are not a
   // caller's: a worker-local switch, so concurrent calls on the context keep their samples and counts)
   bool quiet = false;
-  // where a tapped vocoder call (mi355tts_hifigan_infer_taps) learns the name its last launch was counted under; null otherwise
+  // where a tapped call (mi355tts_hifigan_infer_taps / mi355tts_glow_infer_taps) learns the name its last launch was counted under; null otherwise
   int* kn_out = nullptr;
 };
 

@@ -274,6 +274,47 @@ class Engine:
         )
         return MelBatch(self, out.value)
 
+    def glow_infer_taps(self, model: int, ids, noise_scale: float = 0.667, length_scale: float = 1.0, noise=None, seed: int = 0,
+                        speaker_ids=None, durations=None):
+        """Test seam (`mi355tts_glow_infer_taps` + `mi355tts_voc_tap_copy`): one GlowTTS call with `glow_infer`'s arguments ->
+        (MelBatch, taps).  `taps` lists, in launch order, every f32 plane the schedule wrote to memory: dicts with "name",
+        "channels", "ld", "len" (valid columns per row), "f16" (0), "kernel" (the name the launch was counted under, "-" for
+        none) and "x", the plane as float32 [B, channels, ld]."""
+        rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
+        B = len(rows)
+        lens = np.array([len(r) for r in rows], np.int32)
+        packed = np.zeros((B, max(int(lens.max()) if B else 0, 1)), np.int64)
+        for b, r in enumerate(rows):
+            packed[b, : len(r)] = r
+        nz_ptr, nz_ld = None, 0
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, np.float32)
+            if noise.ndim == 2:
+                noise = noise[None]
+            if noise.shape[0] != B:
+                raise ValueError("noise batch mismatch")
+            nz_ptr, nz_ld = noise.ctypes.data, noise.shape[2]
+        pros, keep = self._prosody(lens, packed.shape[1], None, durations, False)
+        spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
+        out = C.c_void_p()
+        cap = 1 << 20
+        buf = C.create_string_buffer(cap)
+        ffi.check(
+            self.lib,
+            self.lib.mi355tts_glow_infer_taps(
+                self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, packed.shape[1],
+                float(noise_scale), float(length_scale), nz_ptr, nz_ld, int(seed) & (2 ** 64 - 1), None,
+                spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None, None, 0, C.byref(pros), C.byref(out), buf, cap,
+            ),
+        )
+        del keep
+        taps = json.loads(buf.value.decode("ascii"))
+        for i, t in enumerate(taps):
+            x = np.empty((B, t["channels"], t["ld"]), np.float32)
+            ffi.check(self.lib, self.lib.mi355tts_voc_tap_copy(self._ctx, i, ffi.ptr(x), x.size))
+            t["x"] = x
+        return MelBatch(self, out.value, durations_ld=packed.shape[1]), taps
+
     def glow_align(self, model: int, ids, mel, frames=None, speaker_ids: typing.Union[None, int, typing.Sequence[int]] = None,
                    want_latent: bool = False):
         """Forced alignment (`mi355tts_glow_align`): which frames of `mel` belong to which phoneme id.  `ids` as in

@@ -258,6 +258,12 @@ _SIGNATURES: typing.Dict[str, typing.Tuple[typing.Any, typing.List[typing.Any]]]
     ),
     "mi355tts_hifigan_infer_taps": (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_int64, C.c_char_p, C.c_int]),
     "mi355tts_voc_tap_copy": (C.c_int, [_VP, C.c_int, _VP, C.c_int64]),
+    "mi355tts_glow_infer_taps": (
+        C.c_int,
+        [_VP, C.c_int, _VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_float, _VP, C.c_int, C.c_uint64,
+         C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(AudioSettingsC), C.c_uint32, C.POINTER(ProsodyC), C.POINTER(_VP),
+         C.c_char_p, C.c_int],
+    ),
     "mi355tts_bench_conv1d": (C.c_int, [_VP] + [C.c_int] * 8 + [C.POINTER(C.c_float)]),
     "mi355tts_set_profiling": (C.c_int, [_VP, C.c_int]),
     "mi355tts_set_option": (C.c_int, [_VP, C.c_char_p, C.c_int]),

@@ -409,13 +409,18 @@ def forced_durations(hp, F2, P=8, odd_sum=False):
 class GlowCase:
     """One compared call: `n` = the scanned length (P or F2), its ids and forced durations, the frame count they give."""
 
-    def __init__(self, hp, axis, n, odd_sum=False):
+    def __init__(self, hp, axis, n, odd_sum=False, frames_for=None):
+        """`frames_for` (axis "P"): only the first so many ids get their 2 frames, the rest none — a long encoder pass in front of
+        a short decoder pass."""
         from tests.test_emu_prosody import attn_durations
 
         self.axis, self.n, self.odd = axis, int(n), bool(odd_sum)
-        self.key = self.n + (100000 if odd_sum else 0) + (200000 if axis == "F2" else 0)
+        self.key = self.n + (100000 if odd_sum else 0) + (200000 if axis == "F2" else 0) + (400000 if frames_for is not None else 0)
         self.ids = glow_ids(hp, self.n if axis == "P" else 8)
         self.d = np.full(self.n, 2, np.int32) if axis == "P" else forced_durations(hp, self.n, 8, odd_sum)
+        if frames_for is not None:
+            assert axis == "P" and not odd_sum
+            self.d[frames_for:] = 0
         self.exp_d, self.F = attn_durations(self.d, hp.n_sqz)  # what the call reports: the last id truncated with the frame count
         self._hp, self._noise = hp, None
 
@@ -1066,3 +1071,388 @@ def check_layers(engine, hp, precision, frames, options=None, *, v, sd, label=""
                              "largest share: " + most["name"]))
     assert not failures, failures
     return report, kernels
+
+
+# ---- layer by layer: every launch of one GlowTTS call against float64, from the planes that launch read -------------------------
+# The planes of one call (`Engine.glow_infer_taps`) against tests/glow_layers_np.py.  The acoustic model's passes rewrite their
+# planes in place (x, t1, t2, h, acts, skip, z), so the walk keeps the LATEST tap of each tensor and feeds every launch's reference
+# the taps it read; a launch that writes two planes (lin16_kernel.ln with its stored normalised input, res_skip, glow_tail_kernel,
+# wn_f16_kernel) is computed once and its second plane compared when its tap comes.  Bounds: glow_layers_np's rule; acceptance:
+# voc_layers_np.bound_f32 on every valid column of every row, nothing exempt.
+GLOW_NAMED_KERNELS = ("attention_mfma_kernel", "attention_mfma_kernel.p768", "attention_kernel", "oproj_ln_kernel", "lin16_kernel",
+                      "lin16_kernel.ln", "lin16_kernel.wide", "gate16_kernel", "gate16_kernel.wide", "glow_tail_kernel", "wn_f16_kernel")
+
+
+def glow_layer_lengths(hp, precision, axis, kinds, lo=1):
+    """The smallest length >= `lo` along `axis` ("P" / "F2") at which every tile of glow_tiles(hp, precision) whose label starts with
+    one of `kinds` has at least three tiles inside a row, the last one ragged (two interior seams and a partial tile)."""
+    widths = sorted({w for lab, stage, w, _ in glow_tiles(hp, precision) if stage[0] == axis and any(lab.startswith(k) for k in kinds)})
+    assert widths, (axis, kinds)
+    n = lo
+    while not all(n > 2 * w and n % w for w in widths):
+        n += 1
+        assert n < 8192, (axis, kinds, widths)
+    return n
+
+
+WN_RESTATED_LAUNCHES = 2  # wn_f16_kernel launches per call whose planes are restated in float32 (row 0): the first two blocks
+_GLOW_TENSORS = {}  # id(state dict) -> (the state dict itself: held, so that its id is not reused; {tensor name: resolved tensor})
+
+
+def gate_grid_state_dict(sd, hp):
+    """`sd` with every block's LAST gate conv silenced (weight_g = 0: the folded weight is exactly zero) and its biases a grid: that
+    layer's pre-activations are the biases exactly, whatever h holds, so its `acts` plane isolates the gate epilogue (gate16.h /
+    conv_mfma.h: tanhf, expf; wn_f16.h: gate_fast) against float64 tanh(a) sigmoid(b) with nothing carried into the bound.
+    tanh biases span +-18 (block parity: +-6, denser around small arguments), past gate_fast's +-15 clamp; the sigmoid biases
+    span +-30, dealt across the tanh grid with a stride coprime to H."""
+    out = dict(sd)
+    H, j = hp.hidden_channels, hp.n_block_layers - 1
+    for blk in range(hp.n_blocks_dec):
+        key = f"decoder.flows.{3 * blk + 2}.wn.in_layers.{j}"
+        out[key + ".weight_g"] = np.zeros_like(np.asarray(sd[key + ".weight_g"]))
+        a = np.linspace(-18.0, 18.0, H) if blk % 2 == 0 else np.linspace(-6.0, 6.0, H)
+        b = np.linspace(-30.0, 30.0, H)[(np.arange(H) * (7 if blk % 2 == 0 else 11)) % H]
+        out[key + ".bias"] = np.concatenate([a, b]).astype(F32)
+    return out
+
+
+def _frame_to_id(exp_d):
+    return np.repeat(np.arange(len(exp_d)), np.asarray(exp_d, np.int64))
+
+
+def check_glow_layers(engine, hp, precision, case, options=None, *, g, sd, label="", speaker_ids=None, restate=False):
+    """One tapped GlowTTS call of model `g` (weights `sd`) in `precision` ("f32" / "f16") on the rows `case` (a GlowCase or a list
+    of them: one padded batch), durations forced and noise injected, under `options` ({name: (value, default)}).  Asserts: the
+    tapped call returns the plain call's mel plane, frames and durations bit for bit and launches the same kernels; the `mel` tap is
+    that plane, zero behind every row's frames; and for every tap, on every valid column of every row, |plane - ref64| within the
+    derived bound (glow_layers_np / voc_layers_np.bound_f32), ref64 built from the taps the launch read.  Every layer is walked
+    before anything fails; the failure names every failing layer, its kernel, its worst err / bound and (row, channel, column).
+    `restate`: also the float32 chain restatement of every launch of row 0 against the same bound (a CPU property: the device tests
+    leave it off).  Returns (rows of {"name", "kernel", "ratio", "at", "abs", "restated", "n"}, kernel names of the taps, the
+    call's kernel_counts)."""
+    from larynx_amd import weights
+    from tests import glow_layers_np as G
+    from tests import voc_layers_np as V
+
+    cases = list(case) if isinstance(case, (list, tuple)) else [case]
+    B = len(cases)
+    options = dict(options or {})
+    H, nh, win = hp.hidden_channels, hp.n_heads, hp.window_size
+    nsq, n, nb = hp.n_sqz, hp.n_block_layers, hp.n_blocks_dec
+    C = hp.mel_channels * nsq
+    half = C // 2
+    held, cache = _GLOW_TENSORS.setdefault(id(sd), (sd, {}))  # (folding a weight norm is as dear as a small launch's reference)
+    assert held is sd
+
+    def T_(name):
+        if name not in cache:
+            cache[name] = weights.resolve_tensor(sd, name)
+        return cache[name]
+
+    W_ = lambda name: T_(name + ".weight")
+    B_ = lambda name: T_(name + ".bias")
+    Fmax = max(c.F for c in cases)
+    noise = np.zeros((B, hp.mel_channels, Fmax + 5), F32)
+    for b, c in enumerate(cases):
+        noise[b, :, : c.noise.shape[1]] = c.noise
+    kw = dict(noise=noise, durations=[c.d for c in cases])
+    if speaker_ids is not None:
+        kw["speaker_ids"] = speaker_ids
+    ids = [c.ids for c in cases]
+    for k, (val, _) in options.items():
+        engine.set_option(k, val)
+    try:
+        assert engine.set_precision(g, LAYER_PRECISIONS[precision]) == 0, (label, precision)
+        engine.profile_reset()
+        mel = engine.glow_infer(g, ids, 0.667, 1.0, **kw)
+        c_plain = engine.kernel_counts()
+        plain = (mel_plane(engine, mel), [int(f) for f in mel.frames], mel.durations.copy())
+        mel.free()
+        engine.profile_reset()
+        mel, taps = engine.glow_infer_taps(g, ids, 0.667, 1.0, **kw)
+        c_taps = engine.kernel_counts()
+        tapped = (mel_plane(engine, mel), [int(f) for f in mel.frames], mel.durations.copy())
+        mel.free()
+    finally:
+        engine.set_precision(g, LAYER_PRECISIONS["f32"])
+        for k, (_, default) in options.items():
+            engine.set_option(k, default)
+    tag = f"{label} {precision} {cases!r}"
+    assert c_taps == c_plain, (tag, "the seam changed what runs", c_taps, c_plain)
+    failures = []
+    if not (np.array_equal(plain[0], tapped[0]) and plain[1] == tapped[1] and np.array_equal(plain[2], tapped[2])):
+        failures.append((tag, "the tapped call's mel, frames or durations differ from the plain call's"))
+    assert plain[1] == [c.F for c in cases], (tag, plain[1])
+    names = [t["name"] for t in taps]
+    assert len(set(names)) == len(names) and names[0] == "emb" and names[-1] == "mel", (tag, names)
+    by = {t["name"]: t for t in taps}
+    for b, c in enumerate(cases):
+        t = by["mel"]
+        if not (t["len"][b] == c.F and np.array_equal(t["x"][b], tapped[0][b]) and not np.any(t["x"][b][:, c.F :])):
+            failures.append((tag, "the mel tap is not the returned plane, or is not zero behind the row's frames", b))
+
+    def plane(name, b):
+        t = by[name]
+        return t["x"][b, :, : t["len"][b]].astype(np.float64)
+
+    # speaker conditioning (speaker_cond_kernel writes small tables, not planes): float64 from the embedding, with the error of
+    # its f32 evaluation (a gin-term contraction of a normalised vector) carried as a bound
+    gvec = None
+    if speaker_ids is not None:
+        spk = np.full(B, speaker_ids) if np.isscalar(speaker_ids) else np.asarray(speaker_ids)
+        e = T_("emb_g.weight").astype(np.float64)[spk]
+        gvec = e / np.maximum(np.sqrt((e * e).sum(axis=1, keepdims=True)), 1e-12)
+        gin = gvec.shape[1]
+
+    def spk_table(w2d, bias, b):
+        """w2d [rows, gin] . g + bias -> (value, bound)."""
+        w2d = w2d.astype(np.float64)
+        val = w2d @ gvec[b] + (0.0 if bias is None else bias.astype(np.float64))
+        mag = np.abs(w2d) @ np.abs(gvec[b]) + (0.0 if bias is None else np.abs(bias))
+        return val, (2 * gin + 8) * V.U23 * mag  # (the norm's gin-term sum, its root and reciprocal, then the contraction)
+
+    qkv_w = lambda l: np.concatenate([W_(f"encoder.encoder.attn_layers.{l}.conv_{c}") for c in "qkv"], axis=0)
+    qkv_b = lambda l: np.concatenate([B_(f"encoder.encoder.attn_layers.{l}.conv_{c}") for c in "qkv"], axis=0)
+    NORM = lambda p: (T_(p + ".gamma"), T_(p + ".beta"))
+    flow = lambda blk, j: f"decoder.flows.{3 * blk + j}"
+    mixw = lambda blk: (T_(flow(blk, 1) + ".weight_inv"), T_(flow(blk, 0) + ".bias").reshape(-1), T_(flow(blk, 0) + ".logs").reshape(-1))
+    npre = hp.prenet_layers if hp.prenet else 0
+    report, pending, pending32 = [], {}, {}
+    wn_restated, wn_sq = {}, {}  # wn_f16_kernel's planes restated in float32; per plane kind [sum err^2 of the kernel, of the restatement, n]
+    latest = {}  # tensor -> the tap that holds it now: "x" (the encoder's residual stream), "z", "h", "skip"
+
+    def reference(name, kernel, b):
+        """-> {tap name: (ref64, delta)} of the launch that wrote `name`, for row b; and the float32 restatement of `name` (or None)."""
+        c = cases[b]
+        P = len(c.ids)
+        parts = name.split(".")
+        if name == "emb":
+            return {name: G.embed(T_("encoder.emb.weight"), c.ids, H)}, G.embed_chain32(T_("encoder.emb.weight"), c.ids, H)
+        if parts[0] == "pre":
+            if parts[1] == "proj":
+                src, wn_, ln = f"pre.{npre - 1}", "encoder.pre.proj", NORM(f"encoder.pre.norm_layers.{npre - 1}")
+                res = plane("emb", b)
+            else:
+                i = int(parts[1])
+                src, wn_, res = ("emb" if i == 0 else f"pre.{i - 1}"), f"encoder.pre.conv_layers.{i}", None
+                ln = None if i == 0 else NORM(f"encoder.pre.norm_layers.{i - 1}")
+            if len(parts) == 3:  # the separate LayerNorm's output
+                return {name: G.layernorm(plane(src, b), *ln, relu=True)}, G.layernorm_chain32(plane(src, b), *ln, relu=True)
+            if ln is None or name + ".ln" in by:
+                x = plane(name + ".ln" if ln is not None else src, b)
+                return {name: G.linear(W_(wn_), B_(wn_), x, res=res)}, G.linear_chain32(W_(wn_), B_(wn_), x, res=res)
+            (y, dy), _ = G.ln_linear(W_(wn_), B_(wn_), plane(src, b), *ln, True, res=res)
+            return {name: (y, dy)}, G.linear_chain32(W_(wn_), B_(wn_), G.layernorm_chain32(plane(src, b), *ln, relu=True), res=res)
+        if parts[0].startswith("enc") and parts[0] != "enc":
+            l = int(parts[0][3:])
+            a_ = f"encoder.encoder.attn_layers.{l}"
+            f_ = f"encoder.encoder.ffn_layers.{l}"
+            x_in = f"enc{l}.x0" if l else ("pre.proj" if npre else "emb")
+            what = parts[1]
+            if what == "x0":  # the separate LayerNorm of the previous layer's t1 (the fused form files it with qkv)
+                ln = NORM(f"encoder.encoder.norm_layers_2.{l - 1}")
+                return {name: G.layernorm(plane(f"enc{l - 1}.t1", b), *ln)}, G.layernorm_chain32(plane(f"enc{l - 1}.t1", b), *ln)
+            if what == "qkv":
+                if l and kernel == "lin16_kernel.ln":
+                    ln = NORM(f"encoder.encoder.norm_layers_2.{l - 1}")
+                    t1 = plane(f"enc{l - 1}.t1", b)
+                    (y, dy), xn = G.ln_linear(qkv_w(l), qkv_b(l), t1, *ln, False)
+                    xn32 = G.layernorm_chain32(t1, *ln)
+                    return {name: (y, dy), f"enc{l}.x0": xn}, {name: G.linear_chain32(qkv_w(l), qkv_b(l), xn32), f"enc{l}.x0": xn32}
+                return {name: G.linear(qkv_w(l), qkv_b(l), plane(x_in, b))}, G.linear_chain32(qkv_w(l), qkv_b(l), plane(x_in, b))
+            if what == "att":
+                args = (plane(f"enc{l}.qkv", b), T_(a_ + ".emb_rel_k")[0], T_(a_ + ".emb_rel_v")[0], nh, win)
+                return {name: G.attention(*args)}, (G.attention_chain32(*args) if restate and b == 0 else None)
+            if what == "o":
+                args = (W_(a_ + ".conv_o"), B_(a_ + ".conv_o"), plane(f"enc{l}.att", b))
+                return {name: G.linear(*args, res=plane(x_in, b))}, G.linear_chain32(*args, res=plane(x_in, b))
+            if what == "x1":
+                ln = NORM(f"encoder.encoder.norm_layers_1.{l}")
+                if f"enc{l}.o" in by:
+                    return {name: G.layernorm(plane(f"enc{l}.o", b), *ln)}, G.layernorm_chain32(plane(f"enc{l}.o", b), *ln)
+                args = (W_(a_ + ".conv_o"), B_(a_ + ".conv_o"), plane(f"enc{l}.att", b))
+                return {name: G.oproj_ln(*args, plane(x_in, b), *ln)}, G.layernorm_chain32(G.linear_chain32(*args, res=plane(x_in, b)), *ln)
+            if what == "ffn":
+                args = (W_(f_ + ".conv_1"), B_(f_ + ".conv_1"), plane(f"enc{l}.x1", b))
+                return {name: G.linear(*args, relu=True)}, G.linear_chain32(*args, relu=True)
+            assert what == "t1", name
+            args = (W_(f_ + ".conv_2"), B_(f_ + ".conv_2"), plane(f"enc{l}.ffn", b))
+            return {name: G.linear(*args, res=plane(f"enc{l}.x1", b))}, G.linear_chain32(*args, res=plane(f"enc{l}.x1", b))
+        last_l = hp.n_layers_enc - 1
+        if name == "enc.out":
+            ln = NORM(f"encoder.encoder.norm_layers_2.{last_l}")
+            return {name: G.layernorm(plane(f"enc{last_l}.t1", b), *ln)}, G.layernorm_chain32(plane(f"enc{last_l}.t1", b), *ln)
+        pw = "encoder.proj_w"
+        if name == "xm":
+            args = (W_("encoder.proj_m"), B_("encoder.proj_m"), plane("enc.out", b))
+            return {name: G.linear(*args)}, G.linear_chain32(*args)
+        if name == "dp.spk":  # speaker_dp_plane_kernel: the speaker half of conv_1 over a constant vector, cut at the row's ends
+            w1 = W_(pw + ".conv_1")
+            K = w1.shape[2]
+            ref, dl, r32 = np.zeros((w1.shape[0], P)), np.zeros((w1.shape[0], P)), np.zeros((w1.shape[0], P), F32)
+            t = np.arange(P)
+            e32 = T_("emb_g.weight")[spk[b]].astype(F32)  # the restatement: the vector normalised and contracted in float32, backwards
+            g32 = e32 * (F32(1) / np.maximum(np.sqrt(np.sum(e32[::-1] * e32[::-1], dtype=F32)), F32(1e-12)))
+            for k in range(K):
+                val, bd = spk_table(w1[:, H:, k], None, b)
+                ok = ((t + k - K // 2 >= 0) & (t + k - K // 2 < P)).astype(np.float64)
+                ref += val[:, None] * ok[None, :]
+                dl += (bd + V.U23 * K * np.abs(val))[:, None] * ok[None, :]
+            for k in range(K - 1, -1, -1):
+                v32 = np.zeros(w1.shape[0], F32)
+                for i in range(gin - 1, -1, -1):
+                    v32 = v32 + w1[:, H + i, k] * g32[i]
+                r32 += v32[:, None] * ((t + k - K // 2 >= 0) & (t + k - K // 2 < P)).astype(F32)[None, :]
+            return {name: (ref, dl)}, r32
+        if name == "dp.1":
+            w1 = W_(pw + ".conv_1")[:, :H]
+            res = plane("dp.spk", b) if "dp.spk" in by else None
+            args = (w1, B_(pw + ".conv_1"), plane("enc.out", b))
+            return {name: G.linear(*args, res=res, relu=True)}, G.linear_chain32(*args, res=res, relu=True)
+        if name == "dp.2.ln":
+            return {name: G.layernorm(plane("dp.1", b), *NORM(pw + ".norm_1"))}, G.layernorm_chain32(plane("dp.1", b), *NORM(pw + ".norm_1"))
+        if name == "dp.2":
+            wb = (W_(pw + ".conv_2"), B_(pw + ".conv_2"))
+            if "dp.2.ln" in by:
+                return {name: G.linear(*wb, plane("dp.2.ln", b), relu=True)}, G.linear_chain32(*wb, plane("dp.2.ln", b), relu=True)
+            (y, dy), _ = G.ln_linear(*wb, plane("dp.1", b), *NORM(pw + ".norm_1"), False, relu=True)
+            return {name: (y, dy)}, G.linear_chain32(*wb, G.layernorm_chain32(plane("dp.1", b), *NORM(pw + ".norm_1")), relu=True)
+        if name == "logw.ln":
+            return {name: G.layernorm(plane("dp.2", b), *NORM(pw + ".norm_2"))}, G.layernorm_chain32(plane("dp.2", b), *NORM(pw + ".norm_2"))
+        if name == "logw":
+            wb = (W_(pw + ".proj"), B_(pw + ".proj"))
+            if "logw.ln" in by:
+                return {name: G.linear(*wb, plane("logw.ln", b))}, G.linear_chain32(*wb, plane("logw.ln", b))
+            return ({name: G.ln_proj(plane("dp.2", b), *NORM(pw + ".norm_2"), *wb)},
+                    G.linear_chain32(*wb, G.layernorm_chain32(plane("dp.2", b), *NORM(pw + ".norm_2"))))
+        if name == "z0":
+            args = (plane("xm", b), _frame_to_id(c.exp_d), c.noise, 0.667, nsq)
+            return {name: G.expand(*args)}, G.expand_chain32(*args)
+        if name == "mel":
+            return {name: G.finalize(plane(latest["z"], b), nsq)}, None
+        assert parts[0].startswith("blk") and len(parts) == 2, (tag, name)
+        blk, what = int(parts[0][3:]), parts[1]
+        cp = flow(blk, 2)
+        if what == "h":  # the start conv as a launch of its own (the first block's; every block's without the fused tail)
+            args = (W_(cp + ".start"), B_(cp + ".start"), plane(latest["z"], b)[:half])
+            return {name: G.linear(*args)}, G.linear_chain32(*args)
+        if what.startswith("acts"):
+            j = int(what[4:])
+            if kernel == "wn_f16_kernel":
+                assert j == n - 1, name
+                w_in = [W_(f"{cp}.wn.in_layers.{i}") for i in range(n)]
+                b_in = [B_(f"{cp}.wn.in_layers.{i}") for i in range(n)]
+                w_rs = [W_(f"{cp}.wn.res_skip_layers.{i}") for i in range(n - 1)]
+                b_rs = [B_(f"{cp}.wn.res_skip_layers.{i}") for i in range(n - 1)]
+                acts, skip = G.wn_f16(plane(latest["h"], b), w_in, b_in, w_rs, b_rs)
+                out = {name: acts}
+                if skip is not None:
+                    out[f"blk{blk}.skip{n - 2}"] = skip
+                if b == 0 and len(wn_restated) < 2 * WN_RESTATED_LAUNCHES:  # (the calibrated criterion's pool: row 0 of the first launches)
+                    a32, s32 = G.wn_f16_chain32(plane(latest["h"], b), w_in, b_in, w_rs, b_rs)
+                    wn_restated[name] = a32
+                    if s32 is not None:
+                        wn_restated[f"blk{blk}.skip{n - 2}"] = s32
+                return out, None
+            cond = None
+            wg, bg = W_(f"{cp}.wn.in_layers.{j}"), B_(f"{cp}.wn.in_layers.{j}")
+            x = plane(latest["h"], b)
+            dil = hp.dilation_rate ** j
+            if gvec is not None:
+                cw = W_(cp + ".wn.cond_layer")[:, :, 0][2 * H * j : 2 * H * (j + 1)]
+                cond, dcond = spk_table(cw, B_(cp + ".wn.cond_layer")[2 * H * j : 2 * H * (j + 1)], b)
+                pre, d = G.linear(wg, bg, x, dil, res=np.repeat(cond[:, None], x.shape[1], axis=1))
+                d = d + dcond[:, None]
+                return {name: G.gate_value(pre[:H], pre[H:], d[:H], d[H:])}, G.gate_chain32(wg, bg, x, dil, cond)
+            return {name: G.gate(wg, bg, x, dil)}, G.gate_chain32(wg, bg, x, dil)
+        if what.startswith("h") or what.startswith("skip"):
+            j = int(what[1:] if what.startswith("h") else what[4:])
+            lastj = j == n - 1
+            hj, sj = f"blk{blk}.h{j}", f"blk{blk}.skip{j}"
+            wr, br = W_(f"{cp}.wn.res_skip_layers.{j}"), B_(f"{cp}.wn.res_skip_layers.{j}")
+            acts, hin = plane(f"blk{blk}.acts{j}", b), plane(latest["h"], b)
+            sk = plane(f"blk{blk}.skip{j - 1}", b) if j else None
+            hh, ss = G.res_skip(wr, br, acts, hin, sk, lastj)
+            zero = np.zeros_like(acts)
+            r32 = G.linear_chain32(wr, br, acts, res=(zero if sk is None else sk) if lastj else np.concatenate([hin, zero if sk is None else sk]))
+            out = {sj: ss}
+            if hh is not None:
+                out[hj] = hh
+            return out, ({sj: r32} if lastj else {hj: r32[: acts.shape[0]], sj: r32[acts.shape[0] :]})
+        z = plane(latest["z"], b)
+        end = (W_(cp + ".end"), B_(cp + ".end"))
+        if what == "zc":
+            args = (plane(f"blk{blk}.skip{n - 1}", b), z, *end, *mixw(blk))
+            return {name: G.coupling_mix(*args, mix=False)}, G.coupling_mix_chain32(*args, mix=False)
+        assert what == "z", name
+        if kernel == "glow_tail_kernel":
+            rs = (W_(f"{cp}.wn.res_skip_layers.{n - 1}"), B_(f"{cp}.wn.res_skip_layers.{n - 1}"))
+            st = (W_(flow(blk - 1, 2) + ".start"), B_(flow(blk - 1, 2) + ".start")) if blk else None
+            acts = plane(f"blk{blk}.acts{n - 1}", b)
+            sk = plane(f"blk{blk}.skip{n - 2}", b) if n > 1 else None
+            zz, hn = G.glow_tail(acts, sk, z, rs, end, mixw(blk), st)
+            out = {name: zz}
+            if hn is not None:
+                out[f"blk{blk - 1}.h"] = hn
+            z32 = G.coupling_mix_chain32(G.linear_chain32(*rs, acts, res=sk), z, *end, *mixw(blk))
+            return out, ({name: z32} if st is None else {name: z32, f"blk{blk - 1}.h": G.linear_chain32(*st, z32[:half])})
+        if f"blk{blk}.zc" in by:
+            zc = plane(f"blk{blk}.zc", b)
+            return {name: G.mix_actnorm(zc, np.zeros_like(zc), *mixw(blk), n_split=hp.n_split)}, G.mix_actnorm_chain32(zc, *mixw(blk), n_split=hp.n_split)
+        args = (plane(f"blk{blk}.skip{n - 1}", b), z, *end, *mixw(blk))
+        return {name: G.coupling_mix(*args)}, G.coupling_mix_chain32(*args)
+
+    for t in taps:
+        name, kernel = t["name"], t["kernel"]
+        worst, r_worst, count, abs_worst = (0.0, None), None, 0, 0.0
+        for b in range(B):
+            got = plane(name, b)
+            key = (name, b)
+            if key not in pending:
+                refs, r32 = reference(name, kernel, b)
+                for k2, v2 in refs.items():
+                    pending[(k2, b)] = v2
+                # the launch's float32 restatement: of `name`, or {tap name: plane} for a launch that writes two
+                for k2, v2 in (r32 if isinstance(r32, dict) else {name: r32}).items():
+                    pending32[(k2, b)] = v2
+            ref, delta = pending.pop(key)
+            ref32 = pending32.pop(key, None)
+            assert ref.shape == got.shape, (tag, name, b, ref.shape, got.shape)
+            bound = V.bound_f32(ref, delta)
+            ratio = np.where(np.isfinite(got), np.abs(got - ref) / bound, np.inf)  # (an element never written is no number)
+            at = np.unravel_index(int(np.argmax(ratio)), ratio.shape) if ratio.size else (0, 0)
+            if ratio.size and float(ratio[at]) > worst[0]:
+                worst = (float(ratio[at]), (b, int(at[0]), int(at[1])))
+            if ratio.size:
+                abs_worst = max(abs_worst, float(np.abs(np.where(np.isfinite(got), got - ref, np.inf)).max()))
+            if b == 0 and name in wn_restated:
+                acc = wn_sq.setdefault("acts" if ".acts" in name else "skip", [0.0, 0.0, 0])
+                acc[0] += float(((got - ref) ** 2).sum())
+                acc[1] += float(((wn_restated[name].astype(np.float64) - ref) ** 2).sum())
+                acc[2] += got.size
+                if restate:
+                    r_worst = float((np.abs(wn_restated[name].astype(np.float64) - ref) / bound).max())
+            if restate and b == 0 and ref32 is not None and ratio.size:
+                r_worst = float((np.abs(ref32.astype(np.float64) - ref) / bound).max())
+            count += got.size
+        # the tensors a later launch reads by role
+        p2 = name.split(".")
+        if name == "z0" or (p2[0].startswith("blk") and p2[-1] in ("z", "zc")):
+            latest["z"] = name
+        if p2[0].startswith("blk") and p2[-1].startswith("h"):
+            latest["h"] = name
+        report.append(dict(name=name, kernel=kernel, ratio=worst[0], at=worst[1], abs=abs_worst, restated=r_worst, n=count))
+        rs_ = "" if r_worst is None else f", float32 restatement {r_worst:.3f}"
+        print(f"{tag} {name} [{kernel}]: worst err / bound {worst[0]:.3f} at (row, channel, column) {worst[1]} of {count}{rs_}")
+        if not worst[0] <= 1.0:
+            failures.append((tag, name, kernel, "outside the derived bound: err / bound, (row, channel, column)", worst))
+        if r_worst is not None and not r_worst <= 1.0:
+            failures.append((tag, name, "the float32 restatement is outside the bound: a wrong derivation", r_worst))
+    for what, (e_k, e_r, cnt) in sorted(wn_sq.items()):
+        rk, rr = np.sqrt(e_k / cnt), np.sqrt(e_r / cnt)
+        print(f"{tag} wn_f16_kernel {what}: RMS |plane - ref64| {rk:.3e} over {cnt} elements, float32 restatement {rr:.3e} (x {rk / max(rr, 1e-300):.2f})")
+        if not rk <= 4 * rr:
+            failures.append((tag, f"wn_f16_kernel {what}", "wn_f16_kernel", "RMS error above 4 x the float32 restatement's: more than the f32 summation order explains", (rk / max(rr, 1e-300), None)))
+    assert not pending, (tag, "planes a reference expected and no tap delivered", sorted(pending))
+    assert not failures, failures
+    return report, {t["kernel"] for t in taps}, c_taps
