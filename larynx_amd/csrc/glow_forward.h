@@ -8,32 +8,6 @@
 // ------------------------------------------------------------------ GlowTTS forward
 static bool glow_fuse_on(const Worker* w) { return !w->opt.env.glow_fuse_off && w->opt.glow_fuse; }
 
-// ------------------------------------------------------------------ the test seam: the planes of one call
-// (mi355tts_glow_infer_taps; the vocoder's twin, its name helper and the list's rendering are in hifigan_forward.h)
-static std::string tap_name(const char* fmt, ...);
-static std::string voc_taps_json(const VocTaps& T);
-// A copy of one f32 plane [B][ch][ld] with `len[b]` valid columns per row into the call's store (host_context.h: VocTaps), queued
-// on stream `s` behind whatever wrote the plane.  `same_launch`: the second plane of the launch that wrote the previous tap.
-static int glow_tap(VocTaps& T, hipStream_t s, const std::string& name, const float* x, int B, int ch, int ld, const int* len, bool same_launch = false) {
-  VocTap t;
-  t.name = name;
-  t.kn = same_launch && !T.taps.empty() ? T.taps.back().kn : T.last_kn;
-  T.last_kn = -1;  // (most small GlowTTS launches are counted under no name: the next tap must not inherit this one's)
-  t.B = B;
-  t.ch = ch;
-  t.ld = ld;
-  for (int b = 0; b < B; ++b) t.len.push_back(std::min(len[b], ld));
-  t.bytes = sizeof(float) * (size_t)B * (size_t)ch * (size_t)ld;
-  if (T.bytes + t.bytes > VocTaps::MAX_BYTES)
-    return fail(MI355TTS_ERR_NOMEM, "the planes of this call exceed %zu MB of tap copies (at '%s'): fewer ids, frames or rows", VocTaps::MAX_BYTES >> 20,
-                name.c_str());
-  HIPCHECK(hipMalloc(&t.dev, t.bytes));
-  T.bytes += t.bytes;
-  T.taps.push_back(t);  // (owned from here on: ~VocTaps frees it)
-  HIPCHECK(hipMemcpyAsync(t.dev, x, t.bytes, hipMemcpyDeviceToDevice, s));
-  return 0;
-}
-
 // What is constant over a run of GlowTTS launches; one instance serves the encoder, one the decoder.  A launch helper then
 // takes only what differs per launch: the conv, its ConvArgs, the norm's parameters.
 struct GlowPass {
@@ -55,10 +29,10 @@ struct GlowPass {
   VocTaps* taps = nullptr;
   const int* tap_len = nullptr;
 
-  // A copy of plane `x` [B][ch][ld], queued right behind the launch that wrote it (the passes rewrite their planes in place) and
-  // filed under the kernel name that launch was counted under ("-": a launch without one).  Callers test `taps` first.
+  // A copy of the f32 plane `x` [B][ch][ld], queued right behind the launch that wrote it (the passes rewrite their planes in
+  // place; host_taps.h).  `same_launch`: the second plane of the launch that wrote the previous tap.  Callers test `taps` first.
   int tap(const std::string& name, const float* x, int ch, bool same_launch = false) const {
-    return glow_tap(*taps, s, name, x, B, ch, ld, tap_len, same_launch);
+    return taps->add(s, name, x, false, B, ch, ld, tap_len, same_launch);
   }
 
   RowLen rows() const { return row_len(B, host_len, d_len); }
@@ -796,7 +770,7 @@ static int glow_decoder(GlowRun& r) {
     hipLaunchKernelGGL(mel_finalize_kernel, dim3((Fld + 255) / 256, std::min(M, 16), B), dim3(256), 0, s, dv.z, bsZ, F2, mel->frames_dev, M,
                        nsq, mel->raw, mel->voc, (long long)M * Fld, Fld, to_mt(call.audio), call.audio ? 1 : 0);
   }
-  return p.taps ? glow_tap(*p.taps, s, "mel", mel->raw, B, M, Fld, mel->frames.data()) : 0;
+  return p.taps ? p.taps->add(s, "mel", mel->raw, false, B, M, Fld, mel->frames.data(), false) : 0;
 }
 
 // The forward pass on frame `f`, which holds the mel (f.mel) from the moment it exists.  With `final_sync` false the mel's last
@@ -806,14 +780,8 @@ static int glow_run(CallFrame& f, const GlowModel* gm, const GlowCall& call, int
   Worker* w = f.w;
   const int glow_tiles = call.solo_tiles ? (1 << 30) : w->opt.env.glow_tiles > 0 ? w->opt.env.glow_tiles : 1024;
   GlowRun r{f.ctx, w, gm, call, Pmax, glow_tiles, glow_enc_layout(gm->hp, call.B, call.ids_ld, Pmax), {}, nullptr};
-  struct KnOut {  // a tapped call learns its launches' names through the worker; the worker forgets the address on every way out
-    Worker* w;
-    ~KnOut() { w->kn_out = nullptr; }
-  } kn_out{w};
-  if (call.taps) {
-    if (call.row_ids || call.solo_tiles) return fail(MI355TTS_ERR_INVALID, "the rows of a coalesced pass cannot be tapped: a call of its own");
-    w->kn_out = &call.taps->last_kn;
-  }
+  if (call.taps && (call.row_ids || call.solo_tiles)) return fail(MI355TTS_ERR_INVALID, "the rows of a coalesced pass cannot be tapped: a call of its own");
+  TapNames kn_out(w, call.taps);
   CHECK(glow_encoder(r));
   CHECK(glow_durations(r, f));
   if (r.mel->max_frames == 0) f.done = true;  // nothing to decode, and glow_durations has waited for all there was
@@ -880,7 +848,7 @@ extern "C" int mi355tts_glow_infer_prosody(mi355tts_ctx* ctx, int glow, const in
   return glow_infer_impl(ctx, glow, c, out);
 }
 
-// ------------------------------------------------------------------ the test seam's entry point (the vocoder's twin: hifigan_forward.h)
+// ------------------------------------------------------------------ the test seam's entry point (the store and the read-out: host_taps.h)
 extern "C" int mi355tts_glow_infer_taps(mi355tts_ctx* ctx, int glow, const int64_t* ids, const int32_t* id_lens, int B, int ids_ld,
                                         float noise_scale, float length_scale, const float* noise, int noise_ld, uint64_t seed,
                                         const uint64_t* row_seeds, const int32_t* speaker_ids, const mi355tts_audio_settings* audio,
@@ -893,12 +861,7 @@ extern "C" int mi355tts_glow_infer_taps(mi355tts_ctx* ctx, int glow, const int64
   c.set_prosody(prosody, true);
   c.taps = taps.get();
   CHECK(glow_infer_impl(ctx, glow, c, out));  // (ends with the stream synchronised: the copies are complete)
-  const std::string s = voc_taps_json(*taps);
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->voc_taps = taps;  // mi355tts_voc_tap_copy serves whichever call tapped last
-  }
-  const int rc = copy_json(s, json, cap, "tap list buffer too small");
+  const int rc = finish_taps(ctx, taps, json, cap);
   if (rc) {
     mel_destroy(*out);
     *out = nullptr;

@@ -186,35 +186,12 @@ struct VocPass {
 
 // ------------------------------------------------------------------ the test seam: the planes of one call
 // A copy of the plane the last launch on `p.s` wrote — `ch` channels at row stride `ld`, rows of frames x `mul` columns, fp16 octet
-// planes or f32 rows — queued on the same stream right behind that launch: the schedule reuses its planes, so a copy at the end
-// of the call would be too late.  Filed under the kernel name that launch was counted under.  Callers test `p.taps` first: with
-// ProfScope::kernel's test of `kn_out`, all a plain call pays for the seam.
-static std::string tap_name(const char* fmt, ...) {
-  char tmp[64];
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(tmp, sizeof(tmp), fmt, ap);
-  va_end(ap);
-  return tmp;
-}
+// planes or f32 rows — queued on the same stream right behind that launch (host_taps.h).  Callers test `p.taps` first.
 static int voc_tap(VocPass& p, const std::string& name, const void* x, bool f16, int ch, int ld, int mul) {
-  VocTaps& T = *p.taps;
-  VocTap t;
-  t.name = name;
-  t.kn = T.last_kn;
-  t.f16 = f16;
-  t.B = p.B;
-  t.ch = ch;
-  t.ld = ld;
-  for (int b = 0; b < p.B; ++b) t.len.push_back((int)std::min<long long>((long long)p.mel->frames[b] * mul, ld));
-  t.bytes = f16 ? (size_t)p.B * (size_t)((ch + 7) / 8) * (size_t)ld * 16 : sizeof(float) * (size_t)p.B * (size_t)ch * (size_t)ld;
-  if (T.bytes + t.bytes > VocTaps::MAX_BYTES)
-    return fail(MI355TTS_ERR_NOMEM, "the planes of this call exceed %zu MB of tap copies (at '%s'): fewer frames or rows", VocTaps::MAX_BYTES >> 20, name.c_str());
-  HIPCHECK(hipMalloc(&t.dev, t.bytes));
-  T.bytes += t.bytes;
-  T.taps.push_back(t);  // (owned from here on: ~VocTaps frees it)
-  HIPCHECK(hipMemcpyAsync(t.dev, x, t.bytes, hipMemcpyDeviceToDevice, p.s));
-  return 0;
+  std::vector<int> len;
+  for (int b = 0; b < p.B; ++b) len.push_back((int)std::min<long long>((long long)p.mel->frames[b] * mul, ld));
+  // a plane with no counted launch since the tap before it (a `.t` plane, the second of two sums) is filed under that tap's launch
+  return p.taps->add(p.s, name, x, f16, p.B, ch, ld, len.data(), p.taps->last_kn < 0);
 }
 
 // ------------------------------------------------------------------ stage bookkeeping, shared by both precisions
@@ -876,11 +853,7 @@ static int hifigan_run(CallFrame& f, HifiModel* hm, const mi355tts_mel* mel, con
   f.w->flop_scale = (double)sum / ((double)mel->B * mel->max_frames);
   VocPass p(f, hm, mel, call);
   CHECK(p.bind(call, rows));
-  struct KnOut {  // a tapped call learns its launches' names through the worker; the worker forgets the address on every way out
-    Worker* w;
-    ~KnOut() { w->kn_out = nullptr; }
-  } kn_out{f.w};
-  if (p.taps) f.w->kn_out = &p.taps->last_kn;
+  TapNames kn_out(f.w, p.taps);
   CHECK(p.f16 ? hifigan_body_f16(p) : hifigan_body_f32(p));
   return voc_deliver(p, call, rows, voc_denoise(p));
 }
@@ -962,22 +935,7 @@ extern "C" int mi355tts_hifigan_infer_padded(mi355tts_ctx* ctx, int vocoder, con
   return hifigan_call(ctx, vocoder, mel, c);
 }
 
-// ------------------------------------------------------------------ the test seam's two entry points
-// [{"name": "up0", "channels": 64, "ld": 140, "len": [140, 18], "f16": 1, "kernel": "conv_f16_kernel"}, ...] in launch order
-static std::string voc_taps_json(const VocTaps& T) {
-  std::string s = "[";
-  for (size_t i = 0; i < T.taps.size(); ++i) {
-    const VocTap& t = T.taps[i];
-    char tmp[256];
-    std::snprintf(tmp, sizeof(tmp), "%s{\"name\": \"%s\", \"channels\": %d, \"ld\": %d, \"len\": [", i ? ", " : "", t.name.c_str(), t.ch, t.ld);
-    s += tmp;
-    for (size_t b = 0; b < t.len.size(); ++b) s += (b ? ", " : "") + std::to_string(t.len[b]);
-    std::snprintf(tmp, sizeof(tmp), "], \"f16\": %d, \"kernel\": \"%s\"}", t.f16 ? 1 : 0, t.kn >= 0 && t.kn < KN_COUNT ? kname_name[t.kn] : "-");
-    s += tmp;
-  }
-  return s + "]";
-}
-
+// ------------------------------------------------------------------ the test seam's entry point (the store and the read-out: host_taps.h)
 extern "C" int mi355tts_hifigan_infer_taps(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, float* wav_f32, int64_t wav_ld,
                                            char* json, int cap) {
   if (!ctx || !mel || !wav_f32 || !json) return fail(MI355TTS_ERR_INVALID, "null argument");
@@ -987,39 +945,7 @@ extern "C" int mi355tts_hifigan_infer_taps(mi355tts_ctx* ctx, int vocoder, const
   c.wav_ld = wav_ld;
   c.taps = taps.get();
   CHECK(hifigan_call(ctx, vocoder, mel, c));  // (ends with the stream synchronised: the copies are complete)
-  const std::string s = voc_taps_json(*taps);
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->voc_taps = taps;
-  }
-  return copy_json(s, json, cap, "tap list buffer too small");
-}
-
-extern "C" int mi355tts_voc_tap_copy(mi355tts_ctx* ctx, int index, float* dst, int64_t cap) {
-  if (!ctx || !dst) return fail(MI355TTS_ERR_INVALID, "null argument");
-  std::shared_ptr<VocTaps> taps;
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    taps = ctx->voc_taps;
-  }
-  if (!taps || index < 0 || (size_t)index >= taps->taps.size()) return fail(MI355TTS_ERR_INVALID, "no tap %d (mi355tts_hifigan_infer_taps or mi355tts_glow_infer_taps first)", index);
-  const VocTap& t = taps->taps[(size_t)index];
-  const size_t n = (size_t)t.B * t.ch * t.ld;
-  if ((size_t)std::max<int64_t>(cap, 0) < n) return fail(MI355TTS_ERR_TOO_SMALL, "tap %d holds %zu floats", index, n);
-  HIPCHECK(hipSetDevice(ctx->device));
-  if (!t.f16) {
-    HIPCHECK(hipMemcpy(dst, t.dev, t.bytes, hipMemcpyDeviceToHost));
-    return 0;
-  }
-  // octet planes [B][ch / 8][ld][8] halves -> [B][ch][ld] floats (every half is a float: exact)
-  std::vector<_Float16> h(t.bytes / sizeof(_Float16));
-  HIPCHECK(hipMemcpy(h.data(), t.dev, t.bytes, hipMemcpyDeviceToHost));
-  const size_t noct = (size_t)t.ch / 8, ld = (size_t)t.ld;
-  for (size_t b = 0; b < (size_t)t.B; ++b)
-    for (size_t o = 0; o < noct; ++o)
-      for (size_t col = 0; col < ld; ++col)
-        for (size_t e = 0; e < 8; ++e) dst[(b * t.ch + 8 * o + e) * ld + col] = (float)h[((b * noct + o) * ld + col) * 8 + e];
-  return 0;
+  return finish_taps(ctx, taps, json, cap);
 }
 
 extern "C" int mi355tts_hifigan_infer(mi355tts_ctx* ctx, int vocoder, const mi355tts_mel* mel, float denoiser_strength,

@@ -82,33 +82,8 @@ struct Worker : ProfLane {  // (its stream, event pairs, flop_scale and `quiet`:
   CallOptions opt;  // what selects this call's kernels, tiles and schedule: filled when the worker is checked out (acquire_worker)
 };
 
-// The activation planes of ONE tapped call (mi355tts_hifigan_infer_taps / mi355tts_glow_infer_taps, the test seams): a device copy
-// of every plane the schedule wrote, taken in stream order right behind the launch that wrote it (hifigan_forward.h: voc_tap;
-// glow_forward.h: glow_tap).  Owned by the context and replaced by the next such call of either kind.
-struct VocTap {
-  std::string name;
-  int kn = -1;       // the kernel name the writing launch was counted under (KName; -1: none)
-  bool f16 = false;  // fp16 octet planes [B][ch / 8][ld][8]; else f32 [B][ch][ld]
-  int B = 0, ch = 0, ld = 0;
-  std::vector<int> len;  // valid columns per row
-  void* dev = nullptr;
-  size_t bytes = 0;
-};
-struct VocTaps {
-  static constexpr size_t MAX_BYTES = (size_t)256 << 20;
-  std::vector<VocTap> taps;
-  size_t bytes = 0;
-  int last_kn = -1;  // ProfScope::kernel writes the running launch's name here (ProfLane::kn_out)
-  VocTaps() = default;
-  VocTaps(const VocTaps&) = delete;
-  ~VocTaps() {
-    for (auto& t : taps)
-      if (t.dev) hipFree(t.dev);
-  }
-};
-
 struct mi355tts_ctx : ProfSums {  // (the profiling switch, the launch sums and the name counters: host_profile.h)
-  std::shared_ptr<VocTaps> voc_taps;  // the last tapped call's planes (under `mu`)
+  std::shared_ptr<struct VocTaps> voc_taps;  // the last tapped call's planes (under `mu`; host_taps.h)
   int device = 0;
   int ncu = 256;  // compute units (hipGetDeviceProperties at create): the dispatch-order logic of grouped launches
   std::mutex mu;

@@ -57,6 +57,7 @@ using namespace mi355tts;
 #include "host_models.h"
 #include "host_options.h"
 #include "host_context.h"
+#include "host_taps.h"
 #include "host_call.h"
 #include "host_rows.h"
 #include "host_group.h"

@@ -69,7 +69,7 @@ class MelBatch:
             P = self._durations_ld
             out = np.zeros((self.batch, max(P, 1)), np.int32)
             lib = self._engine.lib
-            if lib.mi355tts_mel_durations(self.handle, out.ctypes.data_as(C.POINTER(C.c_int32)), out.shape[1]) < 0:
+            if lib.mi355tts_mel_durations(self.handle, ffi.i32p(out), out.shape[1]) < 0:
                 raise ValueError("this mel batch carries no durations (ask for them: want_durations=True)")
             self._durations = out[:, :P]
         return self._durations
@@ -147,16 +147,19 @@ class Engine:
     def _load(self, fn, hp_c, state_dict, blob, device_ptr) -> int:
         man = ffi.manifest(self.lib, hp_c)
         total = sum(n for _, n in man)
-        model = C.c_int()
         if device_ptr:
-            ffi.check(self.lib, fn(self._ctx, C.byref(hp_c), C.c_void_p(device_ptr), total, 1, C.byref(model)))
-        else:
-            if blob is None:
-                blob = build_blob(man, state_dict)
-            blob = np.ascontiguousarray(blob, np.float32)
-            if blob.size != total:
-                raise ValueError(f"blob has {blob.size} floats, model needs {total}")
-            ffi.check(self.lib, fn(self._ctx, C.byref(hp_c), blob.ctypes.data, total, 0, C.byref(model)))
+            return self._loaded(fn, C.byref(hp_c), C.c_void_p(device_ptr), total, 1)
+        if blob is None:
+            blob = build_blob(man, state_dict)
+        blob = np.ascontiguousarray(blob, np.float32)
+        if blob.size != total:
+            raise ValueError(f"blob has {blob.size} floats, model needs {total}")
+        return self._loaded(fn, C.byref(hp_c), blob.ctypes.data, total, 0)
+
+    def _loaded(self, fn, *args) -> int:
+        """The tail of every load: `fn(ctx, *args, &model)` -> the new model's id."""
+        model = C.c_int()
+        ffi.check(self.lib, fn(self._ctx, *args, C.byref(model)))
         return int(model.value)
 
     def broadcast_weights(self, nccl_comm: int, root: int, device_ptr: int, numel: int, rccl_library: typing.Optional[str] = None):
@@ -203,76 +206,65 @@ class Engine:
         1.0 changes nothing, 0 gives the id no frames.  `durations`: the frames per id outright ([P] ints or one vector
         per row), instead of the duration predictor's.  Either of them, or `want_durations`, makes `MelBatch.durations`
         available."""
-        rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
-        if isinstance(ids, np.ndarray) and ids.ndim == 2:
-            rows = [np.asarray(r, np.int64) for r in ids]
-        B = len(rows)
-        lens = np.array([len(r) for r in rows], np.int32)
-        ld = int(lens.max()) if B else 0
-        packed = np.zeros((B, max(ld, 1)), np.int64)
-        for b, r in enumerate(rows):
-            packed[b, : len(r)] = r
-        nz_ptr, nz_ld = None, 0
-        if noise is not None:
-            noise = np.ascontiguousarray(noise, np.float32)
-            if noise.ndim == 2:
-                noise = noise[None]
-            if noise.shape[0] != B:
-                raise ValueError("noise batch mismatch")
-            nz_ptr, nz_ld = noise.ctypes.data, noise.shape[2]
-        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
-        out = C.c_void_p()
+        packed, lens, B, ld = self._ids_in(ids)
+        noise, nz_ptr, nz_ld = self._noise_in(noise, B)
         if row_seeds is not None and (noise is not None or len(row_seeds) != B):
             raise ValueError("row_seeds: one seed per row, and no explicit noise")
+        rs = None if row_seeds is None else np.array([ffi.u64(x) for x in row_seeds], np.uint64)
+        pros = keep = None
         if id_scales is not None or durations is not None or want_durations:
-            pros, keep = self._prosody(lens, packed.shape[1], id_scales, durations, False)
-            spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
-            rs = None if row_seeds is None else np.array([int(x) & (2 ** 64 - 1) for x in row_seeds], np.uint64)
-            ffi.check(
-                self.lib,
-                self.lib.mi355tts_glow_infer_prosody(
-                    self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, packed.shape[1],
-                    float(noise_scale), float(length_scale), nz_ptr, nz_ld, int(seed) & (2 ** 64 - 1),
-                    rs.ctypes.data_as(C.POINTER(C.c_uint64)) if rs is not None else None,
-                    spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
-                    C.byref(a) if a is not None else None, 0, C.byref(pros), C.byref(out),
-                ),
-            )
-            del keep
-            return MelBatch(self, out.value, durations_ld=packed.shape[1])
-        if speaker_ids is not None:
-            spk = self._speaker_array(speaker_ids, B)
-            rs = None if row_seeds is None else np.array([int(x) & (2 ** 64 - 1) for x in row_seeds], np.uint64)
-            ffi.check(
-                self.lib,
-                self.lib.mi355tts_glow_infer_speakers(
-                    self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, packed.shape[1],
-                    float(noise_scale), float(length_scale), nz_ptr, nz_ld, int(seed) & (2 ** 64 - 1),
-                    rs.ctypes.data_as(C.POINTER(C.c_uint64)) if rs is not None else None,
-                    spk.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(a) if a is not None else None, 0, C.byref(out),
-                ),
-            )
-            return MelBatch(self, out.value)
-        if row_seeds is not None:
-            rs = np.array([int(x) & (2 ** 64 - 1) for x in row_seeds], np.uint64)
-            ffi.check(
-                self.lib,
-                self.lib.mi355tts_glow_infer_rows(
-                    self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, packed.shape[1],
-                    float(noise_scale), float(length_scale), rs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                    C.byref(a) if a is not None else None, 0, C.byref(out),
-                ),
-            )
-            return MelBatch(self, out.value)
-        ffi.check(
-            self.lib,
-            self.lib.mi355tts_glow_infer(
-                self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, packed.shape[1],
-                float(noise_scale), float(length_scale), nz_ptr, nz_ld, int(seed) & (2 ** 64 - 1),
-                C.byref(a) if a is not None else None, 0, C.byref(out),
-            ),
-        )
-        return MelBatch(self, out.value)
+            pros, keep = self._prosody(lens, ld, id_scales, durations, False)
+        spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
+        out = C.c_void_p()
+        head = self._glow_head((model,), packed.ctypes.data, lens, ld, noise_scale, length_scale, nz_ptr, nz_ld, seed)
+        ffi.check(self.lib, self._glow_call("mi355tts_glow_infer", head, rs, spk, (ffi.audio_ref(audio_settings), 0), pros, (C.byref(out),)))
+        del keep
+        return MelBatch(self, out.value, durations_ld=ld if pros is not None else 0)
+
+    @staticmethod
+    def _ids_in(ids):
+        """The phoneme ids of a call, one int64 vector [P] or a sequence of them (the rows of a 2-D array among them), as the
+        library takes them -> (packed int64 [B, ld] with zeros behind a row's ids, lens int32 [B], B, ld = max(longest row, 1)).
+        No rows, or a row without ids, is the library's to refuse."""
+        rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
+        B = len(rows)
+        lens = np.array([len(r) for r in rows], np.int32)
+        packed = np.zeros((B, max(int(lens.max()) if B else 0, 1)), np.int64)
+        for b, r in enumerate(rows):
+            packed[b, : len(r)] = r
+        return packed, lens, B, packed.shape[1]
+
+    @staticmethod
+    def _noise_in(noise, B: int):
+        """The explicit noise of a call, [B, M, >=F] (or [M, >=F] at B = 1) or None -> (the float32 array to hold until the call
+        returns, its pointer, its row stride): (None, None, 0) without noise.  A batch other than B would be read past its end."""
+        if noise is None:
+            return None, None, 0
+        noise = np.ascontiguousarray(noise, np.float32)
+        if noise.ndim == 2:
+            noise = noise[None]
+        if noise.shape[0] != B:
+            raise ValueError("noise batch mismatch")
+        return noise, noise.ctypes.data, noise.shape[2]
+
+    def _glow_head(self, models, ids_ptr, lens: np.ndarray, ids_ld, noise_scale, length_scale, noise_ptr, noise_ld, seed) -> tuple:
+        """The arguments every GlowTTS entry point starts with, context to seed; `models`: (glow,) or (glow, vocoder)."""
+        return (self._ctx, *models, ids_ptr, ffi.i32p(lens), len(lens), ids_ld, float(noise_scale), float(length_scale), noise_ptr,
+                noise_ld, ffi.u64(seed))
+
+    def _glow_call(self, stem: str, head: tuple, rs, spk, tail: tuple, pros, last: tuple = ()) -> int:
+        """Calls the entry point of the family `stem` ("mi355tts_glow_infer" / "mi355tts_synthesize") that the arguments given
+        select, the narrowest that takes them: `_prosody` with `pros`, else `_speakers` with `spk`, else `_rows` with `rs`
+        (row seeds: `glow_infer`'s family alone takes them), else the plain one.  `head`: `_glow_head`'s; `tail`: from the audio
+        settings to the flags; `last`: what follows the prosody.  -> the library's status."""
+        seeds = (ffi.u64p(rs),) if stem == "mi355tts_glow_infer" else ()
+        if pros is not None:
+            return getattr(self.lib, stem + "_prosody")(*head, *seeds, ffi.i32p(spk), *tail, C.byref(pros), *last)
+        if spk is not None:
+            return getattr(self.lib, stem + "_speakers")(*head, *seeds, ffi.i32p(spk), *tail, *last)
+        if rs is not None:  # (no noise pointer, stride or seed: the rows' seeds stand for all three)
+            return self.lib.mi355tts_glow_infer_rows(*head[:-3], *seeds, *tail, *last)
+        return getattr(self.lib, stem)(*head, *tail, *last)
 
     def glow_infer_taps(self, model: int, ids, noise_scale: float = 0.667, length_scale: float = 1.0, noise=None, seed: int = 0,
                         speaker_ids=None, durations=None):
@@ -280,40 +272,26 @@ class Engine:
         (MelBatch, taps).  `taps` lists, in launch order, every f32 plane the schedule wrote to memory: dicts with "name",
         "channels", "ld", "len" (valid columns per row), "f16" (0), "kernel" (the name the launch was counted under, "-" for
         none) and "x", the plane as float32 [B, channels, ld]."""
-        rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
-        B = len(rows)
-        lens = np.array([len(r) for r in rows], np.int32)
-        packed = np.zeros((B, max(int(lens.max()) if B else 0, 1)), np.int64)
-        for b, r in enumerate(rows):
-            packed[b, : len(r)] = r
-        nz_ptr, nz_ld = None, 0
-        if noise is not None:
-            noise = np.ascontiguousarray(noise, np.float32)
-            if noise.ndim == 2:
-                noise = noise[None]
-            if noise.shape[0] != B:
-                raise ValueError("noise batch mismatch")
-            nz_ptr, nz_ld = noise.ctypes.data, noise.shape[2]
-        pros, keep = self._prosody(lens, packed.shape[1], None, durations, False)
+        packed, lens, B, ld = self._ids_in(ids)
+        noise, nz_ptr, nz_ld = self._noise_in(noise, B)
+        pros, keep = self._prosody(lens, ld, None, durations, False)
         spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
         out = C.c_void_p()
         cap = 1 << 20
         buf = C.create_string_buffer(cap)
-        ffi.check(
-            self.lib,
-            self.lib.mi355tts_glow_infer_taps(
-                self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, packed.shape[1],
-                float(noise_scale), float(length_scale), nz_ptr, nz_ld, int(seed) & (2 ** 64 - 1), None,
-                spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None, None, 0, C.byref(pros), C.byref(out), buf, cap,
-            ),
-        )
+        head = self._glow_head((model,), packed.ctypes.data, lens, ld, noise_scale, length_scale, nz_ptr, nz_ld, seed)
+        ffi.check(self.lib, self.lib.mi355tts_glow_infer_taps(*head, None, ffi.i32p(spk), None, 0, C.byref(pros), C.byref(out), buf, cap))
         del keep
+        return MelBatch(self, out.value, durations_ld=ld), self._taps_out(buf, B)
+
+    def _taps_out(self, buf, B: int) -> list:
+        """The tap list a `*_infer_taps` call left in `buf`, every entry with its plane "x" (`mi355tts_voc_tap_copy`)."""
         taps = json.loads(buf.value.decode("ascii"))
         for i, t in enumerate(taps):
             x = np.empty((B, t["channels"], t["ld"]), np.float32)
             ffi.check(self.lib, self.lib.mi355tts_voc_tap_copy(self._ctx, i, ffi.ptr(x), x.size))
             t["x"] = x
-        return MelBatch(self, out.value, durations_ld=packed.shape[1]), taps
+        return taps
 
     def glow_align(self, model: int, ids, mel, frames=None, speaker_ids: typing.Union[None, int, typing.Sequence[int]] = None,
                    want_latent: bool = False):
@@ -323,13 +301,7 @@ class Engine:
         a row's length, each row summing to its frame count cut down to a multiple of n_sqz —, scores float32 [B]) and, with
         `want_latent`, the latent z [B, M, F] as a third item.  Feed a row's durations to `glow_infer(durations=...)` to put
         this mel's timing onto another take."""
-        rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
-        B = len(rows)
-        lens = np.array([len(r) for r in rows], np.int32)
-        ld = max(int(lens.max()) if B else 0, 1)
-        packed = np.zeros((B, ld), np.int64)
-        for b, r in enumerate(rows):
-            packed[b, : len(r)] = r
+        packed, lens, B, ld = self._ids_in(ids)
         flags = 0
         if isinstance(mel, MelBatch):  # its raw plane where it lies: no host round trip
             if mel.batch != B or mel.max_frames < 1:
@@ -356,9 +328,8 @@ class Engine:
         ffi.check(
             self.lib,
             self.lib.mi355tts_glow_align(
-                self._ctx, model, packed.ctypes.data, lens.ctypes.data_as(C.POINTER(C.c_int32)), B, ld, mel_ptr,
-                fr.ctypes.data_as(C.POINTER(C.c_int32)), mel_ld, spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
-                flags, dur.ctypes.data_as(C.POINTER(C.c_int32)), ld, score.ctypes.data_as(C.POINTER(C.c_float)), ffi.ptr(z),
+                self._ctx, model, packed.ctypes.data, ffi.i32p(lens), B, ld, mel_ptr, ffi.i32p(fr), mel_ld, ffi.i32p(spk),
+                flags, ffi.i32p(dur), ld, ffi.f32p(score), ffi.ptr(z),
             ),
         )
         return (dur, score, z[:, :, :z_frames]) if want_latent else (dur, score)
@@ -374,9 +345,8 @@ class Engine:
         fr = np.full(B, F, np.int32) if frames is None else np.ascontiguousarray(frames, np.int32)
         dur = np.zeros((B, P), np.int32)
         score = np.zeros(B, np.float32)
-        i32 = C.POINTER(C.c_int32)
-        ffi.check(self.lib, self.lib.mi355tts_op_maximum_path(self._ctx, value.ctypes.data, B, P, F, pl.ctypes.data_as(i32), fr.ctypes.data_as(i32),
-                                                             dur.ctypes.data_as(i32), P, score.ctypes.data_as(C.POINTER(C.c_float))))
+        ffi.check(self.lib, self.lib.mi355tts_op_maximum_path(self._ctx, value.ctypes.data, B, P, F, ffi.i32p(pl), ffi.i32p(fr),
+                                                             ffi.i32p(dur), P, ffi.f32p(score)))
         return dur, score
 
     @staticmethod
@@ -400,9 +370,9 @@ class Engine:
         din = pack(durations, np.int32, "durations")
         dout = np.zeros((B, ld), np.int32) if want_out else None
         p = ffi.ProsodyC()
-        p.id_scales = sc.ctypes.data_as(C.POINTER(C.c_float)) if sc is not None else None
-        p.durations_in = din.ctypes.data_as(C.POINTER(C.c_int32)) if din is not None else None
-        p.durations_out = dout.ctypes.data_as(C.POINTER(C.c_int32)) if dout is not None else None
+        p.id_scales = ffi.f32p(sc)
+        p.durations_in = ffi.i32p(din)
+        p.durations_out = ffi.i32p(dout)
         p.ld = ld
         return p, (sc, din, dout)
 
@@ -417,16 +387,9 @@ class Engine:
                        seed=0, audio_settings=None, flags=0) -> MelBatch:
         """Pointer-level entry (ids/noise may be device memory with flags=ffi.IN_DEVICE)."""
         lens = np.ascontiguousarray(lens, np.int32)
-        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
         out = C.c_void_p()
-        ffi.check(
-            self.lib,
-            self.lib.mi355tts_glow_infer(
-                self._ctx, model, ids_ptr, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), ids_ld,
-                float(noise_scale), float(length_scale), noise_ptr, noise_ld, int(seed) & (2 ** 64 - 1),
-                C.byref(a) if a is not None else None, flags, C.byref(out),
-            ),
-        )
+        head = self._glow_head((model,), ids_ptr, lens, ids_ld, noise_scale, length_scale, noise_ptr, noise_ld, seed)
+        ffi.check(self.lib, self.lib.mi355tts_glow_infer(*head, ffi.audio_ref(audio_settings), flags, C.byref(out)))
         return MelBatch(self, out.value)
 
     def hifigan_infer_raw(self, vocoder, mel: MelBatch, f32_ptr, i16_ptr, wav_ld, flags=0, denoiser_strength=0.0,
@@ -439,16 +402,12 @@ class Engine:
                        pad_after=0, flags=0) -> np.ndarray:
         """Pointer-level fused call (`mi355tts_synthesize`); returns the per-row mel frame counts."""
         lens = np.ascontiguousarray(lens, np.int32)
-        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
         frames = np.zeros(len(lens), np.int32)
+        head = self._glow_head((glow, vocoder), ids_ptr, lens, ids_ld, noise_scale, length_scale, noise_ptr, noise_ld, seed)
         ffi.check(
             self.lib,
-            self.lib.mi355tts_synthesize(
-                self._ctx, glow, vocoder, ids_ptr, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), ids_ld,
-                float(noise_scale), float(length_scale), noise_ptr, noise_ld, int(seed) & (2 ** 64 - 1),
-                C.byref(a) if a is not None else None, float(denoiser_strength), int(pad_before), int(pad_after),
-                frames.ctypes.data_as(C.POINTER(C.c_int32)), f32_ptr, i16_ptr, wav_ld, flags,
-            ),
+            self.lib.mi355tts_synthesize(*head, ffi.audio_ref(audio_settings), float(denoiser_strength), int(pad_before), int(pad_after),
+                                         ffi.i32p(frames), f32_ptr, i16_ptr, wav_ld, flags),
         )
         return frames
 
@@ -462,19 +421,8 @@ class Engine:
         (`mi355tts_synthesize`): row b holds pad_before zeros, frames[b]*hop samples, then zeros.
         The frame count is data dependent; the output buffer is sized from a guess and the call
         is repeated once with the exact size in the rare case the guess was too small."""
-        rows = [np.asarray(ids, np.int64)] if isinstance(ids, np.ndarray) and ids.ndim == 1 else [np.asarray(r, np.int64) for r in ids]
-        B = len(rows)
-        lens = np.array([len(r) for r in rows], np.int32)
-        ld = int(lens.max())
-        packed = np.zeros((B, ld), np.int64)
-        for b, r in enumerate(rows):
-            packed[b, : len(r)] = r
-        nz_ptr, nz_ld = None, 0
-        if noise is not None:
-            noise = np.ascontiguousarray(noise, np.float32)
-            if noise.ndim == 2:
-                noise = noise[None]
-            nz_ptr, nz_ld = noise.ctypes.data, noise.shape[2]
+        packed, lens, B, ld = self._ids_in(ids)
+        noise, nz_ptr, nz_ld = self._noise_in(noise, B)
         hop = self.hop(vocoder)
         pads = int(pad_before) + int(pad_after)
         cap = int(ld * frames_per_id_guess * max(length_scale, 0.05)) * hop + pads
@@ -482,26 +430,17 @@ class Engine:
         if id_scales is not None or durations is not None or return_durations:
             pros, keep = self._prosody(lens, ld, id_scales, durations, return_durations)
             if durations is not None:  # the frame count is known: no guessing
-                cap = max(int(keep[1].sum(axis=1).max()), 1) * hop + pads
-        lens_c = lens.ctypes.data_as(C.POINTER(C.c_int32))
-        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
+                cap = max(int(keep[1].sum(axis=1).max(initial=0)), 1) * hop + pads
+        a = ffi.audio_ref(audio_settings)
         frames = np.zeros(B, np.int32)
         spk = self._speaker_array(speaker_ids, B) if speaker_ids is not None else None
+        head = self._glow_head((glow, vocoder), packed.ctypes.data, lens, ld, noise_scale, length_scale, nz_ptr, nz_ld, seed)
         for attempt in range(2):
             f32 = np.empty((B, cap), np.float32) if want_float else None
             i16 = np.empty((B, cap), np.int16)
-            head = (self._ctx, glow, vocoder, packed.ctypes.data, lens_c, B, ld, float(noise_scale), float(length_scale), nz_ptr,
-                    nz_ld, int(seed) & (2 ** 64 - 1))
-            tail = (C.byref(a) if a is not None else None, float(denoiser_strength), int(pad_before), int(pad_after),
-                    frames.ctypes.data_as(C.POINTER(C.c_int32)), ffi.ptr(f32), i16.ctypes.data, cap, 0)
-            if pros is not None:
-                rc = self.lib.mi355tts_synthesize_prosody(*head, spk.ctypes.data_as(C.POINTER(C.c_int32)) if spk is not None else None,
-                                                          *tail, C.byref(pros))
-            elif spk is not None:
-                rc = self.lib.mi355tts_synthesize_speakers(*head, spk.ctypes.data_as(C.POINTER(C.c_int32)), *tail)
-            else:
-                rc = self.lib.mi355tts_synthesize(*head, *tail)
-            n = int(frames.max()) * hop + pads
+            tail = (a, float(denoiser_strength), int(pad_before), int(pad_after), ffi.i32p(frames), ffi.ptr(f32), i16.ctypes.data, cap, 0)
+            rc = self._glow_call("mi355tts_synthesize", head, None, spk, tail, pros)
+            n = int(frames.max(initial=0)) * hop + pads  # (no rows: the library has refused, `check` below says why)
             if rc == -4 and attempt == 0 and n > cap:  # MI355TTS_ERR_TOO_SMALL: frames_out holds the real counts
                 cap = n
                 continue
@@ -528,9 +467,7 @@ class Engine:
 
     def worker_queue_groups(self) -> typing.List[int]:
         """The hardware-queue group of every worker, in creation order (`mi355tts_worker_queue_groups`; -1 = not probed)."""
-        import ctypes
-
-        buf = (ctypes.c_int32 * 256)()
+        buf = (C.c_int32 * 256)()
         n = self.lib.mi355tts_worker_queue_groups(self._ctx, buf, 256)
         if n < 0:
             ffi.check(self.lib, n)
@@ -541,31 +478,19 @@ class Engine:
         if mel.ndim == 2:
             mel = mel[None]
         B, M, ld = mel.shape
-        fr = np.full(B, ld, np.int32) if frames is None else np.asarray(frames, np.int32)
-        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
-        out = C.c_void_p()
-        ffi.check(
-            self.lib,
-            self.lib.mi355tts_mel_from_buffer(
-                self._ctx, mel.ctypes.data, fr.ctypes.data_as(C.POINTER(C.c_int32)), B, M, ld,
-                C.byref(a) if a is not None else None, 0, C.byref(out),
-            ),
-        )
-        return MelBatch(self, out.value)
+        return self._mel_from_buffer(mel.ctypes.data, np.full(B, ld, np.int32) if frames is None else frames, B, M, ld, audio_settings, 0)
 
     def mel_from_device(self, device_ptr: int, frames, channels: int, ld: int, audio_settings=None) -> MelBatch:
         """Wrap a mel that already lives in device memory ([B][channels][ld] fp32, e.g. a
         torch tensor's `data_ptr()`); `frames` gives each row's valid length."""
         fr = np.ascontiguousarray(frames, np.int32)
-        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
+        return self._mel_from_buffer(C.c_void_p(int(device_ptr)), fr, len(fr), channels, ld, audio_settings, ffi.IN_DEVICE)
+
+    def _mel_from_buffer(self, mel_ptr, frames, B: int, channels: int, ld: int, audio_settings, flags: int) -> MelBatch:
+        fr = np.ascontiguousarray(frames, np.int32)
         out = C.c_void_p()
-        ffi.check(
-            self.lib,
-            self.lib.mi355tts_mel_from_buffer(
-                self._ctx, C.c_void_p(int(device_ptr)), fr.ctypes.data_as(C.POINTER(C.c_int32)), len(fr), int(channels), int(ld),
-                C.byref(a) if a is not None else None, ffi.IN_DEVICE, C.byref(out),
-            ),
-        )
+        ffi.check(self.lib, self.lib.mi355tts_mel_from_buffer(self._ctx, mel_ptr, ffi.i32p(fr), int(B), int(channels), int(ld),
+                                                             ffi.audio_ref(audio_settings), flags, C.byref(out)))
         return MelBatch(self, out.value)
 
     def hop(self, vocoder: int) -> int:
@@ -597,12 +522,7 @@ class Engine:
         f32 = np.empty((mel.batch, n), np.float32)
         buf = C.create_string_buffer(1 << 16)
         ffi.check(self.lib, self.lib.mi355tts_hifigan_infer_taps(self._ctx, vocoder, mel.handle, ffi.ptr(f32), n, buf, 1 << 16))
-        taps = json.loads(buf.value.decode("ascii"))
-        for i, t in enumerate(taps):
-            x = np.empty((mel.batch, t["channels"], t["ld"]), np.float32)
-            ffi.check(self.lib, self.lib.mi355tts_voc_tap_copy(self._ctx, i, ffi.ptr(x), x.size))
-            t["x"] = x
-        return f32, taps
+        return f32, self._taps_out(buf, mel.batch)
 
     # ---- Griffin-Lim -----------------------------------------------------------
     def load_griffin_lim(self, mel_basis: np.ndarray, mel_scaling: float = 1000.0, iterations: int = 60) -> int:
@@ -612,9 +532,7 @@ class Engine:
         if basis.ndim != 2 or basis.shape[1] != 513:
             raise ValueError(f"mel_basis must be [num_mels, 513] (1024-point frames), got {basis.shape}")
         p = ffi.GriffinLimParamsC(int(basis.shape[0]), float(mel_scaling), int(iterations))
-        model = C.c_int()
-        ffi.check(self.lib, self.lib.mi355tts_load_griffin_lim(self._ctx, C.byref(p), basis.ctypes.data, C.byref(model)))
-        return int(model.value)
+        return self._loaded(self.lib.mi355tts_load_griffin_lim, C.byref(p), basis.ctypes.data)
 
     def griffin_lim_infer(self, model: int, mel: MelBatch, phase0: typing.Optional[np.ndarray] = None, seed: int = 0,
                           iterations: int = 0, want_float: bool = True, want_int16: bool = False, want_phase: bool = False):
@@ -636,7 +554,7 @@ class Engine:
         ph = np.empty((B, 513, T), np.float32) if want_phase else None
         ffi.check(
             self.lib,
-            self.lib.mi355tts_griffin_lim_infer(self._ctx, int(model), mel.handle, ffi.ptr(phase0), int(seed) & (2 ** 64 - 1),
+            self.lib.mi355tts_griffin_lim_infer(self._ctx, int(model), mel.handle, ffi.ptr(phase0), ffi.u64(seed),
                                                 ffi.ptr(ph), ffi.ptr(f32), ffi.ptr(i16), n, int(iterations), 0),
         )
         return f32, i16, ph
@@ -645,7 +563,7 @@ class Engine:
                               iterations=0, flags=0):
         """Pointer-level entry (`flags`: ffi.IN_DEVICE for phase0, ffi.OUT_DEVICE for phase_out and the waveforms)."""
         ffi.check(self.lib, self.lib.mi355tts_griffin_lim_infer(self._ctx, int(model), mel.handle, phase0_ptr,
-                                                                int(seed) & (2 ** 64 - 1), phase_out_ptr, f32_ptr, i16_ptr,
+                                                                ffi.u64(seed), phase_out_ptr, f32_ptr, i16_ptr,
                                                                 int(wav_ld), int(iterations), int(flags)))
 
     # ---- mel analysis ------------------------------------------------------------
@@ -662,9 +580,7 @@ class Engine:
         if mag_eps is None:
             mag_eps = 1e-9 if fr == ffi.FRAMING_HIFIGAN else 0.0
         p = ffi.AnalysisParamsC(int(basis.shape[0]), fr, float(mag_eps))
-        model = C.c_int()
-        ffi.check(self.lib, self.lib.mi355tts_load_analysis(self._ctx, C.byref(p), basis.ctypes.data, C.byref(model)))
-        return int(model.value)
+        return self._loaded(self.lib.mi355tts_load_analysis, C.byref(p), basis.ctypes.data)
 
     # ---- audio in, rows out ---------------------------------------------------------
     @staticmethod
@@ -682,13 +598,18 @@ class Engine:
         if audio.ndim != 2:
             raise ValueError("audio: [N] or [B, N]")
         B, N = audio.shape
-        n = np.full(B, N, np.int64) if samples is None else np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        n = np.full(B, N, np.int64) if samples is None else Engine._samples(samples)
         if n.shape != (B,):
             raise ValueError("samples: one count per row")
         if N == 0:  # (an empty array has no address worth passing: one sample nobody reads stands in)
             audio = np.zeros((B, 1), audio.dtype)
         ptr = audio.ctypes.data
         return (audio, flat, B, N, n, None, ptr) if audio.dtype == np.int16 else (audio, flat, B, N, n, ptr, None)
+
+    @staticmethod
+    def _samples(samples) -> np.ndarray:
+        """The rows' sample counts as every call that reads audio hands them to the library: int64 [B], contiguous."""
+        return np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
 
     @staticmethod
     def _rows_out(flat: bool, *rows):
@@ -704,13 +625,12 @@ class Engine:
 
     def mel_from_audio_raw(self, model: int, f32_ptr, i16_ptr, samples, wav_ld: int, audio_settings=None, flags: int = 0) -> MelBatch:
         """Pointer-level entry: exactly one of the two pointers, [B][wav_ld] (device memory with flags=ffi.IN_DEVICE)."""
-        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
-        a = ffi.audio_settings_c(audio_settings) if audio_settings is not None else None
+        n = self._samples(samples)
         out = C.c_void_p()
         ffi.check(
             self.lib,
-            self.lib.mi355tts_mel_from_audio(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n),
-                                             int(wav_ld), C.byref(a) if a is not None else None, int(flags), C.byref(out)),
+            self.lib.mi355tts_mel_from_audio(self._ctx, int(model), f32_ptr, i16_ptr, ffi.i64p(n), len(n),
+                                             int(wav_ld), ffi.audio_ref(audio_settings), int(flags), C.byref(out)),
         )
         return MelBatch(self, out.value)
 
@@ -722,9 +642,7 @@ class Engine:
         if len(taps) % 2 != 1:
             raise ValueError(f"taps must be [2 H + 1] (a symmetric prototype around its centre), got {len(taps)}")
         p = ffi.ResamplerParamsC(int(up), int(down), len(taps) // 2)
-        model = C.c_int()
-        ffi.check(self.lib, self.lib.mi355tts_load_resampler(self._ctx, C.byref(p), taps.ctypes.data, C.byref(model)))
-        return int(model.value)
+        return self._loaded(self.lib.mi355tts_load_resampler, C.byref(p), taps.ctypes.data)
 
     def resample_length(self, model: int, samples: int) -> int:
         """`mi355tts_resample_length`: ceil(samples * up / down)."""
@@ -750,13 +668,13 @@ class Engine:
                      pcm_mode: int = 0, flags: int = 0) -> np.ndarray:
         """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE), at least one output
         pointer [B][out_ld] (device memory with ffi.OUT_DEVICE); returns the rows' output lengths, int64 [B]."""
-        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        n = self._samples(samples)
         out = np.zeros(len(n), np.int64)
         ffi.check(
             self.lib,
-            self.lib.mi355tts_resample(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+            self.lib.mi355tts_resample(self._ctx, int(model), f32_ptr, i16_ptr, ffi.i64p(n), len(n), int(in_ld),
                                        out_f32_ptr, out_i16_ptr, int(out_ld), int(pcm_mode),
-                                       out.ctypes.data_as(C.POINTER(C.c_int64)), int(flags)),
+                                       ffi.i64p(out), int(flags)),
         )
         return out
 
@@ -771,9 +689,7 @@ class Engine:
                 raise ValueError(f"{name}: {n} coefficients")
             setattr(p, name, (C.c_float * n)(*vals.tolist()))
         p.block, p.hop = int(block), int(hop)
-        model = C.c_int()
-        ffi.check(self.lib, self.lib.mi355tts_load_loudness(self._ctx, C.byref(p), C.byref(model)))
-        return int(model.value)
+        return self._loaded(self.lib.mi355tts_load_loudness, C.byref(p))
 
     def loudness(self, model: int, audio: np.ndarray, samples=None, target: float = float("nan"), ceiling: float = 1.0,
                  max_gain_db: float = 30.0, want_float: bool = False, want_int16: bool = False, want_weighted: bool = False) -> dict:
@@ -794,11 +710,11 @@ class Engine:
         """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE); the output pointers
         [B][out_ld] and the weighted rows [B][in_ld] are optional (device memory with ffi.OUT_DEVICE); returns the rows'
         (lufs, gain, peak), float32 [B] each."""
-        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        n = self._samples(samples)
         res = np.zeros((3, len(n)), np.float32)
         ffi.check(
             self.lib,
-            self.lib.mi355tts_loudness(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+            self.lib.mi355tts_loudness(self._ctx, int(model), f32_ptr, i16_ptr, ffi.i64p(n), len(n), int(in_ld),
                                        float(target), float(ceiling), float(max_gain_db), out_f32_ptr, out_i16_ptr, int(out_ld),
                                        res[0].ctypes.data, res[1].ctypes.data, res[2].ctypes.data, weighted_ptr, int(flags)),
         )
@@ -819,9 +735,7 @@ class Engine:
                 raise ValueError(f"taps must be [2 H + 1] (a symmetric prototype around its centre), got {len(taps)}")
             half_len = len(taps) // 2
         p = ffi.LimiterParamsC(int(oversample), half_len, len(window) - 1, float(release))
-        model = C.c_int()
-        ffi.check(self.lib, self.lib.mi355tts_load_limiter(self._ctx, C.byref(p), ffi.ptr(taps), window.ctypes.data, C.byref(model)))
-        return int(model.value)
+        return self._loaded(self.lib.mi355tts_load_limiter, C.byref(p), ffi.ptr(taps), window.ctypes.data)
 
     def limit(self, model: int, audio: np.ndarray, samples=None, gain=None, ceiling: float = 1.0, want_float: bool = False,
               want_int16: bool = False, want_curve: bool = False) -> dict:
@@ -844,14 +758,14 @@ class Engine:
         """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE); `gain`: float32 [B] or
         None; the output pointers [B][out_ld] and the curve [B][in_ld] are optional (device memory with ffi.OUT_DEVICE); returns
         the rows' (true_peak, min_gain), float32 [B] each."""
-        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        n = self._samples(samples)
         g = None if gain is None else np.ascontiguousarray(gain, np.float32).reshape(-1)
         if g is not None and g.shape != n.shape:
             raise ValueError("gain: one per row")
         res = np.zeros((2, len(n)), np.float32)
         ffi.check(
             self.lib,
-            self.lib.mi355tts_limit(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+            self.lib.mi355tts_limit(self._ctx, int(model), f32_ptr, i16_ptr, ffi.i64p(n), len(n), int(in_ld),
                                     ffi.ptr(g), float(ceiling), out_f32_ptr, out_i16_ptr, int(out_ld), res[0].ctypes.data,
                                     res[1].ctypes.data, curve_ptr, int(flags)),
         )
@@ -863,9 +777,7 @@ class Engine:
         """`mi355tts_load_pitch`: a YIN tracker from its rate, hop, window, lag range [tau_min, tau_max], threshold on d' and
         interpolation switch (`larynx_amd.pitch.PitchTracker` derives them from a frequency range).  `unload` frees it."""
         p = ffi.PitchParamsC(int(sample_rate), int(hop), int(window), int(tau_min), int(tau_max), float(threshold), int(bool(interpolate)))
-        model = C.c_int()
-        ffi.check(self.lib, self.lib.mi355tts_load_pitch(self._ctx, C.byref(p), C.byref(model)))
-        return int(model.value)
+        return self._loaded(self.lib.mi355tts_load_pitch, C.byref(p))
 
     def pitch_frames(self, model: int, samples: int) -> int:
         """`mi355tts_pitch_frames`: floor(samples / hop)."""
@@ -889,10 +801,10 @@ class Engine:
                   cmnd_ptr=None, out_ld: int = 0, flags: int = 0) -> None:
         """Pointer-level entry: exactly one input pointer [B][in_ld] (device memory with ffi.IN_DEVICE); the planes [B][out_ld]
         (at least one of the first three) and the d' rows [B][out_ld][tau_max + 1] (device memory with ffi.OUT_DEVICE)."""
-        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        n = self._samples(samples)
         ffi.check(
             self.lib,
-            self.lib.mi355tts_pitch(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+            self.lib.mi355tts_pitch(self._ctx, int(model), f32_ptr, i16_ptr, ffi.i64p(n), len(n), int(in_ld),
                                     f0_ptr, periodicity_ptr, level_ptr, cmnd_ptr, int(out_ld), int(flags)),
         )
 
@@ -904,9 +816,7 @@ class Engine:
         both alive; `unload` frees it."""
         window = np.ascontiguousarray(window, np.float32).reshape(-1)
         p = ffi.ShiftParamsC(int(up), int(down), len(window), int(pitch), int(resampler))
-        model = C.c_int()
-        ffi.check(self.lib, self.lib.mi355tts_load_shift(self._ctx, C.byref(p), window.ctypes.data, C.byref(model)))
-        return int(model.value)
+        return self._loaded(self.lib.mi355tts_load_shift, C.byref(p), window.ctypes.data)
 
     def shift_length(self, model: int, samples: int) -> int:
         """`mi355tts_shift_length`: a row's delivered length: `samples` (PITCH mode) or ceil(samples * up / down) (TEMPO)."""
@@ -943,13 +853,13 @@ class Engine:
         """Pointer-level entry: exactly one input pointer [B][in_ld] and optionally positions_in int32 [B][pos_ld] (device memory
         with ffi.IN_DEVICE); at least one output pointer [B][out_ld], optionally positions int32 [B][pos_ld] and f0 [B][f0_ld]
         (device memory with ffi.OUT_DEVICE); returns the rows' delivered lengths, int64 [B]."""
-        n = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1))
+        n = self._samples(samples)
         out = np.zeros(len(n), np.int64)
         ffi.check(
             self.lib,
-            self.lib.mi355tts_shift(self._ctx, int(model), f32_ptr, i16_ptr, n.ctypes.data_as(C.POINTER(C.c_int64)), len(n), int(in_ld),
+            self.lib.mi355tts_shift(self._ctx, int(model), f32_ptr, i16_ptr, ffi.i64p(n), len(n), int(in_ld),
                                     positions_in_ptr, out_f32_ptr, out_i16_ptr, int(out_ld), int(pcm_mode), positions_ptr, int(pos_ld),
-                                    f0_ptr, int(f0_ld), out.ctypes.data_as(C.POINTER(C.c_int64)), int(flags)),
+                                    f0_ptr, int(f0_ld), ffi.i64p(out), int(flags)),
         )
         return out
 
@@ -965,7 +875,7 @@ class Engine:
         ffi.check(
             self.lib,
             self.lib.mi355tts_op_conv1d(
-                self._ctx, x.ctypes.data, B, Cin, L, None if ln is None else ln.ctypes.data_as(C.POINTER(C.c_int32)),
+                self._ctx, x.ctypes.data, B, Cin, L, ffi.i32p(ln),
                 w.ctypes.data, ffi.ptr(b), Cout, K, int(dilation), float(in_slope), int(out_act), y.ctypes.data,
             ),
         )
@@ -975,7 +885,7 @@ class Engine:
         """[B, channels, T] draws of the device noise generator (what `glow_infer` adds when no
         explicit noise tensor is given)."""
         out = np.empty((B, channels, T), np.float32)
-        ffi.check(self.lib, self.lib.mi355tts_op_gauss_noise(self._ctx, int(seed) & (2 ** 64 - 1), B, channels, T, out.ctypes.data))
+        ffi.check(self.lib, self.lib.mi355tts_op_gauss_noise(self._ctx, ffi.u64(seed), B, channels, T, out.ctypes.data))
         return out
 
     def denoise(self, wav: np.ndarray, bias_spec: np.ndarray, strength: float) -> np.ndarray:
@@ -1031,10 +941,14 @@ class Engine:
         ffi.check(self.lib, self.lib.mi355tts_profile_event_overhead(self._ctx, int(pairs), C.byref(us)))
         return float(us.value)
 
-    def profile(self) -> dict:
-        buf = C.create_string_buffer(4096)
-        ffi.check(self.lib, self.lib.mi355tts_profile_json(self._ctx, buf, 4096))
+    def _json(self, fn, cap: int) -> dict:
+        """What the getter `fn(ctx, buf, cap)` renders."""
+        buf = C.create_string_buffer(cap)
+        ffi.check(self.lib, fn(self._ctx, buf, cap))
         return json.loads(buf.value.decode("ascii"))
+
+    def profile(self) -> dict:
+        return self._json(self.lib.mi355tts_profile_json, 4096)
 
     def get_call_coalesce_default(self) -> int:
         """The library's built-in default of option `call_coalesce` (`mi355tts_call_coalesce_default`)."""
@@ -1042,9 +956,7 @@ class Engine:
 
     def profile_kernels(self) -> dict:
         """The profiled launches per kernel NAME and sub-key (`mi355tts_profile_kernels_json`): {class: {"name/sub": {...}}}."""
-        buf = C.create_string_buffer(32768)
-        ffi.check(self.lib, self.lib.mi355tts_profile_kernels_json(self._ctx, buf, 32768))
-        return json.loads(buf.value.decode("ascii"))
+        return self._json(self.lib.mi355tts_profile_kernels_json, 32768)
 
     def dispatch_selfcheck(self) -> dict:
         """The one-off check of the dispatch-order assumption (`mi355tts_dispatch_selfcheck`): runs it if it has not run."""
@@ -1055,6 +967,4 @@ class Engine:
 
     def kernel_counts(self) -> dict:
         """Launches per kernel name since the last `profile_reset` (`mi355tts_kernel_counts_json`; always counted)."""
-        buf = C.create_string_buffer(4096)
-        ffi.check(self.lib, self.lib.mi355tts_kernel_counts_json(self._ctx, buf, 4096))
-        return json.loads(buf.value.decode("ascii"))
+        return self._json(self.lib.mi355tts_kernel_counts_json, 4096)

@@ -375,3 +375,22 @@ def manifest(lib: C.CDLL, hp_c) -> typing.List[typing.Tuple[str, int]]:
 
 def ptr(a: typing.Optional[np.ndarray]) -> typing.Optional[int]:
     return None if a is None else a.ctypes.data
+
+
+def _typed(ctype):
+    p = C.POINTER(ctype)
+    return lambda a: None if a is None else a.ctypes.data_as(p)
+
+
+# an array of that dtype (or None) as the typed pointer the signatures above ask for; it holds while the array is held
+i32p, i64p, u64p, f32p = _typed(C.c_int32), _typed(C.c_int64), _typed(C.c_uint64), _typed(C.c_float)
+
+
+def u64(seed) -> int:
+    """A seed of any sign or size as the uint64_t the library takes."""
+    return int(seed) & (2 ** 64 - 1)
+
+
+def audio_ref(s):
+    """The optional `const mi355tts_audio_settings*` of a call: NULL for None (the reference holds its struct)."""
+    return None if s is None else C.byref(audio_settings_c(s))
